@@ -18,7 +18,14 @@ Default sharding: whole volumes (every rank segments its own CT, no data-path co
 `--shard tiles|models` lets the N GPUs share every volume (strong scaling; tile rows split with an RCCL exchange of the
 overlap slabs of the fp16 accumulators, or the part models dealt out to the ranks).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--models total+bca|total] [--batch 8] [--no-cpu]
+A plain run sets up, warms up, times the K steps and prints the line; the figures it carries beside the headline
+(`roofline`, `hbm_stages`, `hbm_roofline`, `kernel_variants`) come from the timed steps themselves.  `--full` adds everything
+that takes runs of its own: the same loop without event profiling, the bare-MFMA rates, the `total` half alone, host-to-host,
+configs[2], two lanes, the structured-phantom stages, the parity sample, the CPU baseline and the exact mode (each can still be
+left out with its `--no-*` option).  `--dump-outputs DIR` writes what the last timed step computed (see dump_outputs).
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--models total+bca|total] [--batch 8] [--full [--no-cpu]]
+                    [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -84,7 +91,81 @@ def parse_args():
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="torch.distributed backend for N>1 (nccl = RCCL; gloo lets several ranks share one GPU for validation)")
     ap.add_argument("--dump", type=str, default=None, help="write per-kernel-class timings to this JSON file")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extras that take runs of their own (no-event loop, bare-MFMA rates, total alone, host-to-host, "
+                         "configs[2], two lanes, phantom stages, parity sample, CPU baseline, exact mode); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, < 64 MB in all)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+DUMP_VOXELS = 1 << 21          # voxels of each label volume in the dump (8 MB as float32)
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 20261015
+
+
+def _numbers(obj, acc):
+    """The numeric leaves of a nested dict / list in a fixed order (dict keys sorted) as floats; strings are left out, None
+    stays None."""
+    if isinstance(obj, dict):
+        for k in sorted(obj, key=str):
+            _numbers(obj[k], acc)
+    elif isinstance(obj, (list, tuple)):
+        for v in obj:
+            _numbers(v, acc)
+    elif isinstance(obj, np.ndarray):
+        if obj.dtype.kind in "biuf":
+            acc.extend(np.asarray(obj, np.float64).ravel().tolist())
+    elif obj is None:
+        acc.append(None)
+    elif isinstance(obj, (bool, int, float, np.bool_, np.integer, np.floating)):
+        acc.append(float(obj))
+    return acc
+
+
+def dump_outputs(out_dir, volumes, tables):
+    """What one step returns to its caller, as DIR/<name>.npy, comparable output for output between two builds:
+      <volume>.npy         float32: the labels at DUMP_VOXELS distinct voxel indices drawn from a fixed seed (the whole volume when
+                           it is smaller), flat C order of the array the caller receives
+      <volume>_counts.npy  float64: voxels per label value over the WHOLE volume
+      <table>.npy          float64: the numeric leaves of the returned dict (keys sorted, strings left out), 0 where a leaf
+                           is None, NaN or infinite
+      <table>_nonfinite.npy  float64, one per leaf: 0 finite, 1 NaN, 2 +inf, 3 -inf, 4 None (every file holds finite values only)
+    `volumes`: name -> host label array; `tables`: name -> dict.  Returns {file name: bytes}."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for name, a in volumes.items():
+        flat = np.ascontiguousarray(a).reshape(-1)
+        if flat.dtype.kind != "u":
+            raise TypeError(f"dump_outputs: {name} is {flat.dtype}, label volumes are unsigned")
+        if flat.size > DUMP_VOXELS:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(flat.size, size=DUMP_VOXELS, replace=False, shuffle=False))
+            flat_s = flat[idx]
+        else:
+            flat_s = flat
+        arrays[name] = flat_s.astype(np.float32)
+        arrays[name + "_counts"] = np.bincount(flat, minlength=256).astype(np.float64)
+    for name, t in tables.items():
+        leaves = _numbers(t, [])
+        vals = np.array([np.nan if v is None else v for v in leaves], np.float64)
+        kind = np.select([np.array([v is None for v in leaves], bool), np.isnan(vals), vals == np.inf, vals == -np.inf],
+                         [4, 1, 2, 3], 0)
+        arrays[name] = np.where(kind == 0, vals, 0.0)
+        arrays[name + "_nonfinite"] = kind.astype(np.float64)
+    bad = [name for name, a in arrays.items() if not np.isfinite(a).all()]
+    if bad:
+        raise ValueError(f"dump_outputs: non-finite values in {bad}")
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError(f"dump_outputs: {total} bytes exceed {DUMP_MAX_BYTES}")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name + ".npy": a.nbytes for name, a in arrays.items()}
 
 
 def self_launch(args):
@@ -486,9 +567,10 @@ def main():
             stage_log[name] = stage_log.get(name, 0.0) + time.perf_counter() - t0
         return time.perf_counter()
 
-    def step(d_in, download=False, run=None):
+    def step(d_in, download=False, run=None, keep=None):
         """One CT through total -> total measurements -> bca (boa_hip/lanes.py).  `download`: also bring the label volumes to
-        the host.  `run`: the TotalBcaRunner (default: the one-stream runner of the timed region)."""
+        the host.  `run`: the TotalBcaRunner (default: the one-stream runner of the timed region).  `keep`: a dict that
+        receives the whole result, label volumes left on the device for the caller to free."""
         clock = [time.perf_counter()]
 
         def on_stage(name):
@@ -497,8 +579,11 @@ def main():
         out = (run or runner).run_resident(d_in, affine, (1.5, 1.5, 1.5), on_stage)
         outs = [out[k] for k in ("total", "body_parts", "body_regions", "tissues") if k in out]
         host = [a.download() for a in outs] if download else None
-        for a in outs:
-            a.free()
+        if keep is not None:
+            keep.update(out)
+        else:
+            for a in outs:
+                a.free()
         return out["total_measurements"], out.get("bca_measurements"), host
 
     def barrier():
@@ -525,9 +610,11 @@ def main():
     barrier()
     t_start = time.perf_counter()
     step_s = []
-    for _ in range(args.steps):
+    last = {} if args.dump_outputs else None
+    for i in range(args.steps):
         t_s = time.perf_counter()
-        meas, bca_js, _ = step(d_ct)     # (a step ends with the download of its last table: it has completed on the device)
+        # (a step ends with the download of its last table: it has completed on the device)
+        meas, bca_js, _ = step(d_ct, keep=last if i == args.steps - 1 else None)
         step_s.append(time.perf_counter() - t_s)
     barrier()
     elapsed = time.perf_counter() - t_start
@@ -546,10 +633,19 @@ def main():
         if ranks_seen != args.gpus:
             print(f"bench.py: {ranks_seen} ranks answered the all-reduce, --gpus {args.gpus}", file=sys.stderr)
             sys.exit(2)
+    if last is not None:
+        vols = {k: v for k, v in last.items() if isinstance(v, DevArray)}
+        if rank == 0:
+            host = {k: np.array(v.download()) for k, v in vols.items()}
+            files = dump_outputs(args.dump_outputs, host, {k: v for k, v in last.items() if k not in vols})
+            log(f"outputs of the last timed step: {len(files)} files, {sum(files.values()) / 2 ** 20:.1f} MiB in {args.dump_outputs}")
+        for v in vols.values():
+            v.free()
+        last = None
 
     # the same loop without the per-launch HIP events (~33 k event records per step): what the events cost the headline
     no_events = None
-    if rank == 0 and args.gpus == 1 and not args.no_prof:
+    if args.full and rank == 0 and args.gpus == 1 and not args.no_prof:
         ctx.sync()
         tb = time.perf_counter()
         n_ne = max(5, args.steps)
@@ -561,7 +657,7 @@ def main():
     # what the matrix cores of this very GPU sustain with no memory traffic at all (outside the timed region, ~50 ms): the part
     # is power-limited under matrix load and the clock it holds depends on the operand bits
     attainable = None
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             attainable = {"pure_mfma_constant_operands_TFLOPs": ctx.mfma_peak(False), "pure_mfma_random_operands_TFLOPs": ctx.mfma_peak(True),
                           "note": "v_mfma_f32_32x32x16_f16 only, one wave per SIMD, 4 accumulator chains, no LDS / memory traffic; "
@@ -569,7 +665,7 @@ def main():
         except Exception as e:  # diagnostics only
             attainable = {"error": f"{type(e).__name__}: {e}"}
     total_only = None
-    if rank == 0 and args.models == "total+bca" and args.gpus == 1 and not args.no_h2h:
+    if args.full and rank == 0 and args.models == "total+bca" and args.gpus == 1 and not args.no_h2h:
         # the `total` half alone (configs[1] as round 1 reported it), outside the timed region: 2 volumes
         ctx.sync()
         tb = time.perf_counter()
@@ -578,7 +674,7 @@ def main():
         ctx.sync()
         total_only = {"volumes_per_s": 2.0 / (time.perf_counter() - tb), "steps": 2, "tile_forwards_per_volume": 625}
     h2h = None
-    if rank == 0 and not args.no_h2h and args.gpus == 1:
+    if args.full and rank == 0 and not args.no_h2h and args.gpus == 1:
         # PCIe-inclusive: upload the CT, download `total` + the three BCA label volumes (tables are host dicts already);
         # median of 5 volumes
         def host_to_host():
@@ -606,7 +702,7 @@ def main():
             h2h = {"error": f"{type(e).__name__}: {e}"}
 
     configs2 = None
-    if rank == 0 and with_bca and args.gpus == 1 and not args.no_c3 and list(shape) == [512, 512, 512]:
+    if args.full and rank == 0 and with_bca and args.gpus == 1 and not args.no_c3 and list(shape) == [512, 512, 512]:
         # configs[2] of BASELINE.json (the largest single-GPU configuration): one 512x512x768 whole-body volume, `total+bca`, same
         # predictors, same one-stream runner; 1 warm-up + 3 timed volumes, CT resident
         try:
@@ -630,7 +726,7 @@ def main():
             configs2 = {"error": f"{type(e).__name__}: {e}"}
         log(f"configs[2]: {configs2}")
     two_lanes = None
-    if rank == 0 and with_bca and args.gpus == 1 and not args.no_lanes:
+    if args.full and rank == 0 and with_bca and args.gpus == 1 and not args.no_lanes:
         # the product's two-lane mode (boa_hip/lanes.py): `total` + its measurements on this context's stream, both BCA nets +
         # post-processing + tissues on a second context (own stream, pool, predictors) of the same GPU; same kernels, same
         # results (tests/test_gpu_lanes.py).  Timed outside the headline region because the per-class HIP-event times of two
@@ -671,7 +767,7 @@ def main():
                     pass
         log(f"two lanes: {two_lanes}")
     phantom = None
-    if rank == 0 and args.gpus == 1 and not args.no_phantom:
+    if args.full and rank == 0 and args.gpus == 1 and not args.no_phantom:
         try:
             phantom = phantom_stages(ctx, shape, ct, log)
         except Exception as e:  # noqa: BLE001  (an extra must never cost the headline line)
@@ -774,13 +870,13 @@ def main():
             res["comm"] = dict(comm.stats(), note="rank 0's boa_comm_stats over the whole process (warm-up + timed steps): RCCL calls and bytes "
                                                   "sent or reduced; DESIGN.md section 6 tabulates the expected bytes per boundary")
         dev_tiles, close_parity = None, None
-        if not args.no_parity and args.gpus == 1:
+        if args.full and not args.no_parity and args.gpus == 1:
             try:
                 res["parity"], dev_tiles, close_parity = parity_sample(ctx, part_models[0][1], part_models[0][2], min(args.batch, 8), log,
                                                                        tile_forwards, elapsed / args.steps)
             except Exception as e:  # noqa: BLE001  (an extra must never cost the headline line)
                 res["parity"] = {"error": f"{type(e).__name__}: {e}"}
-        if not args.no_cpu and args.gpus == 1:
+        if args.full and not args.no_cpu and args.gpus == 1:
             res["cpu_baseline"], vs_oracle = cpu_baseline(part_models[0][3], args.cpu_tiles,
                                                           {"tile_forwards": tile_forwards, "class_voxels": class_voxels, "voxels": float(nvox),
                                                            "with_bca": with_bca, "shape": list(shape), "all_cores": args.cpu_all_cores}, log,
@@ -791,7 +887,7 @@ def main():
             res["cpu_baseline"] = None
         if close_parity is not None:
             close_parity()
-        if not args.no_exact and args.gpus == 1:
+        if args.full and not args.no_exact and args.gpus == 1:
             # The label-contract mode, MEASURED: one whole volume of the same workload with every network in the fp32 mode
             # (split precision on the matrix cores, csrc/net_x3.hip; labels of the CPU path: tests/test_gpu_production_geometry.py).
             # The production predictors are closed first (their weight sets and statistics tables are not needed any more; the
