@@ -6,8 +6,10 @@ documented behaviour of ITK's series reader / NIfTI writer; it is exercised agai
 only -- PARITY UNPINNED vs GDCM / SimpleITK.
 
 Scope (everything else raises, nothing is guessed):
-  * transfer syntaxes: implicit VR little endian (1.2.840.10008.1.2) and explicit VR little endian (1.2.840.10008.1.2.1), i.e.
-    uncompressed; encapsulated / deflated / big-endian files raise NotImplementedError;
+  * transfer syntaxes: implicit VR little endian (1.2.840.10008.1.2), explicit VR little endian (1.2.840.10008.1.2.1) and
+    JPEG Lossless Process 14 (1.2.840.10008.1.2.4.57, .70: encapsulated PixelData, one frame per file, decoded on the GPU for
+    the whole series in one call -- boa_hip/jpeg_lossless.py); other compressed, deflated and big-endian files raise
+    NotImplementedError;
   * single-frame, MONOCHROME2, SamplesPerPixel 1, BitsAllocated 16 (8 and 32 are read too);
   * one series per call: like `GetGDCMSeriesFileNames(dir)` without a series id, the FIRST series (smallest SeriesInstanceUID
     in sorted order) of the folder is taken, other series' files are ignored;
@@ -27,6 +29,8 @@ import struct
 from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
+
+from . import jpeg_lossless
 
 IMPLICIT_LE = "1.2.840.10008.1.2"
 EXPLICIT_LE = "1.2.840.10008.1.2.1"
@@ -181,10 +185,12 @@ def read_file(path, stop_before_pixels: bool = False) -> Dict[str, Any]:
             tsuid = _convert("UI", raw)
     if tsuid is None:
         raise DicomError(f"{path}: no TransferSyntaxUID in the file meta information")
-    if tsuid not in (IMPLICIT_LE, EXPLICIT_LE):
+    if tsuid not in (IMPLICIT_LE, EXPLICIT_LE) + jpeg_lossless.SYNTAXES:
         raise NotImplementedError(f"{path}: transfer syntax {tsuid} (compressed, deflated or big endian) is not supported; "
-                                  "only implicit / explicit VR little endian (uncompressed) are read")
-    explicit = tsuid == EXPLICIT_LE
+                                  "only implicit / explicit VR little endian (uncompressed) and JPEG Lossless (Process 14) "
+                                  "are read")
+    explicit = tsuid != IMPLICIT_LE
+    jpeg = tsuid in jpeg_lossless.SYNTAXES
     out["TransferSyntaxUID"] = tsuid
     out["_explicit"] = explicit
     want = set(TAGS)
@@ -192,6 +198,16 @@ def read_file(path, stop_before_pixels: bool = False) -> Dict[str, Any]:
         g, e = struct.unpack("<HH", buf[cur.pos:cur.pos + 4])
         if stop_before_pixels and (g, e) >= (0x7FE0, 0x0010):
             break
+        if jpeg and (g, e) == (0x7FE0, 0x0010):     # PS3.5 A.4: encapsulated, undefined length, explicit VR OB / OW
+            vr_b = buf[cur.pos + 4:cur.pos + 6]
+            length = struct.unpack_from("<I", buf, cur.pos + 8)[0] if cur.pos + 12 <= len(buf) else 0
+            if vr_b not in (b"OB", b"OW") or length != 0xFFFFFFFF:
+                raise NotImplementedError(f"{path}: transfer syntax {tsuid} with native (not encapsulated) PixelData is "
+                                          "not read")
+            frame, cur.pos = jpeg_lossless.read_encapsulated(buf, cur.pos + 12, str(path))
+            out["PixelData"] = jpeg_lossless.CompressedFrame(frame)
+            out["PixelData"].transfer_syntax = tsuid
+            continue
         tag, vr, raw = _read_element(cur, explicit, want)
         if tag in TAGS and vr != "SQ":
             kw, dvr = TAGS[tag]
@@ -284,8 +300,8 @@ def _output_dtype(ds: Dict[str, Any]) -> np.dtype:
     return np.dtype(np.float64)
 
 
-def _slice_pixels(ds: Dict[str, Any]) -> np.ndarray:
-    rows, cols, alloc = int(ds["Rows"]), int(ds["Columns"]), int(ds["BitsAllocated"])
+def _pixel_dtype(ds: Dict[str, Any]) -> np.dtype:
+    alloc = int(ds["BitsAllocated"])
     if int(ds.get("SamplesPerPixel", 1)) != 1 or ds.get("PhotometricInterpretation", "MONOCHROME2") != "MONOCHROME2":
         raise NotImplementedError(f"{ds['_path']}: only MONOCHROME2 single-sample images are read")
     if int(ds.get("NumberOfFrames", 1) or 1) != 1:
@@ -293,11 +309,23 @@ def _slice_pixels(ds: Dict[str, Any]) -> np.ndarray:
     if alloc not in (8, 16, 32):
         raise NotImplementedError(f"{ds['_path']}: BitsAllocated {alloc}")
     signed = int(ds.get("PixelRepresentation", 0)) == 1
-    dt = np.dtype({8: "i1" if signed else "u1", 16: "<i2" if signed else "<u2", 32: "<i4" if signed else "<u4"}[alloc])
+    return np.dtype({8: "i1" if signed else "u1", 16: "<i2" if signed else "<u2", 32: "<i4" if signed else "<u4"}[alloc])
+
+
+def _slice_pixels(ds: Dict[str, Any], decoded: Optional[np.ndarray] = None) -> np.ndarray:
+    """Stored values of one slice; `decoded`: the decoded samples (uint16 bit patterns) of a compressed slice."""
+    rows, cols, alloc = int(ds["Rows"]), int(ds["Columns"]), int(ds["BitsAllocated"])
+    dt = _pixel_dtype(ds)
+    signed = dt.kind == "i"
     raw = ds.get("PixelData")
-    if raw is None or len(raw) < rows * cols * dt.itemsize:
+    if isinstance(raw, jpeg_lossless.CompressedFrame):
+        if decoded is None or decoded.shape != (rows, cols):
+            raise DicomError(f"{ds['_path']}: compressed PixelData was not decoded")
+        px = decoded.astype(np.dtype(f"<u{dt.itemsize}")).view(dt)
+    elif raw is None or len(raw) < rows * cols * dt.itemsize:
         raise DicomError(f"{ds['_path']}: PixelData holds {0 if raw is None else len(raw)} bytes, {rows * cols * dt.itemsize} expected")
-    px = np.frombuffer(raw, dtype=dt, count=rows * cols).reshape(rows, cols)
+    else:
+        px = np.frombuffer(raw, dtype=dt, count=rows * cols).reshape(rows, cols)
     stored = int(ds.get("BitsStored", alloc))
     if stored < alloc:                              # bits above BitsStored are not part of the value (HighBit = BitsStored - 1 assumed)
         if int(ds.get("HighBit", stored - 1)) != stored - 1:
@@ -310,10 +338,11 @@ def _slice_pixels(ds: Dict[str, Any]) -> np.ndarray:
     return px
 
 
-def load_series(folder) -> Tuple[np.ndarray, Dict[str, Any], List[str]]:
+def load_series(folder, ctx=None) -> Tuple[np.ndarray, Dict[str, Any], List[str]]:
     """Folder -> (volume [x, y, z] in the file axis order of the NIfTI that `sitk.WriteImage` would write, geometry, files).
     geometry: LPS `origin` (3), `spacing` (3), `direction` (3 x 3, columns = row-direction / column-direction / slice normal),
-    and the RAS `affine` (4 x 4) of the NIfTI file."""
+    and the RAS `affine` (4 x 4) of the NIfTI file.  JPEG Lossless slices are decoded on the device in one batched call (ctx:
+    a device Context; default the process's `compute.inference.get_context()`, used only when the series holds such a slice)."""
     files = series_file_names(folder)
     sl = [read_file(p) for p in files]
     first = sl[0]
@@ -351,10 +380,11 @@ def load_series(folder) -> Tuple[np.ndarray, Dict[str, Any], List[str]]:
         dz = mean
     else:
         dz = float(first.get("SliceThickness") or 1.0)
+    decoded = _decode_compressed(sl, rows, cols, ctx)
     odt = _output_dtype(first)
     vol = np.empty((n, rows, cols), dtype=odt)
     for i, d in enumerate(sl):
-        px = _slice_pixels(d)
+        px = _slice_pixels(d, decoded.get(i))
         slope, inter = float(d.get("RescaleSlope", 1.0) or 1.0), float(d.get("RescaleIntercept", 0.0) or 0.0)
         if odt.kind == "f":
             vol[i] = px.astype(np.float64) * slope + inter
@@ -375,6 +405,26 @@ def load_series(folder) -> Tuple[np.ndarray, Dict[str, Any], List[str]]:
     affine = np.diag([-1.0, -1.0, 1.0, 1.0]) @ lps             # LPS -> RAS, as ITK's NiftiImageIO writes the s/q-form
     geom = {"origin": origin, "spacing": spacing, "direction": direction, "affine": affine}
     return data, geom, files
+
+
+def _decode_compressed(sl: List[Dict[str, Any]], rows: int, cols: int, ctx=None) -> Dict[int, np.ndarray]:
+    """{slice index: decoded uint16 samples} of the series' compressed slices: every frame is parsed on the host first (refusals
+    raise before the device is touched), then the whole batch is decoded in one device call."""
+    idx = [i for i, d in enumerate(sl) if isinstance(d.get("PixelData"), jpeg_lossless.CompressedFrame)]
+    if not idx:
+        return {}
+    frames = []
+    for i in idx:
+        d = sl[i]
+        _pixel_dtype(d)
+        alloc = int(d["BitsAllocated"])
+        frames.append(jpeg_lossless.parse_frame(d["PixelData"], rows=rows, cols=cols, bits_allocated=alloc,
+                                                bits_stored=int(d.get("BitsStored", alloc)), name=d["_path"]))
+    if ctx is None:
+        from .compute.inference import get_context
+        ctx = get_context()
+    px = jpeg_lossless.decode(ctx, frames)
+    return {i: px[k] for k, i in enumerate(idx)}
 
 
 def _parse_da(value) -> Optional[Tuple[int, int, int]]:

@@ -505,6 +505,48 @@ int boa_comm_stats(boa_comm* comm, long long* calls, long long* bytes);
  * fp16 sum of a slab ("allreduce" exchange mode) */
 int boa_add_f16_planes(boa_ctx* ctx, uint16_t* dev_acc, uint16_t* dev_n, const uint16_t* dev_stage, int C, const int PV[3], int lo, int hi);
 
+/* ------------------------------------------------------------------ JPEG Lossless decode (jpeg_ll.hip) --- */
+/* DICOM transfer syntaxes 1.2.840.10008.1.2.4.57 / .70 = ITU T.81 Process 14, one component.  The host parses the markers,
+ * removes the byte stuffing and the RSTn markers (boa_hip/jpeg_lossless.py) and passes, all as HOST arrays:
+ *   frames  int32 [n_frames][BOA_LJ_FRAME_WORDS]: fields BOA_LJ_F_* (byte offset of the frame's un-stuffed entropy-coded data
+ *           in dev_data: 4-aligned, its bytes padded to a multiple of 4 inside the buffer; restart rows 0 = no restart interval);
+ *           every frame of a batch has the same rows x cols;
+ *   segs    int32 [n_segs][4]: one per restart interval of each frame, in frame order: start byte, end byte (relative to the
+ *           frame), first row (= k x restart rows), index of its first subsequence;
+ *   subs    int32 [n_subs][2]: the split of every segment for the parallel decode: start byte (relative to the frame; the first
+ *           one = the segment's start, then strictly increasing below its end), segment index;
+ *   tables  uint32 [n_tables][BOA_LJ_TABLE_WORDS]: a DHT table expanded for lookup: words 0-255 = 512 uint16 entries
+ *           (len << 8 | SSSS) indexed by the next 9 stream bits, 0 where the code is longer; words 256-273 = maxcode[l]
+ *           (int32, -1 when no code has l bits), 274-291 = valoff[l] (huffval index of code c of length l = valoff[l] + c),
+ *           292-355 = huffval bytes (little-endian packed).
+ * Decodes the whole batch in one launch (serial = 0: one workgroup per frame, parallel entropy decode; serial = 1: one lane
+ * per frame, the sequential T.81 decoder) into dev_out uint16 [n_frames][rows][cols] (sample << Pt, modulo 2^16) and returns
+ * the per-frame status (BOA_LJ_OK / _TRUNCATED / _INVALID_CODE / _TRAILING_GARBAGE) in host_status.  Every offset is
+ * validated on the host first (BOA_EINVAL); malformed streams are reported per frame, never by a fault.  Synchronous. */
+#define BOA_LJ_FRAME_WORDS 16
+#define BOA_LJ_F_OFF_LO 0
+#define BOA_LJ_F_OFF_HI 1
+#define BOA_LJ_F_LEN 2
+#define BOA_LJ_F_ROWS 3
+#define BOA_LJ_F_COLS 4
+#define BOA_LJ_F_P 5
+#define BOA_LJ_F_PT 6
+#define BOA_LJ_F_PRED 7
+#define BOA_LJ_F_RESTART_ROWS 8
+#define BOA_LJ_F_TABLE 9
+#define BOA_LJ_F_SEG_FIRST 10
+#define BOA_LJ_F_N_SEG 11
+#define BOA_LJ_F_SUB_FIRST 12
+#define BOA_LJ_F_N_SUB 13
+#define BOA_LJ_TABLE_WORDS 384
+#define BOA_LJ_OK 0
+#define BOA_LJ_TRUNCATED 1
+#define BOA_LJ_INVALID_CODE 2
+#define BOA_LJ_TRAILING_GARBAGE 3
+int boa_ljpeg_decode(boa_ctx* ctx, const uint8_t* dev_data, size_t data_bytes, int n_frames, const int* frames, int n_segs,
+                     const int* segs, int n_subs, const int* subs, int n_tables, const uint32_t* tables, uint16_t* dev_out,
+                     int* host_status, int serial);
+
 #ifdef __cplusplus
 }
 #endif
