@@ -1,8 +1,9 @@
 """Mirror of the input side of BOA/compute/io.py for the hot path: `get_image_info` (:326-383) -- a folder with one DICOM CT
 series -> `<output_folder>/image.nii.gz` + the `ct_info` name / value list the Excel / JSON writers consume.  The DICOM-SEG /
 PACS / SMB half of that file (`store_dicoms`, `store_excel`) is the reference's control plane and stays there (DESIGN.md
-section 7).  Reader: boa_hip/dicom.py (uncompressed little-endian and JPEG Lossless CT; parity unpinned vs SimpleITK / GDCM).
-A series with JPEG Lossless slices is decoded on the process's device context (`compute.inference.get_context()`)."""
+section 7).  Reader: boa_hip/dicom.py (uncompressed little-endian, JPEG Lossless and JPEG 2000 lossless CT; parity unpinned vs
+SimpleITK / GDCM).  A series with JPEG Lossless or JPEG 2000 slices is decoded on the process's device context
+(`compute.inference.get_context()`)."""
 from __future__ import annotations
 
 import pathlib

@@ -6,9 +6,10 @@ documented behaviour of ITK's series reader / NIfTI writer; it is exercised agai
 only -- PARITY UNPINNED vs GDCM / SimpleITK.
 
 Scope (everything else raises, nothing is guessed):
-  * transfer syntaxes: implicit VR little endian (1.2.840.10008.1.2), explicit VR little endian (1.2.840.10008.1.2.1) and
-    JPEG Lossless Process 14 (1.2.840.10008.1.2.4.57, .70: encapsulated PixelData, one frame per file, decoded on the GPU for
-    the whole series in one call -- boa_hip/jpeg_lossless.py); other compressed, deflated and big-endian files raise
+  * transfer syntaxes: implicit VR little endian (1.2.840.10008.1.2), explicit VR little endian (1.2.840.10008.1.2.1),
+    JPEG Lossless Process 14 (1.2.840.10008.1.2.4.57, .70 -- boa_hip/jpeg_lossless.py) and JPEG 2000 holding a reversible
+    5/3 stream (1.2.840.10008.1.2.4.90, .91 -- boa_hip/jpeg2000.py): encapsulated PixelData, one frame per file, the frames
+    of a series decoded on the GPU in one call per codec; other compressed, deflated and big-endian files raise
     NotImplementedError;
   * single-frame, MONOCHROME2, SamplesPerPixel 1, BitsAllocated 16 (8 and 32 are read too);
   * one series per call: like `GetGDCMSeriesFileNames(dir)` without a series id, the FIRST series (smallest SeriesInstanceUID
@@ -30,7 +31,7 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
 
-from . import jpeg_lossless
+from . import jpeg2000, jpeg_lossless
 
 IMPLICIT_LE = "1.2.840.10008.1.2"
 EXPLICIT_LE = "1.2.840.10008.1.2.1"
@@ -185,12 +186,12 @@ def read_file(path, stop_before_pixels: bool = False) -> Dict[str, Any]:
             tsuid = _convert("UI", raw)
     if tsuid is None:
         raise DicomError(f"{path}: no TransferSyntaxUID in the file meta information")
-    if tsuid not in (IMPLICIT_LE, EXPLICIT_LE) + jpeg_lossless.SYNTAXES:
+    if tsuid not in (IMPLICIT_LE, EXPLICIT_LE) + jpeg_lossless.SYNTAXES + jpeg2000.SYNTAXES:
         raise NotImplementedError(f"{path}: transfer syntax {tsuid} (compressed, deflated or big endian) is not supported; "
-                                  "only implicit / explicit VR little endian (uncompressed) and JPEG Lossless (Process 14) "
-                                  "are read")
+                                  "only implicit / explicit VR little endian (uncompressed), JPEG Lossless (Process 14) "
+                                  "and JPEG 2000 (reversible) are read")
     explicit = tsuid != IMPLICIT_LE
-    jpeg = tsuid in jpeg_lossless.SYNTAXES
+    jpeg = tsuid in jpeg_lossless.SYNTAXES + jpeg2000.SYNTAXES
     out["TransferSyntaxUID"] = tsuid
     out["_explicit"] = explicit
     want = set(TAGS)
@@ -341,8 +342,9 @@ def _slice_pixels(ds: Dict[str, Any], decoded: Optional[np.ndarray] = None) -> n
 def load_series(folder, ctx=None) -> Tuple[np.ndarray, Dict[str, Any], List[str]]:
     """Folder -> (volume [x, y, z] in the file axis order of the NIfTI that `sitk.WriteImage` would write, geometry, files).
     geometry: LPS `origin` (3), `spacing` (3), `direction` (3 x 3, columns = row-direction / column-direction / slice normal),
-    and the RAS `affine` (4 x 4) of the NIfTI file.  JPEG Lossless slices are decoded on the device in one batched call (ctx:
-    a device Context; default the process's `compute.inference.get_context()`, used only when the series holds such a slice)."""
+    and the RAS `affine` (4 x 4) of the NIfTI file.  JPEG Lossless and JPEG 2000 slices are decoded on the device in one
+    batched call per codec (ctx: a device Context; default the process's `compute.inference.get_context()`, used only when
+    the series holds such a slice)."""
     files = series_file_names(folder)
     sl = [read_file(p) for p in files]
     first = sl[0]
@@ -409,22 +411,30 @@ def load_series(folder, ctx=None) -> Tuple[np.ndarray, Dict[str, Any], List[str]
 
 def _decode_compressed(sl: List[Dict[str, Any]], rows: int, cols: int, ctx=None) -> Dict[int, np.ndarray]:
     """{slice index: decoded uint16 samples} of the series' compressed slices: every frame is parsed on the host first (refusals
-    raise before the device is touched), then the whole batch is decoded in one device call."""
+    raise before the device is touched), then the frames of each codec (JPEG Lossless, JPEG 2000) are decoded in one device
+    call per codec."""
     idx = [i for i, d in enumerate(sl) if isinstance(d.get("PixelData"), jpeg_lossless.CompressedFrame)]
     if not idx:
         return {}
-    frames = []
+    groups: Dict[Any, Tuple[List[int], list]] = {}
     for i in idx:
         d = sl[i]
         _pixel_dtype(d)
         alloc = int(d["BitsAllocated"])
-        frames.append(jpeg_lossless.parse_frame(d["PixelData"], rows=rows, cols=cols, bits_allocated=alloc,
-                                                bits_stored=int(d.get("BitsStored", alloc)), name=d["_path"]))
+        codec = jpeg2000 if d["PixelData"].transfer_syntax in jpeg2000.SYNTAXES else jpeg_lossless
+        fr = codec.parse_frame(d["PixelData"], rows=rows, cols=cols, bits_allocated=alloc,
+                               bits_stored=int(d.get("BitsStored", alloc)), name=d["_path"])
+        g = groups.setdefault(codec, ([], []))
+        g[0].append(i)
+        g[1].append(fr)
     if ctx is None:
         from .compute.inference import get_context
         ctx = get_context()
-    px = jpeg_lossless.decode(ctx, frames)
-    return {i: px[k] for k, i in enumerate(idx)}
+    out: Dict[int, np.ndarray] = {}
+    for codec, (ids, frames) in groups.items():
+        px = codec.decode(ctx, frames)
+        out.update({i: px[k] for k, i in enumerate(ids)})
+    return out
 
 
 def _parse_da(value) -> Optional[Tuple[int, int, int]]:

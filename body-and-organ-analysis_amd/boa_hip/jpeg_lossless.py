@@ -38,7 +38,8 @@ def _err(msg: str):
 
 class CompressedFrame(bytes):
     """The bytes of one compressed frame (the concatenated fragments of an encapsulated PixelData), tagged with the file's
-    transfer syntax: what `dicom.read_file` returns as PixelData for a JPEG Lossless file."""
+    transfer syntax, which names the codec: what `dicom.read_file` returns as PixelData for a JPEG Lossless or JPEG 2000
+    file."""
     transfer_syntax: str = ""
 
 

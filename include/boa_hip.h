@@ -547,6 +547,48 @@ int boa_ljpeg_decode(boa_ctx* ctx, const uint8_t* dev_data, size_t data_bytes, i
                      const int* segs, int n_subs, const int* subs, int n_tables, const uint32_t* tables, uint16_t* dev_out,
                      int* host_status, int serial);
 
+/* ------------------------------------------------------------------ JPEG 2000 lossless decode (j2k.hip) --- */
+/* DICOM transfer syntaxes 1.2.840.10008.1.2.4.90 / .91 holding a reversible (5/3) stream, ITU T.800, one component, one tile,
+ * code-block style 0.  The host parses the codestream and runs tier-2 (boa_hip/jpeg2000.py) and passes, as HOST arrays:
+ *   frames  int32 [n_frames][BOA_J2K_FRAME_WORDS]: fields BOA_J2K_F_* (sample offset of the frame's output in dev_out: frames
+ *           packed in order, each rows x cols; decomposition levels; precision P 1..16; signed 0 / 1; its range of blocks:
+ *           blocks grouped by frame, in frame order); frames of a batch may differ in size, levels and precision;
+ *   blocks  int32 [n_blocks][BOA_J2K_BLOCK_WORDS]: fields BOA_J2K_B_* (frame; orientation 0 LL, 1 HL, 2 LH, 3 HH; x0, y0, w, h:
+ *           the block's place in the frame's coefficient plane, Mallat layout, w x h at most 4096; magnitude bit-planes
+ *           Mb - zero bit-planes; coding passes, the first a cleanup pass on the most significant plane; byte offset and length
+ *           of its data in dev_data, the contributions of all layers concatenated).
+ * Runs tier-1 of every block in one launch per chunk of frames (chunks keep the workspace below 1 GiB), then the inverse 5/3
+ * with the DC level shift, into dev_out uint16 (the sample clamped to its P-bit range, modulo 2^16), and returns the per-frame
+ * status (BOA_J2K_OK / _INVALID: a block with more passes than its bit-planes allow, or beyond 30 bit-planes) in host_status.
+ * Every field is validated on the host first (BOA_EINVAL); malformed streams are reported per frame, never by a fault.
+ * Synchronous. */
+#define BOA_J2K_FRAME_WORDS 12
+#define BOA_J2K_F_OUT_LO 0
+#define BOA_J2K_F_OUT_HI 1
+#define BOA_J2K_F_ROWS 2
+#define BOA_J2K_F_COLS 3
+#define BOA_J2K_F_LEVELS 4
+#define BOA_J2K_F_P 5
+#define BOA_J2K_F_SIGNED 6
+#define BOA_J2K_F_BLOCK_FIRST 7
+#define BOA_J2K_F_N_BLOCKS 8
+#define BOA_J2K_BLOCK_WORDS 12
+#define BOA_J2K_B_FRAME 0
+#define BOA_J2K_B_ORIENT 1
+#define BOA_J2K_B_X0 2
+#define BOA_J2K_B_Y0 3
+#define BOA_J2K_B_W 4
+#define BOA_J2K_B_H 5
+#define BOA_J2K_B_NUMBPS 6
+#define BOA_J2K_B_PASSES 7
+#define BOA_J2K_B_OFF_LO 8
+#define BOA_J2K_B_OFF_HI 9
+#define BOA_J2K_B_LEN 10
+#define BOA_J2K_OK 0
+#define BOA_J2K_INVALID 1
+int boa_j2k_decode(boa_ctx* ctx, const uint8_t* dev_data, size_t data_bytes, int n_frames, const int* frames, int n_blocks,
+                   const int* blocks, uint16_t* dev_out, int* host_status);
+
 #ifdef __cplusplus
 }
 #endif
