@@ -42,6 +42,8 @@ void pack_conv_weights(const float* w /*[Cout][Cin][k0][k1][k2]*/, int Cin, int 
 size_t convt_wpk_halves(int Cin, int Cout, const int s[3]);
 // split-precision mode (precision 2): hi / lo fp16 parts of w * scale, 8 real channels per MFMA K step
 float x3_weight_scale(const float* w, size_t n);
+// power of two folded into a transposed conv's output (and its inverse into the consumer's up-channel weights): puts the output near 1
+float x3_output_fold(const float* w, size_t n, int cin, const float* bias, int cout);
 size_t conv_wpk_halves_x3(int Cin_total, int Cout, const int k[3]);
 void pack_conv_weights_x3(const float* w, int Cin, int Cout, const int k[3], float scale, __half* dst);
 size_t convt_wpk_halves_x3(int Cin, int Cout, const int s[3]);
@@ -65,6 +67,14 @@ int launch_conv_x3(boa_ctx* ctx, const float* src0, const float* ss0, int C0, co
                    const ConvGeom& g, const ConvTile& t, const __half* wpk, float wscale, const float* bias, float slope, float* out,
                    float* partials);
 int conv_first_nblk(const int P[3], int cu_count);
+// which form the launchers pick (shared with the per-layer test seam boa_net_debug_layer, so that it reports what ran):
+// first conv on k_conv_first_mfma (else the fp32 VALU k_conv_first); k_conv_ws in its row-reuse form (X3: the tap-paired
+// consume_chunk_y_x3; else the per-tap consume_chunk); fp16 transposed conv 0 = k_convt_mfma, 1 = k_convt_mfma_rw, 2 = k_convt_deep;
+// k_convt_x3<MT>
+bool first_mfma_ok(int Cin, const int P[3], const int k[3], int Cout);
+bool conv_ws_row_reuse(int R, int k1, int s1, int w1, int b1, int b2);
+int convt_mfma_form(int Cin, const int s[3], bool norm_src);
+int convt_x3_mt(size_t vin);
 void conv_first_padded_dims(const int P[3], const int k[3], int out[3]);
 
 // InstanceNorm statistics -> (scale, shift) per (n, c):  scale = gamma * rsqrt(var + eps), shift = beta - mean * scale

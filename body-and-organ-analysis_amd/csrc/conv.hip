@@ -63,6 +63,18 @@ float x3_weight_scale(const float* w, size_t n) {
     return std::ldexp(1.f, std::max(-24, std::min(14 - e, 40)));   // m * scale in [2^13, 2^14)
 }
 
+float x3_output_fold(const float* w, size_t n, int cin, const float* bias, int cout) {
+    // output scale of a transposed conv fed with O(1) activations: sqrt(Cin) rms(w), or the largest bias if that is larger
+    double q = 0.0, bmax = 0.0;
+    for (size_t i = 0; i < n; ++i) q += (double)w[i] * w[i];
+    for (int i = 0; i < cout; ++i) bmax = std::max(bmax, (double)std::fabs(bias[i]));
+    const double mag = std::max(std::sqrt(q / std::max<size_t>(n, 1) * cin), bmax);
+    if (!(mag > 0.0) || !std::isfinite(mag)) return 1.f;
+    const int e = (int)std::lround(-std::log2(mag));
+    // within [-2, 2] the fold changes nothing worth a different rounding of the consumer's weights: keep the bits of the unfolded net
+    return (e >= -2 && e <= 2) ? 1.f : std::ldexp(1.f, std::max(-30, std::min(e, 30)));
+}
+
 static inline void x3_split(float v, __half* hi, __half* lo) {
     const __half h = __float2half_rn(v);
     *hi = h;
@@ -1068,7 +1080,7 @@ __global__ __launch_bounds__(256) void k_conv_first_mfma(FirstMfmaArgs p) {
     flush(slot);
 }
 
-static bool first_mfma_ok(int Cin, const int P[3], const int k[3], int Cout) {
+bool first_mfma_ok(int Cin, const int P[3], const int k[3], int Cout) {
     static const bool off = getenv("BOA_FIRST_MFMA") && atoi(getenv("BOA_FIRST_MFMA")) == 0;
     return !off && Cin == 1 && Cout == 32 && k[0] == 3 && k[1] == 3 && k[2] == 3 && P[0] % MF0 == 0 && P[1] % MF1 == 0 && P[2] % MF2 == 0;
 }
@@ -1769,6 +1781,15 @@ __global__ __launch_bounds__(256) void k_convt_deep(ConvTArgs p) {
     }
 }
 
+int convt_mfma_form(int Cin, const int s[3], bool norm_src) {
+    static const bool no_rw = getenv("BOA_CONVT_NO_RW") != nullptr;
+    static const bool no_deep = getenv("BOA_CONVT_NO_DEEP") != nullptr;
+    static const bool deep128 = getenv("BOA_CONVT_DEEP128") != nullptr;   // experiment: the 32^3 -> 64^3 layer on k_convt_deep too
+    if (!no_deep && s[0] == 2 && s[1] == 2 && s[2] == 2 && norm_src && (Cin == 256 || Cin == 320 || (deep128 && Cin == 128))) return 2;
+    if (!no_rw && s[2] == 2 && norm_src && (Cin == 64 || Cin == 128)) return 1;
+    return 0;
+}
+
 int launch_convt_mfma(boa_ctx* ctx, const ActSrc& src, int N, const int din[3], const int s[3], int Cout,
                       const __half* wpk, const float* bias, float slope, __half* out) {
     BOA_REQUIRE(src.C % 16 == 0 && Cout % 32 == 0, "convT: channels %d -> %d unsupported", src.C, Cout);
@@ -1792,11 +1813,8 @@ int launch_convt_mfma(boa_ctx* ctx, const ActSrc& src, int N, const int din[3], 
     (void)once;
     const double taps = (double)s[0] * s[1] * s[2];
     KernelTimer tm(ctx, BOA_K_CONVT, 2.0 * total * taps * src.C * Cout, 2.0 * total * (src.C + taps * Cout));
-    static const bool no_rw = getenv("BOA_CONVT_NO_RW") != nullptr;
-    const bool rw = !no_rw && s[2] == 2 && src.ss16 != nullptr && (src.C == 64 || src.C == 128);
-    static const bool no_deep = getenv("BOA_CONVT_NO_DEEP") != nullptr;
-    static const bool deep128 = getenv("BOA_CONVT_DEEP128") != nullptr;   // experiment: the 32^3 -> 64^3 layer on k_convt_deep too
-    const bool deep = !no_deep && s[0] == 2 && s[1] == 2 && s[2] == 2 && src.ss16 != nullptr && (src.C == 256 || src.C == 320 || (deep128 && src.C == 128));
+    const int form = convt_mfma_form(src.C, s, src.ss16 != nullptr);
+    const bool rw = form == 1, deep = form == 2;
     if (deep) {
         const int ncc = src.C / 16;
         const int gxd = (int)((total + 255) / 256);    // 4 waves x 2 M-tiles x 32 voxels per block

@@ -956,12 +956,16 @@ static void launch_ws_y(boa_ctx* ctx, const ConvArgs& a, const ConvTile& t, int 
                        getenv("BOA_WS_DBG") ? atoi(getenv("BOA_WS_DBG")) : 0, desc, desc_row);
 }
 
+bool conv_ws_row_reuse(int R, int k1, int s1, int w1, int b1, int b2) {
+    static const bool off = getenv("BOA_WS_NO_YREUSE") != nullptr;
+    return R > 1 && k1 == 3 && s1 == 1 && w1 == 1 && b2 == 1 && b1 % R == 0 && !off;
+}
+
 template <int R, int K0, int K1, int K2, bool X3>
 static void launch_ws_t(boa_ctx* ctx, const ConvArgs& a, const ConvTile& t, int total, int grid, int resident, const int* desc, int desc_row) {
     // row reuse: the R M-tiles of a wave are consecutive output rows (m = cw * R + r, my = m & (b1 - 1) when b2 == 1),
     // one voxel high, stride 1 along y
-    static const bool off = getenv("BOA_WS_NO_YREUSE") != nullptr;
-    const bool yr = R > 1 && K1 == 3 && a.s1 == 1 && a.w1 == 1 && a.b2 == 1 && a.b1 % R == 0 && !off;
+    const bool yr = conv_ws_row_reuse(R, K1, a.s1, a.w1, a.b1, a.b2);
     if (R > 1 && yr)
         launch_ws_y<R, K0, K1, K2, (R > 1), X3>(ctx, a, t, total, grid, resident, desc, desc_row);
     else

@@ -1,5 +1,6 @@
 // PlainConvUNet on device + the sliding-window tile loop
 // (NN/inference/predict_from_raw_data.py:543,560-631; architecture per NN/utilities/plans_handling/plans_handler.py:59-92).
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -43,6 +44,7 @@ struct UpLayer {
     __half* out = nullptr;
     float* out32 = nullptr;  // fp32 / split-precision mode
     float wscale = 1.f;      // split-precision mode
+    float fold = 1.f;        // split-precision mode: power of two folded into the stored output (out32 = fold * convT output)
 };
 
 }  // namespace
@@ -94,7 +96,8 @@ struct boa_net {
         size_t n;
         unsigned long long sample_hash;  // FNV-1a over ~4096 evenly spaced floats: guards against a recycled host address
         unsigned char* arena;
-        std::vector<float> scales;       // split-precision mode: weight scale of every conv / transposed conv, blob order
+        std::vector<float> scales;       // split-precision mode: weight scale of every conv / transposed conv (+ the output fold of a
+                                         // transposed conv), blob order
     };
     std::vector<WeightSet> wsets;
 };
@@ -287,7 +290,7 @@ static void point_layers_at(boa_net* net, unsigned char* arena, const std::vecto
         void* p = arena + off;
         switch (kind) {
             case 11: L->wpk = (__half*)p; L->wscale = scales[si++]; break;
-            case 12: U->wpk = (__half*)p; U->wscale = scales[si++]; break;
+            case 12: U->wpk = (__half*)p; U->wscale = scales[si++]; U->fold = scales[si++]; break;
             case 0: L->wfirst = (float*)p; break;
             case 1: L->wpk = (__half*)p; break;
             case 2: L->bias = (float*)p; break;
@@ -331,6 +334,13 @@ extern "C" int boa_net_load_weights(boa_net* net, const float* w, size_t n_float
     std::vector<float> scales;
     const float* p = w;
     size_t off = 0;
+    // Split-precision mode: activations are split unscaled (x3_split4), so the lo part of a value below 2^-3 is an fp16 subnormal with
+    // an absolute floor of 2^-25.  Normalised activations are O(1), but a transposed conv's output is the one raw source of the stack:
+    // its magnitude is whatever its weights make it.  A power of two g, chosen here from the weights so that the output lands near 1,
+    // is folded into the transposed conv (stored output = g * output: winv and bias times g) and 1 / g into the up-channel weights of
+    // the decoder conv that consumes it -- exact in binary, no instruction on the hot path.  (g = 1 for the usual Kaiming weights.)
+    float up_fold = 1.f;
+    const ConvLayer* fold_target = nullptr;
     for_each_weight_piece(net, [&](int kind, ConvLayer* L, UpLayer* U, size_t bytes) {
         unsigned char* dst = stage.data() + off;
         switch (kind) {
@@ -352,20 +362,38 @@ extern "C" int boa_net_load_weights(boa_net* net, const float* w, size_t n_float
                 p += (size_t)U->Cin * U->Cout * U->s[0] * U->s[1] * U->s[2];
                 break;
             case 11: {  // split-precision conv: hi / lo fp16 parts of w * 2^e
-                const float sc = x3_weight_scale(p, L->w_elems);
+                const float* wl = p;
+                std::vector<float> folded;
+                if (L == fold_target && up_fold != 1.f) {   // [Cout][Cin0 + Cin1][taps]: the first Cin0 inputs are the transposed conv's
+                    const int cin = L->Cin0 + L->Cin1, taps = L->g.k[0] * L->g.k[1] * L->g.k[2];
+                    folded.assign(p, p + L->w_elems);
+                    for (int co = 0; co < L->g.Cout; ++co)
+                        for (size_t i = 0; i < (size_t)L->Cin0 * taps; ++i) folded[(size_t)co * cin * taps + i] /= up_fold;
+                    wl = folded.data();
+                }
+                const float sc = x3_weight_scale(wl, L->w_elems);
                 scales.push_back(sc);
-                pack_conv_weights_x3(p, L->Cin0 + L->Cin1, L->g.Cout, L->g.k, sc, (__half*)dst);
+                pack_conv_weights_x3(wl, L->Cin0 + L->Cin1, L->g.Cout, L->g.k, sc, (__half*)dst);
                 p += L->w_elems;
                 break;
             }
             case 12: {
                 const size_t ne = (size_t)U->Cin * U->Cout * U->s[0] * U->s[1] * U->s[2];
                 const float sc = x3_weight_scale(p, ne);
-                scales.push_back(sc);
+                up_fold = x3_output_fold(p, ne, U->Cin, p + ne, U->Cout);   // (the bias follows the weights in the blob)
+                fold_target = &net->dec[U - net->up.data()][0];
+                scales.push_back(sc / up_fold);   // winv = 1 / wscale = fold / sc
+                scales.push_back(up_fold);
                 pack_convt_weights_x3(p, U->Cin, U->Cout, U->s, sc, (__half*)dst);
                 p += ne;
                 break;
             }
+            case 6:   // transposed-conv bias (times the output fold in the split-precision mode)
+                memcpy(dst, p, bytes);
+                if (net->precision == 2 && up_fold != 1.f)
+                    for (int i = 0; i < U->Cout; ++i) ((float*)dst)[i] *= up_fold;
+                p += bytes / sizeof(float);
+                break;
             case 9: {  // fp32 mode conv: [cout][cin][taps] -> [tap][cin][cout]
                 const int cin = L->Cin0 + L->Cin1, cout = L->g.Cout, taps = L->g.k[0] * L->g.k[1] * L->g.k[2];
                 float* wf = (float*)dst;
@@ -642,6 +670,9 @@ static int net_forward_stack_x3(boa_net* net, const float* volume, const int V[3
     return BOA_OK;
 }
 
+// split-precision mode: the MFMA head (k_head_x3, the gather head's arithmetic) for F0 = 32 and up to 32 classes, else the fp32 head
+static bool head_x3(const boa_net* net) { return net->precision == 2 && net->d.features[0] == 32 && net->d.num_classes <= 32; }
+
 // head of tile i of the current batch (either precision)
 static int net_head(boa_net* net, int i, const int P[3], int plane_skip, float* logits_out, const uint16_t* gauss, uint16_t* acc,
                     uint16_t* nacc, const int PV[3], const int start[3]) {
@@ -655,7 +686,7 @@ static int net_head(boa_net* net, int i, const int P[3], int plane_skip, float* 
                                nacc, PV, start);
     if (net->precision == 2) {  // split-precision mode: fp32 octet planes; skipped axis-0 planes are an offset inside every plane
         const float* a32 = last.out32 + (size_t)i * pv * d.features[0] + (size_t)plane_skip * d.patch[1] * d.patch[2] * 8;
-        if (d.features[0] == 32 && d.num_classes <= 32)   // the gather head's arithmetic (label path == logits API, bit for bit)
+        if (head_x3(net))   // the gather head's arithmetic (label path == logits API, bit for bit)
             return launch_head_x3(net->ctx, a32, ss, d.features[0], P, d.num_classes, net->head_w, net->head_b, d.lrelu_slope, logits_out, gauss, acc,
                                   nacc, PV, start, pv);
         return launch_head_f32(net->ctx, a32, ss, d.features[0], P, d.num_classes, net->head_w, net->head_b, d.lrelu_slope, logits_out, gauss, acc, nacc,
@@ -1417,6 +1448,24 @@ extern "C" int boa_conv_block_test(boa_ctx* ctx, const float* dev_in, int N, int
     return rc;
 }
 
+// octet planes -> fp32 NCDHW for the debug seams, with a transposed conv's output fold taken out again (x / fold is exact): through
+// the conversion's (scale, shift) path with scale 1 / fold, shift 0 and slope 1 (LeakyReLU with slope 1 is the identity)
+static int octet_to_nchw_unfold(boa_net* net, const float* a32, float fold, int C, size_t vox, float* out) {
+    if (fold == 1.f) return launch_octet_to_nchw_f32(net->ctx, a32, nullptr, net->d.lrelu_slope, C, vox, out);
+    std::vector<float> tab((size_t)C * 2);
+    for (int i = 0; i < C; ++i) {
+        tab[2 * i] = 1.f / fold;
+        tab[2 * i + 1] = 0.f;
+    }
+    float* dss = nullptr;
+    BOA_TRY(boa_malloc(net->ctx, tab.size() * sizeof(float), (void**)&dss));
+    int rc = boa_h2d(net->ctx, dss, tab.data(), tab.size() * sizeof(float));
+    if (rc == BOA_OK) rc = launch_octet_to_nchw_f32(net->ctx, a32, dss, 1.f, C, vox, out);
+    if (rc == BOA_OK) rc = boa_sync(net->ctx);
+    boa_free(net->ctx, dss);
+    return rc;
+}
+
 extern "C" int boa_net_debug_activation(boa_net* net, int kind, int stage, int conv, int tile, float* dev_out, int* channels_out,
                                         int dims_out[3]) {
     BOA_REQUIRE(net && channels_out && dims_out, "boa_net_debug_activation: NULL argument");
@@ -1425,6 +1474,7 @@ extern "C" int boa_net_debug_activation(boa_net* net, int kind, int stage, int c
     const float* ss = nullptr;
     const __half* a16 = nullptr;
     const float* a32 = nullptr;
+    float fold = 1.f;
     int Cc = 0, dm[3] = {0, 0, 0};
     if (kind == 1) {
         BOA_REQUIRE(stage >= 0 && stage < (int)net->up.size(), "boa_net_debug_activation: no transposed conv %d", stage);
@@ -1433,6 +1483,7 @@ extern "C" int boa_net_debug_activation(boa_net* net, int kind, int stage, int c
         for (int a = 0; a < 3; ++a) dm[a] = U.din[a] * U.s[a];
         a16 = U.out;
         a32 = U.out32;
+        fold = U.fold;
     } else {
         auto& stages = kind == 0 ? net->enc : net->dec;
         BOA_REQUIRE((kind == 0 || kind == 2) && stage >= 0 && stage < (int)stages.size() && conv >= 0 && conv < (int)stages[stage].size(),
@@ -1451,8 +1502,94 @@ extern "C" int boa_net_debug_activation(boa_net* net, int kind, int stage, int c
     if (net->precision == 1)
         return launch_ndhwc32_to_nchw_f32(net->ctx, a32 + (size_t)tile * vox * Cc, ss, net->d.lrelu_slope, Cc, vox, dev_out);
     if (net->precision == 2)
-        return launch_octet_to_nchw_f32(net->ctx, a32 + (size_t)tile * vox * Cc, ss, net->d.lrelu_slope, Cc, vox, dev_out);
+        return ss ? launch_octet_to_nchw_f32(net->ctx, a32 + (size_t)tile * vox * Cc, ss, net->d.lrelu_slope, Cc, vox, dev_out)
+                  : octet_to_nchw_unfold(net, a32 + (size_t)tile * vox * Cc, fold, Cc, vox, dev_out);
     return launch_ndhwc_to_nchw_f32(net->ctx, a16 + (size_t)tile * vox * Cc, ss, net->d.lrelu_slope, 1, Cc, vox, dev_out);
+}
+
+extern "C" int boa_net_debug_layer(boa_net* net, int kind, int stage, int conv, int tile, float* dev_raw, float* host_ss,
+                                   uint16_t* host_ss16, int* channels_out, int dims_out[3], int* host_info) {
+    BOA_REQUIRE(net && channels_out && dims_out, "boa_net_debug_layer: NULL argument");
+    BOA_REQUIRE(tile >= 0 && tile < net->maxN, "boa_net_debug_layer: tile %d outside the batch", tile);
+    BOA_TRY(net_bind_arena(net));
+    const boa_net_desc& d = net->d;
+    const __half* a16 = nullptr;
+    const float* a32 = nullptr;
+    const ConvLayer* L = nullptr;
+    float fold = 1.f;
+    int Cc = 0, dm[3] = {0, 0, 0}, info[3] = {0, 0, 0};
+    if (kind == 3) {   // the head: which kernel net_head launches (its output is the logits of boa_net_forward, nothing is stored)
+        BOA_REQUIRE(!dev_raw && !host_ss && !host_ss16, "boa_net_debug_layer: the head stores no output (kind 3 reports the kernel only)");
+        *channels_out = d.num_classes;
+        for (int a = 0; a < 3; ++a) dims_out[a] = d.patch[a];
+        if (host_info) {
+            host_info[0] = net->precision == 0 ? BOA_LK_HEAD_MFMA : head_x3(net) ? BOA_LK_HEAD_X3 : BOA_LK_HEAD_F32;
+            host_info[1] = host_info[2] = 0;
+        }
+        return BOA_OK;
+    }
+    if (kind == 1) {
+        BOA_REQUIRE(stage >= 0 && stage < (int)net->up.size(), "boa_net_debug_layer: no transposed conv %d", stage);
+        const UpLayer& U = net->up[stage];
+        Cc = U.Cout;
+        for (int a = 0; a < 3; ++a) dm[a] = U.din[a] * U.s[a];
+        a16 = U.out;
+        a32 = U.out32;
+        if (net->precision == 1) {
+            info[0] = BOA_LK_CONVT_F32;
+        } else if (net->precision == 2) {
+            info[0] = BOA_LK_CONVT_X3;
+            info[1] = convt_x3_mt((size_t)U.din[0] * U.din[1] * U.din[2]);
+            info[2] = (int)std::lround(std::log2((double)U.fold));
+            fold = U.fold;
+        } else {
+            const int form = convt_mfma_form(U.Cin, U.s, true);   // (the source of a transposed conv is always a normalised conv output)
+            info[0] = form == 2 ? BOA_LK_CONVT_DEEP : form == 1 ? BOA_LK_CONVT_RW : BOA_LK_CONVT_MFMA;
+        }
+    } else {
+        auto& stages = kind == 0 ? net->enc : net->dec;
+        BOA_REQUIRE((kind == 0 || kind == 2) && stage >= 0 && stage < (int)stages.size() && conv >= 0 && conv < (int)stages[stage].size(),
+                    "boa_net_debug_layer: no layer (kind %d, stage %d, conv %d)", kind, stage, conv);
+        L = &stages[stage][conv];
+        Cc = L->g.Cout;
+        dm[0] = L->g.Do; dm[1] = L->g.Ho; dm[2] = L->g.Wo;
+        a16 = L->out;
+        a32 = L->out32;
+        if (net->precision == 1) {
+            info[0] = BOA_LK_CONV_F32;
+        } else if (L->first) {
+            info[0] = first_mfma_ok(d.in_channels, d.patch, L->g.k, L->g.Cout) ? BOA_LK_FIRST_MFMA : BOA_LK_FIRST_VALU;
+        } else {
+            const ConvTile& t = L->t;
+            info[0] = t.variant == 2 ? BOA_LK_CONV_NS : t.variant == 1 ? BOA_LK_CONV_WS : BOA_LK_CONV_MFMA;
+            info[1] = t.R;
+            info[2] = t.variant == 1 && conv_ws_row_reuse(t.R, L->g.k[1], L->g.s[1], t.w[1], t.b[1], t.b[2]) ? 1 : 0;
+        }
+    }
+    *channels_out = Cc;
+    for (int a = 0; a < 3; ++a) dims_out[a] = dm[a];
+    if (host_info)
+        for (int i = 0; i < 3; ++i) host_info[i] = info[i];
+    if (host_ss) {
+        if (L) {
+            BOA_TRY(boa_sync(net->ctx));
+            BOA_HIP_TRY(hipMemcpy(host_ss, L->ss + (size_t)tile * Cc * 2, (size_t)Cc * 2 * sizeof(float), hipMemcpyDeviceToHost));
+        } else {
+            for (int i = 0; i < 2 * Cc; ++i) host_ss[i] = i & 1 ? 0.f : 1.f;   // (raw source: identity)
+        }
+    }
+    if (host_ss16) {
+        BOA_REQUIRE(L && L->ss16, "boa_net_debug_layer: fp16 (scale, shift) exist for the convs of the fp16 mode only");
+        BOA_TRY(boa_sync(net->ctx));
+        BOA_HIP_TRY(hipMemcpy(host_ss16, L->ss16 + (size_t)tile * Cc, (size_t)Cc * sizeof(unsigned), hipMemcpyDeviceToHost));
+    }
+    if (!dev_raw) return BOA_OK;
+    const size_t vox = (size_t)dm[0] * dm[1] * dm[2];
+    if (net->precision == 1)
+        return launch_ndhwc32_to_nchw_f32(net->ctx, a32 + (size_t)tile * vox * Cc, nullptr, d.lrelu_slope, Cc, vox, dev_raw);
+    if (net->precision == 2)
+        return octet_to_nchw_unfold(net, a32 + (size_t)tile * vox * Cc, fold, Cc, vox, dev_raw);
+    return launch_ndhwc_to_nchw_f32(net->ctx, a16 + (size_t)tile * vox * Cc, nullptr, d.lrelu_slope, 1, Cc, vox, dev_raw);
 }
 
 extern "C" int boa_head_tile(boa_ctx* ctx, const uint16_t* dev_act, const float* dev_ss, int F0, const int P[3], int C,

@@ -238,6 +238,9 @@ __global__ void k_octet_to_nchw_f32(const float* __restrict__ in, const float* _
 
 }  // namespace
 
+// two M-tiles per block halve the weight re-reads; small inputs keep one so that more blocks exist
+int convt_x3_mt(size_t vin) { return vin >= 4096 ? 2 : 1; }
+
 int launch_convt_x3(boa_ctx* ctx, const float* src, const float* ss, int Cin, int N, const int din[3], const int s[3], int Cout,
                     const __half* wpk, float wscale, const float* bias, float slope, float* out) {
     BOA_REQUIRE(Cin % 8 == 0 && Cout % 32 == 0, "convT_x3: channel counts %d -> %d unsupported", Cin, Cout);
@@ -247,8 +250,7 @@ int launch_convt_x3(boa_ctx* ctx, const float* src, const float* ss, int Cin, in
     const size_t vin = (size_t)din[0] * din[1] * din[2];
     BOA_REQUIRE(vin < (1u << 31), "convT_x3: input too large");
     const int taps = s[0] * s[1] * s[2];
-    // two M-tiles per block halve the weight re-reads; small inputs keep one so that more blocks exist
-    const int MT = vin >= 4096 ? 2 : 1;
+    const int MT = convt_x3_mt(vin);
     const size_t lds = (size_t)Cin * MT * 128;
     BOA_REQUIRE(lds <= 160 * 1024, "convT_x3: Cin=%d does not fit LDS", Cin);
     KernelTimer tm(ctx, BOA_K_CONVT, 2.0 * N * (double)vin * taps * Cin * Cout, 4.0 * N * (double)vin * (Cin + (double)taps * Cout));

@@ -267,6 +267,34 @@ int boa_conv_block_test(boa_ctx* ctx, const float* dev_in, int N, int Cin, const
  * dev_out == NULL only returns channels / dims. */
 int boa_net_debug_activation(boa_net* net, int kind, int stage, int conv, int tile, float* dev_out, int* channels_out,
                              int dims_out[3]);
+/* Per-layer test seam (tests/test_gpu_layer_parity.py): what one layer stored for `tile` of the LAST batch through the conv stack,
+ * with the same (kind, stage, conv) addressing as boa_net_debug_activation.
+ *   dev_raw   (may be NULL) dev fp32 [C][D][H][W]: the layer's RAW stored output (pre-norm conv output + bias; fp16 storage widened
+ *             exactly, fp32 / octet storage as it is)
+ *   host_ss   (may be NULL) host fp32 [C][2]: the (scale, shift) the consumers apply, lrelu(raw * scale + shift); (1, 0) for a
+ *             transposed conv, whose output is consumed raw
+ *   host_ss16 (may be NULL; fp16-mode convs only) host uint16 [C/2][4]: the packed words the fp16 consumers read,
+ *             {scale(c), scale(c + 1), shift(c), shift(c + 1)} as fp16 bits per channel pair
+ *   host_info (may be NULL) int[3]: {BOA_LK_* kernel that ran, R of k_conv_ws / k_conv_ns / k_conv_mfma or MT of k_convt_x3,
+ *             convs: 1 if k_conv_ws ran its row-reuse form (split precision: the tap-paired loop); transposed convs: log2 of the
+ *             power of two the split-precision mode folds into the stored output (dev_raw has it taken out again)}
+ * kind 3 = the head (stage, conv ignored): reports channels / dims / host_info[0] only; dev_raw, host_ss, host_ss16 must be NULL. */
+#define BOA_LK_FIRST_VALU 1   /* k_conv_first (fp32 VALU)       */
+#define BOA_LK_FIRST_MFMA 2   /* k_conv_first_mfma              */
+#define BOA_LK_CONV_WS 3      /* k_conv_ws                      */
+#define BOA_LK_CONV_NS 4      /* k_conv_ns                      */
+#define BOA_LK_CONV_MFMA 5    /* k_conv_mfma fallback           */
+#define BOA_LK_CONV_F32 6     /* fp32 mode conv (net_f32.hip)   */
+#define BOA_LK_CONVT_X3 7     /* k_convt_x3                     */
+#define BOA_LK_CONVT_MFMA 8   /* k_convt_mfma                   */
+#define BOA_LK_CONVT_RW 9     /* k_convt_mfma_rw                */
+#define BOA_LK_CONVT_DEEP 10  /* k_convt_deep                   */
+#define BOA_LK_CONVT_F32 11   /* fp32 mode transposed conv      */
+#define BOA_LK_HEAD_X3 12     /* k_head_x3                      */
+#define BOA_LK_HEAD_F32 13    /* k_head_f32 (fp32 / octet input) */
+#define BOA_LK_HEAD_MFMA 14   /* launch_head: k_head_mfma or its VALU fallback (boa_debug_counter tells which) */
+int boa_net_debug_layer(boa_net* net, int kind, int stage, int conv, int tile, float* dev_raw, float* host_ss, uint16_t* host_ss16,
+                        int* channels_out, int dims_out[3], int* host_info);
 
 /* Unit-test seam: the fused 1x1x1 head + Gaussian-weighted fp16 accumulation of ONE tile, launched exactly as the tile
  * loop of boa_net_predict_sliding_window launches it (same kernel selection: the MFMA head when F0 == 32, C <= 31,
