@@ -125,9 +125,8 @@ extern "C" int boa_tissue_aggregate(boa_ctx* c, const int16_t* dev_ct, const int
                       (((uintptr_t)dev_parts) % 8 == 0) && (((uintptr_t)dev_tissues_out) % 8 == 0);
     const int nvec = vec8 ? sv / 8 : sv;
     // workgroups per slice: 16 (each thread reduces >= 64 voxels before the wave / block reduction and its 14 global atomics; 64
-    // workgroups per slice measured 0.43 ms per 512^3 volume, 8 ... 32: 0.35 ms); $BOA_TISSUE_GX: experiment hook
-    static const int gx_cap = getenv("BOA_TISSUE_GX") ? atoi(getenv("BOA_TISSUE_GX")) : 16;
-    int gx = std::min(ceil_div(nvec, 256), gx_cap);
+    // workgroups per slice measured 0.43 ms per 512^3 volume, 8 ... 32: 0.35 ms)
+    const int gx = std::min(ceil_div(nvec, 256), 16);
     const double vox = (double)Z * sv;
     KernelTimer t(c, BOA_K_AGG, 0, vox * (3.0 + (dev_ct_rules ? 2 : 0) + (dev_parts ? 1 : 0) + (dev_tissues_out ? 1 : 0)));
     if (vec8)
@@ -380,20 +379,6 @@ __global__ __launch_bounds__(HT) void k_label_hist(const short* __restrict__ ct,
             const unsigned c = 16u * (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(live));
             if (k0 != 0u && (tid & 63) == 0 && c) count(k0, c);
         } else if (live) {
-#ifdef BOA_HIST_SERIAL   // (A/B: the round-5 form, one dependent probe chain per run of equal keys)
-            unsigned rk = key[0], run = 1;
-#pragma unroll
-            for (int i = 1; i < 16; ++i) {
-                if (key[i] == rk) {
-                    ++run;
-                } else {
-                    if (rk) count(rk, run);
-                    rk = key[i];
-                    run = 1;
-                }
-            }
-            if (rk) count(rk, run);
-#else
             // Round 6: the 16 voxels of a lane are looked up TOGETHER.  In the steady state a key already sits in its home slot (a slot
             // keeps its key until the next flush, and flushes are behind the workgroup barrier): 16 independent ds_read_b32 of the home
             // slots, then one return-less ds_add_u32 per hit -- throughput instead of 16 dependent LDS round trips with a probe loop
@@ -422,7 +407,6 @@ __global__ __launch_bounds__(HT) void k_label_hist(const short* __restrict__ ct,
                         count(key[i], cc[i]);
                 }
             }
-#endif
         }
         __syncthreads();
         if (nkeys > HIST_FLUSH) flush();   // (uniform: nkeys is read after the barrier by everyone)
@@ -468,44 +452,22 @@ extern "C" int boa_label_hu_histogram(boa_ctx* c, const int16_t* dev_ct, const u
     if (head > n) head = n;
     const bool together = (((uintptr_t)dev_ct + 2 * head) & 15) == 0 && (!dev_mask || (((uintptr_t)dev_mask + head) & 15) == 0);
     // contiguous voxel ranges per workgroup (few labels each): ~4 workgroups per CU, at least one 4 096-voxel iteration
-    // table size / workgroups per CU, kernel time in us (tools/hist_sweep.sh, tools/hist_bench.sh; 512^3):   structured phantom | bench labels (noise-like)
+    // table size / workgroups per CU, kernel time in us (round 5, 512^3):   structured phantom | bench labels (noise-like)
     //   2^14, 4:  845 | 947      2^13, 8:  679 | 1 124      2^12, 8:  571 | 1 905      2^12, 16:  650 | 2 056
     // compact organs want occupancy, salt-and-pepper labels a table that merges more duplicates before it spills: 2^13 is the default
-    // round 6 (tools/r6_hist_sweep.sh, profiles/r06_hist_sweep.txt; kernel us on the structured phantom | on salt-and-pepper labels, 512^3):
+    // round 6 (profiles/r06_hist_sweep.txt; kernel us on the structured phantom | on salt-and-pepper labels, 512^3):
     //   2^13 x 256 threads x 8 per CU (round 5)  638 | 2 937      2^13 x 1 024 x 2   486 | 2 600      2^12 x 1 024 x 2   547 | 2 650
-    //   2^14 x 1 024 x 1  420 | 2 106  <- default: ONE 1 024-thread workgroup per CU with the largest table = the fewest flush atomics
-    // ($BOA_HIST_THREADS=256 restores the small workgroups)
-    static const int hist_log2 = getenv("BOA_HIST_LOG2") ? atoi(getenv("BOA_HIST_LOG2")) : 14;
-    static const int hist_threads = getenv("BOA_HIST_THREADS") ? atoi(getenv("BOA_HIST_THREADS")) : 1024;
-    const int HT = hist_threads == 256 ? 256 : (hist_threads == 512 ? 512 : 1024);
-    static const int hist_wg = getenv("BOA_HIST_WG") ? atoi(getenv("BOA_HIST_WG")) : 0;   // workgroups per CU (0: what fits next to each other)
-    const int wg = hist_wg > 0 ? hist_wg : (HT == 256 ? (hist_log2 == 14 ? 4 : 8) : std::max(1, std::min((160 * 1024) / (8 << hist_log2), 2048 / HT)));
+    //   2^14 x 1 024 x 1  420 | 2 106  <- kept: ONE 1 024-thread workgroup per CU with the largest table = the fewest flush atomics
+    constexpr int LOG2 = 14, HT = 1024;   // (the 128 KiB table leaves room for one workgroup per CU)
     const size_t iters = ((n - head) / 16 + HT - 1) / HT;
-    const size_t gpb = std::max<size_t>(1, (iters + (size_t)c->cu_count * wg - 1) / ((size_t)c->cu_count * wg));
+    const size_t gpb = std::max<size_t>(1, (iters + (size_t)c->cu_count - 1) / (size_t)c->cu_count);
     const int grid = (int)std::max<size_t>(1, (iters + gpb - 1) / gpb);
     KernelTimer t(c, BOA_K_AGG, 0, (double)n * (3.0 + (dev_mask ? 1 : 0)));
     if (together) {
-#define BOA_HIST_LAUNCH(L, T)                                                                                                         \
-    do {                                                                                                                              \
-        static bool once = (hipFuncSetAttribute((const void*)k_label_hist<L, T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024), true); \
-        (void)once;                                                                                                                   \
-        hipLaunchKernelGGL((k_label_hist<L, T>), dim3(grid), dim3(T), (size_t)8 << L, c->stream, dev_ct, dev_labels, dev_mask, n, head, hu_min, \
-                           nbins, dev_hist, gpb);                                                                                     \
-    } while (0)
-#define BOA_HIST_BY_T(L)                                  \
-    do {                                                  \
-        if (HT == 256) BOA_HIST_LAUNCH(L, 256);           \
-        else if (HT == 512) BOA_HIST_LAUNCH(L, 512);      \
-        else BOA_HIST_LAUNCH(L, 1024);                    \
-    } while (0)
-        if (hist_log2 == 14)
-            BOA_HIST_BY_T(14);
-        else if (hist_log2 == 13)
-            BOA_HIST_BY_T(13);
-        else
-            BOA_HIST_BY_T(12);
-#undef BOA_HIST_BY_T
-#undef BOA_HIST_LAUNCH
+        static bool once = (hipFuncSetAttribute((const void*)k_label_hist<LOG2, HT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024), true);
+        (void)once;
+        hipLaunchKernelGGL((k_label_hist<LOG2, HT>), dim3(grid), dim3(HT), (size_t)8 << LOG2, c->stream, dev_ct, dev_labels, dev_mask, n, head,
+                           hu_min, nbins, dev_hist, gpb);
     } else {
         hipLaunchKernelGGL(k_label_hist_scalar, dim3((unsigned)std::min<size_t>((n + 255) / 256, (size_t)c->cu_count * 32)), dim3(256), 0,
                            c->stream, dev_ct, dev_labels, dev_mask, n, hu_min, nbins, dev_hist);
@@ -614,9 +576,8 @@ extern "C" int boa_binary_erode(boa_ctx* c, const uint8_t* dev_mask, uint8_t* de
     const int lo = -center, hi = k - 1 - center;
     const size_t n = (size_t)Z * Y * X;
     // bit-mask form (csrc/ccl_bits.hip): 1 byte read + 1 byte written per voxel and three passes over 1 / 8 byte per voxel, instead of
-    // three byte passes of one thread per voxel (1.9 ms -> 0.2 ms per 512^3 mask); $BOA_ERODE_BYTES=1 keeps the byte passes
-    static const bool bytes_only = getenv("BOA_ERODE_BYTES") != nullptr;
-    if (!bytes_only && lo > -32 && hi < 32) return boa_bits_erode_u8(c, dev_mask, dev_out, Z, Y, X, lo, hi);
+    // three byte passes of one thread per voxel (1.9 ms -> 0.2 ms per 512^3 mask); the byte passes take reaches of 32 and more
+    if (lo > -32 && hi < 32) return boa_bits_erode_u8(c, dev_mask, dev_out, Z, Y, X, lo, hi);
     unsigned grid = (unsigned)((n + 255) / 256);
     KernelTimer t(c, BOA_K_AGG, 0, (double)n * 6.0);
     hipLaunchKernelGGL(k_erode_axis, dim3(grid), dim3(256), 0, c->stream, dev_mask, dev_out, Z, Y, X, 2, lo, hi);
@@ -664,51 +625,10 @@ __device__ __forceinline__ void uf_union(int* L, int a, int b) {
     }
 }
 
-__global__ __launch_bounds__(256) void k_ccl_init(const unsigned char* __restrict__ mask, size_t n, int* __restrict__ L) {
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) L[i] = mask[i] ? (int)i : -1;
-}
-
-__global__ __launch_bounds__(256) void k_ccl_merge(const unsigned char* __restrict__ mask, int Z, int Y, int X, int* L) {
-    const size_t n = (size_t)Z * Y * X;
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n || !mask[i]) return;
-    const int x = (int)(i % X);
-    const int y = (int)((i / X) % Y);
-    const int z = (int)(i / ((size_t)X * Y));
-    // The 13 neighbours with larger linear index: (x+1) in this row and the x-1, x, x+1 triples of the four "later" rows
-    // (dz,dy) = (0,1), (1,-1), (1,0), (1,1).  When the left neighbour (x-1) of this row is foreground it is in our component
-    // and has already linked itself to the x-2, x-1, x voxels of those rows, so only their x+1 voxel is new information;
-    // likewise within a triple one link is enough when consecutive voxels of the later row are foreground (they are linked to
-    // each other by that row's own x+1 link).  This cuts the unions from up to 13 to ~5 per voxel without changing the
-    // components.
-    const bool left = x > 0 && mask[i - 1];
-    if (x + 1 < X && mask[i + 1]) uf_union(L, (int)i, (int)(i + 1));
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int dz = r == 0 ? 0 : 1, dy = r == 0 ? 1 : r - 2;
-        const int zz = z + dz, yy = y + dy;
-        if (zz >= Z || yy < 0 || yy >= Y) continue;
-        const size_t row = ((size_t)zz * Y + yy) * X;
-        const bool m0 = x > 0 && mask[row + x - 1], m1 = mask[row + x] != 0, m2 = x + 1 < X && mask[row + x + 1];
-        if (!left) {
-            if (m1) {
-                uf_union(L, (int)i, (int)(row + x));            // x-1 and x+1 of that row hang on its x voxel
-            } else {
-                if (m0) uf_union(L, (int)i, (int)(row + x - 1));
-                if (m2) uf_union(L, (int)i, (int)(row + x + 1));
-            }
-        } else if (m2 && !m1) {
-            uf_union(L, (int)i, (int)(row + x + 1));            // (with m1 set, x+1 is linked to x, which the left voxel linked)
-        }
-    }
-}
-
 // ---- two-level labelling: tiles of CCL_TX x CCL_TY x CCL_TZ voxels are labelled in LDS first, then only the unions that
-// cross a tile face go through global memory.  The per-voxel global version above spends its time in device-scope atomics and
-// pointer chasing through HBM (5.7 ms per 512^3 mask); inside a tile the same union-find runs on LDS words.  The result is the
-// same forest invariant (parent index <= own index, root = smallest linear index of the component), so k_ccl_compress and
-// everything downstream see identical roots and sizes.
+// cross a tile face go through global memory.  A per-voxel version (uf_union on every voxel) spent its time in device-scope atomics
+// and pointer chasing through HBM (5.7 ms per 512^3 mask); inside a tile the same union-find runs on LDS words.  Forest invariant:
+// parent index <= own index, root = smallest linear index of the component.
 #define CCL_TX 32
 #define CCL_TY 16
 #define CCL_TZ 16
@@ -937,8 +857,9 @@ __device__ __forceinline__ void ccl_border_voxel(const unsigned char* __restrict
         const bool m0 = x > 0 && mask[row + x - 1], m1 = mask[row + x] != 0, m2 = x + 1 < X && mask[row + x + 1];
         // (a link inside the tile was made in LDS; x - 1 / x + 1 of the other row hang on its x voxel through that row's own links)
         if (row_other) {
-            // the whole row lies in another tile.  As in k_ccl_merge: a foreground left neighbour (same face, so it runs this
-            // code too -- in this tile or the one to the left) has linked itself to x - 2, x - 1, x of that row already
+            // the whole row lies in another tile.  A foreground left neighbour (same face, so it runs this code too -- in this tile
+            // or the one to the left) has linked itself to x - 2, x - 1, x of that row already, so only x + 1 is new; within the
+            // triple one link is enough when consecutive voxels of that row are foreground (that row's own x + 1 links join them)
             if (!left) {
                 if (m1) {
                     uf_union(L, (int)i, (int)(row + x));
@@ -982,80 +903,6 @@ __global__ __launch_bounds__(256) void k_ccl_border(const unsigned char* __restr
     }
 }
 
-#define CCL_VPT 8
-__global__ __launch_bounds__(256) void k_ccl_compress(size_t n, int* L, unsigned int* sizes, int* n_comp) {
-    // Each thread resolves CCL_VPT voxels (256 apart, so the loads stay coalesced) and run-length merges their roots; the wave
-    // then adds each distinct root's count with ONE atomic.  With one voxel per thread a single giant component (the inverted
-    // body mask: 90 % of 134 M voxels) meant 2 M atomics on the same address, which alone took ~20 ms.
-    const size_t base = (size_t)blockIdx.x * 256 * CCL_VPT + threadIdx.x;
-    int roots[CCL_VPT];
-    unsigned int cnts[CCL_VPT];
-    int np = 0, ncomp = 0;
-#pragma unroll
-    for (int k = 0; k < CCL_VPT; ++k) {
-        roots[k] = -1;
-        cnts[k] = 0;
-    }
-#pragma unroll
-    for (int k = 0; k < CCL_VPT; ++k) {
-        const size_t i = base + (size_t)k * 256;
-        if (i < n && L[i] >= 0) {
-            int root = (int)i;
-            int p = L[root];
-            while (p != root) {
-                root = p;
-                p = L[root];
-            }
-            L[i] = root;  // values only ever move towards the root: a concurrent walker through i just gets there sooner
-            if (root == (int)i) ++ncomp;
-            bool merged = false;
-#pragma unroll
-            for (int q = 0; q < CCL_VPT; ++q)
-                if (!merged && q < np && roots[q] == root) {
-                    ++cnts[q];
-                    merged = true;
-                }
-            if (!merged) {
-#pragma unroll
-                for (int q = 0; q < CCL_VPT; ++q)
-                    if (q == np) {
-                        roots[q] = root;
-                        cnts[q] = 1;
-                    }
-                ++np;
-            }
-        }
-    }
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int q = 0; q < CCL_VPT; ++q) {
-        bool mine = q < np;
-        const int root = roots[q];
-        const unsigned int cnt = cnts[q];
-        unsigned long long active = __ballot(mine);
-        while (active) {
-            const int leader = __ffsll((long long)active) - 1;
-            const int r = __shfl(root, leader);
-            const bool match = mine && root == r;
-            const unsigned long long same = __ballot(match);
-            unsigned int v = match ? cnt : 0u;
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-            if (lane == leader) atomicAdd(&sizes[r], v);
-            if (match) mine = false;
-            active &= ~same;
-        }
-    }
-    // number of components: wave sum, one atomic per wave
-    unsigned int nc = (unsigned int)ncomp;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) nc += __shfl_xor(nc, m);
-    if (lane == 0 && nc) atomicAdd(n_comp, (int)nc);
-}
-
-// note on k_ccl_compress: path compression writes L[i] = root while other threads may still walk through i.
-// A walker that reads the new value simply jumps to the root sooner: values only ever move towards the root.
-
 extern "C" int boa_ccl26(boa_ctx* c, const uint8_t* dev_mask, int Z, int Y, int X, int32_t* dev_roots,
                          uint32_t* dev_sizes, int* host_n_components) {
     BOA_REQUIRE(c && dev_mask && dev_roots && dev_sizes && Z > 0 && Y > 0 && X > 0, "boa_ccl26: bad argument");
@@ -1065,10 +912,8 @@ extern "C" int boa_ccl26(boa_ctx* c, const uint8_t* dev_mask, int Z, int Y, int 
     // synchronise (the BCA post-processing chains 16 of these per volume)
     int* d_count = nullptr;
     BOA_TRY(boa_malloc(c, sizeof(int), (void**)&d_count));
-    static const bool flat = getenv("BOA_CCL_FLAT") != nullptr;  // the one-level version (A/B switch)
     {   // (an early return must hand the pooled counter back)
-        hipError_t e0 = hipMemsetAsync(d_count, 0, sizeof(int), c->stream);
-        if (e0 == hipSuccess && flat) e0 = hipMemsetAsync(dev_sizes, 0, n * sizeof(uint32_t), c->stream);
+        const hipError_t e0 = hipMemsetAsync(d_count, 0, sizeof(int), c->stream);
         if (e0 != hipSuccess) {
             boa_free(c, d_count);
             BOA_HIP_TRY(e0);
@@ -1076,23 +921,16 @@ extern "C" int boa_ccl26(boa_ctx* c, const uint8_t* dev_mask, int Z, int Y, int 
     }
     unsigned grid = (unsigned)((n + 255) / 256);
     KernelTimer t(c, BOA_K_MORPH, 0, (double)n * 14.0);
-    if (flat) {
-        hipLaunchKernelGGL(k_ccl_init, dim3(grid), dim3(256), 0, c->stream, dev_mask, n, dev_roots);
-        hipLaunchKernelGGL(k_ccl_merge, dim3(grid), dim3(256), 0, c->stream, dev_mask, Z, Y, X, dev_roots);
-        hipLaunchKernelGGL(k_ccl_compress, dim3((unsigned)((n + 256 * CCL_VPT - 1) / (256 * CCL_VPT))), dim3(256), 0, c->stream, n, dev_roots,
-                           dev_sizes, d_count);
-    } else {
-        const int tx = (X + CCL_TX - 1) / CCL_TX, ty = (Y + CCL_TY - 1) / CCL_TY, tz = (Z + CCL_TZ - 1) / CCL_TZ;
-        hipLaunchKernelGGL(k_ccl_local, dim3((unsigned)((size_t)tx * ty * tz)), dim3(256), 0, c->stream, dev_mask, Z, Y, X, tx, ty, dev_roots,
-                           dev_sizes);
-        hipLaunchKernelGGL(k_ccl_border, dim3((unsigned)((X + 255) / 256), (unsigned)Y, (unsigned)tz), dim3(256), 0, c->stream, dev_mask, Z, Y, X,
-                           dev_roots, 0);
-        hipLaunchKernelGGL(k_ccl_border, dim3((unsigned)((X + 255) / 256), (unsigned)(2 * ty), (unsigned)Z), dim3(256), 0, c->stream, dev_mask, Z,
-                           Y, X, dev_roots, 1);
-        hipLaunchKernelGGL(k_ccl_border, dim3((unsigned)(((size_t)2 * tx * Y + 255) / 256), 1, (unsigned)Z), dim3(256), 0, c->stream, dev_mask, Z, Y,
-                           X, dev_roots, 2);
-        hipLaunchKernelGGL(k_ccl_resolve, dim3(grid), dim3(256), 0, c->stream, n, dev_roots, dev_sizes, d_count);
-    }
+    const int tx = (X + CCL_TX - 1) / CCL_TX, ty = (Y + CCL_TY - 1) / CCL_TY, tz = (Z + CCL_TZ - 1) / CCL_TZ;
+    hipLaunchKernelGGL(k_ccl_local, dim3((unsigned)((size_t)tx * ty * tz)), dim3(256), 0, c->stream, dev_mask, Z, Y, X, tx, ty, dev_roots,
+                       dev_sizes);
+    hipLaunchKernelGGL(k_ccl_border, dim3((unsigned)((X + 255) / 256), (unsigned)Y, (unsigned)tz), dim3(256), 0, c->stream, dev_mask, Z, Y, X,
+                       dev_roots, 0);
+    hipLaunchKernelGGL(k_ccl_border, dim3((unsigned)((X + 255) / 256), (unsigned)(2 * ty), (unsigned)Z), dim3(256), 0, c->stream, dev_mask, Z,
+                       Y, X, dev_roots, 1);
+    hipLaunchKernelGGL(k_ccl_border, dim3((unsigned)(((size_t)2 * tx * Y + 255) / 256), 1, (unsigned)Z), dim3(256), 0, c->stream, dev_mask, Z, Y,
+                       X, dev_roots, 2);
+    hipLaunchKernelGGL(k_ccl_resolve, dim3(grid), dim3(256), 0, c->stream, n, dev_roots, dev_sizes, d_count);
     t.stop();
     hipError_t e = hipGetLastError();
     if (host_n_components && e == hipSuccess) {

@@ -125,14 +125,6 @@ size_t conv_ws_lds_bytes(int HV, int taps, int ncc, int Cout);
 bool conv_ws_supported(const int k[3], int HV);
 bool conv_ws_resident(int HV, int taps, int ncc, int Cout);
 
-static int conv_variant_override() {
-    static int v = [] {
-        const char* e = getenv("BOA_CONV_VARIANT");
-        return e ? atoi(e) : -1;
-    }();
-    return v;
-}
-
 // Pick the wave M-tile shape, the block tile and the kernel variant.  Cost model (cycles per 32-voxel M-tile):
 //   variant 1 (k_conv_ws): chunk time = max(MFMA time of the consumers, staging time of the producers) + barrier;
 //   variant 0 (k_conv_mfma): MFMA and staging serialised inside a block, partly hidden by the second block on the CU.
@@ -142,9 +134,7 @@ bool choose_conv_tile(const ConvGeom& g, int cu_count, ConvTile* out, bool x3) {
     const int ncc = x3 ? g.Cin / 8 : g.Cin / 16;   // split-precision mode: 8 real channels per staged chunk, two MFMAs per tap
     double best_cost = 1e30;
     bool found = false;
-    const int force = x3 ? -1 : conv_variant_override();
-    // (split-precision mode: the stride-2 layers take the N-split kernel too -- its stride-1 instantiation is not built for X3)
-    if (force < 0 && conv_ns_applicable(g) && !(x3 && g.s[0] != 2) && !(x3 && getenv("BOA_X3_NO_NS"))) {  // N-split kernel (conv_ns.hip): stride-2 and deep layers, fixed tile shape
+    if (conv_ns_applicable(g)) {  // N-split kernel (conv_ns.hip): stride-2 layers (split-precision mode too), fixed tile shape
         conv_ns_tile(g, out);
         return true;
     }
@@ -159,7 +149,7 @@ bool choose_conv_tile(const ConvGeom& g, int cu_count, ConvTile* out, bool x3) {
             if (!relax && (w1 > next_pow2(dims[1]) || w0 > next_pow2(dims[0]))) continue;
             const int w[3] = {w0, w1, w2};
             for (int variant : {1, 0}) {
-                if ((force >= 0 && variant != force) || (x3 && variant != 1)) continue;
+                if (x3 && variant != 1) continue;
                 for (int R : {4, 2, 1}) {
                     const int M = 4 * R;
                     for (int b0 = 1; b0 <= M; b0 *= 2)
@@ -183,7 +173,7 @@ bool choose_conv_tile(const ConvGeom& g, int cu_count, ConvTile* out, bool x3) {
                             // launches' LDS cycles were conflicts (profiles/r05_pmc_lds.txt).  The planes are padded to xs = w2 (mod 16): the
                             // rows of every lane group then tile a 256-byte bank row.  HV below counts the padded planes.
                             int xs = h[1] * h[2];
-                            if (variant == 1 && w0 > 1 && w1 == 1 && w2 >= 8 && w2 <= 16 && g.s[0] == 1 && g.s[2] == 1 && !getenv("BOA_WS_NO_XPAD"))
+                            if (variant == 1 && w0 > 1 && w1 == 1 && w2 >= 8 && w2 <= 16 && g.s[0] == 1 && g.s[2] == 1)
                                 while (xs % 16 != w2 % 16) ++xs;
                             if (variant == 1) HV = (long long)h[0] * xs;
                             if (variant == 1 && !conv_ws_supported(g.k, (int)HV)) continue;
@@ -191,12 +181,6 @@ bool choose_conv_tile(const ConvGeom& g, int cu_count, ConvTile* out, bool x3) {
                                                             : conv_lds_bytes((int)HV, taps);
                             if (lds > 160 * 1024 - 2048) continue;   // (2 KiB stay free for the split-precision kernel's bias table)
                             const long long nblocks = tiles * (g.Cout / 32) * g.N;
-                            // experiment hook: BOA_CONV_TILE="w0,w1,w2,b0,b1,b2" forces that shape wherever it is legal
-                            static int ft[6] = {0, 0, 0, 0, 0, 0};
-                            static const bool have_ft = getenv("BOA_CONV_TILE") &&
-                                sscanf(getenv("BOA_CONV_TILE"), "%d,%d,%d,%d,%d,%d", ft, ft + 1, ft + 2, ft + 3, ft + 4, ft + 5) == 6;
-                            const bool forced = have_ft && variant == 1 && g.s[0] == 1 && w0 == ft[0] && w1 == ft[1] && w2 == ft[2] &&
-                                                b0 == ft[3] && b1 == ft[4] && b2 == ft[5];
                             const double valid = (double)dims[0] * dims[1] * dims[2];
                             const double waste = (double)covered / valid;
                             // LDS fragment reads are conflict-free when a wave row is contiguous (w2 lanes at the
@@ -221,7 +205,7 @@ bool choose_conv_tile(const ConvGeom& g, int cu_count, ConvTile* out, bool x3) {
                             // epilogue + tile turnaround amortised over the chunks of a tile
                             const double t_tile = t_chunk * ncc + (variant == 1 ? 3000.0 : 6000.0);
                             const double rounds = std::ceil((double)nblocks / slots);
-                            const double cost = forced ? -1.0 : t_tile * rounds * waste / (double)M * (slots / (double)nblocks);
+                            const double cost = t_tile * rounds * waste / (double)M * (slots / (double)nblocks);
                             if (cost < best_cost) {
                                 best_cost = cost;
                                 found = true;
@@ -1081,8 +1065,7 @@ __global__ __launch_bounds__(256) void k_conv_first_mfma(FirstMfmaArgs p) {
 }
 
 bool first_mfma_ok(int Cin, const int P[3], const int k[3], int Cout) {
-    static const bool off = getenv("BOA_FIRST_MFMA") && atoi(getenv("BOA_FIRST_MFMA")) == 0;
-    return !off && Cin == 1 && Cout == 32 && k[0] == 3 && k[1] == 3 && k[2] == 3 && P[0] % MF0 == 0 && P[1] % MF1 == 0 && P[2] % MF2 == 0;
+    return Cin == 1 && Cout == 32 && k[0] == 3 && k[1] == 3 && k[2] == 3 && P[0] % MF0 == 0 && P[1] % MF1 == 0 && P[2] % MF2 == 0;
 }
 
 int conv_first_nblk(const int P[3], int cu_count) {
@@ -1107,13 +1090,6 @@ int launch_conv_first(boa_ctx* ctx, const float* volume, const int V[3], const i
     const size_t pvol = (size_t)PD[0] * PD[1] * PD[2];
     const double vox = (double)N * P[0] * P[1] * P[2];
     KernelTimer tm(ctx, BOA_K_CONV_FIRST, 2.0 * vox * k[0] * k[1] * k[2] * Cin * Cout, vox * (4.0 * Cin + 2.0 * Cout));
-    static const bool fuse_gather = !(getenv("BOA_FIRST_GATHER") && atoi(getenv("BOA_FIRST_GATHER")) == 1);  // 1: separate gather kernel
-    const bool fused = fuse_gather && first_mfma_ok(Cin, P, k, Cout);
-    if (!fused)
-    hipLaunchKernelGGL(k_gather_patches, dim3((unsigned)((pvol + 255) / 256), Cin, N), dim3(256), 0, ctx->stream, volume,
-                       dev_origins, V[0], V[1], V[2], vol_off ? vol_off[0] : 0, vol_off ? vol_off[1] : 0,
-                       vol_off ? vol_off[2] : 0, Cin, P[0], P[1], P[2], (k[0] - 1) / 2, (k[1] - 1) / 2, (k[2] - 1) / 2, PD[0],
-                       PD[1], PD[2], flip_mask, padded_scratch);
     const int nblk_tab = conv_first_nblk(P, ctx->cu_count);
     if (nblk_out) *nblk_out = nblk_tab;
     if (first_mfma_ok(Cin, P, k, Cout)) {
@@ -1122,7 +1098,7 @@ int launch_conv_first(boa_ctx* ctx, const float* volume, const int V[3], const i
         m.wscale = X3_HEAD_WSCALE;   // (first-conv weights are O(0.1 .. 1) like the head's: one fixed power of two)
         m.winv = 1.0f / X3_HEAD_WSCALE;
         m.padded = padded_scratch; m.PX = PD[0]; m.PY = PD[1]; m.PZ = PD[2];
-        m.vol = fused ? volume : nullptr; m.origins = dev_origins; m.flip = flip_mask;
+        m.vol = volume; m.origins = dev_origins; m.flip = flip_mask;
         m.V0 = V[0]; m.V1 = V[1]; m.V2 = V[2];
         m.o0 = vol_off ? vol_off[0] : 0; m.o1 = vol_off ? vol_off[1] : 0; m.o2 = vol_off ? vol_off[2] : 0;
         m.N = N; m.P0 = P[0]; m.P1 = P[1]; m.P2 = P[2];
@@ -1131,8 +1107,7 @@ int launch_conv_first(boa_ctx* ctx, const float* volume, const int V[3], const i
         m.vw = std::min(m.t0 * m.t1 * m.t2, ctx->cu_count);
         // (physical workgroup b runs the virtual workgroups b, b + G, ...: any G gives the same results; more than one workgroup
         //  per CU hides the halo gather's and the stores' latency -- the kernel is a 3.4 GB write per 25 tiles)
-        static const int grid_mult = getenv("BOA_FIRST_GRID") ? std::max(1, atoi(getenv("BOA_FIRST_GRID"))) : 4;
-        const dim3 fgrid((unsigned)std::min<long long>((long long)m.vw * N, (long long)ctx->cu_count * grid_mult));
+        const dim3 fgrid((unsigned)std::min<long long>((long long)m.vw * N, (long long)ctx->cu_count * 4));
         if (out32) {
             hipLaunchKernelGGL(k_conv_first_mfma<true>, fgrid, dim3(256), 0, ctx->stream, m);
             ctx->counters[BOA_CNT_X3]++;
@@ -1144,6 +1119,11 @@ int launch_conv_first(boa_ctx* ctx, const float* volume, const int V[3], const i
         BOA_HIP_TRY(hipGetLastError());
         return BOA_OK;
     }
+    // (the MFMA kernel gathers its halo from the volume itself; the VALU kernel reads a zero-padded copy)
+    hipLaunchKernelGGL(k_gather_patches, dim3((unsigned)((pvol + 255) / 256), Cin, N), dim3(256), 0, ctx->stream, volume,
+                       dev_origins, V[0], V[1], V[2], vol_off ? vol_off[0] : 0, vol_off ? vol_off[1] : 0,
+                       vol_off ? vol_off[2] : 0, Cin, P[0], P[1], P[2], (k[0] - 1) / 2, (k[1] - 1) / 2, (k[2] - 1) / 2, PD[0],
+                       PD[1], PD[2], flip_mask, padded_scratch);
     FirstArgs a;
     a.nblk = nblk_tab;
     a.padded = padded_scratch; a.PX = PD[0]; a.PY = PD[1]; a.PZ = PD[2];
@@ -1782,11 +1762,8 @@ __global__ __launch_bounds__(256) void k_convt_deep(ConvTArgs p) {
 }
 
 int convt_mfma_form(int Cin, const int s[3], bool norm_src) {
-    static const bool no_rw = getenv("BOA_CONVT_NO_RW") != nullptr;
-    static const bool no_deep = getenv("BOA_CONVT_NO_DEEP") != nullptr;
-    static const bool deep128 = getenv("BOA_CONVT_DEEP128") != nullptr;   // experiment: the 32^3 -> 64^3 layer on k_convt_deep too
-    if (!no_deep && s[0] == 2 && s[1] == 2 && s[2] == 2 && norm_src && (Cin == 256 || Cin == 320 || (deep128 && Cin == 128))) return 2;
-    if (!no_rw && s[2] == 2 && norm_src && (Cin == 64 || Cin == 128)) return 1;
+    if (s[0] == 2 && s[1] == 2 && s[2] == 2 && norm_src && (Cin == 256 || Cin == 320)) return 2;
+    if (s[2] == 2 && norm_src && (Cin == 64 || Cin == 128)) return 1;
     return 0;
 }
 
@@ -1821,38 +1798,26 @@ int launch_convt_mfma(boa_ctx* ctx, const ActSrc& src, int N, const int din[3], 
         // the (x tap, y tap, cout chunk) passes are spread over gridDim.y until there is about one block per CU (one fits: 64-80 KiB of
         // weight buffers), at least two passes per block so that the weight DMA overlaps (measured at 25 tiles: 16^3 124 / 140 / 151 /
         // 189 us at 1 / 2 / 4 / 8 slices, 8^3 139 / 81 / 48 / 58, 4^3 166 / 94 / 52 / 34 and 22 at 20)
-        static const int gy_force = getenv("BOA_CONVT_DEEP_GY") ? atoi(getenv("BOA_CONVT_DEEP_GY")) : 0;
-        const int gyd = gy_force > 0 ? std::min(gy_force, npairs) : std::max(1, std::min(npairs / 2, ctx->cu_count / std::max(gxd, 1)));
+        const int gyd = std::max(1, std::min(npairs / 2, ctx->cu_count / std::max(gxd, 1)));
         const size_t ldsd = (size_t)2 * 2 * ncc * 1024 + 4 * (2 * 32 * 2 * 32) + (size_t)Cout * sizeof(float);
         static bool od = (hipFuncSetAttribute((const void*)k_convt_deep<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-                          hipFuncSetAttribute((const void*)k_convt_deep<20>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-                          hipFuncSetAttribute((const void*)k_convt_deep<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), true);
+                          hipFuncSetAttribute((const void*)k_convt_deep<20>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), true);
         (void)od;
-        if (ncc == 8)
-            hipLaunchKernelGGL(k_convt_deep<8>, dim3(gxd, gyd), dim3(256), ldsd, ctx->stream, a);
-        else if (ncc == 16)
+        if (ncc == 16)
             hipLaunchKernelGGL(k_convt_deep<16>, dim3(gxd, gyd), dim3(256), ldsd, ctx->stream, a);
         else
             hipLaunchKernelGGL(k_convt_deep<20>, dim3(gxd, gyd), dim3(256), ldsd, ctx->stream, a);
     } else if (rw) {
         // register-weights variant: G groups of 32 voxels per wave (G x 128 voxels per block)
-        static const int g128 = getenv("BOA_CONVT_G128") ? atoi(getenv("BOA_CONVT_G128")) : 2;   // (32^3 -> 64^3: 125 -> 105 us per 8 tiles: two workgroups per CU)
-        static const int g64 = getenv("BOA_CONVT_G64") ? atoi(getenv("BOA_CONVT_G64")) : 2;
-        const int G = src.C == 64 ? g64 : g128;
+        const int G = 2;   // (32^3 -> 64^3: 125 -> 105 us per 8 tiles: two workgroups per CU)
         const int gxr = (int)((total + 128 * G - 1) / (128 * G));
         const int gyr = std::min(npairs, std::max(1, ceil_div(gy_mult * ctx->cu_count, gxr)));
         const size_t ldsr = (size_t)4 * ((size_t)G * (src.C / 16) * 1024 + 2 * 32 * 2 * 32);
-        static bool o1 = (hipFuncSetAttribute((const void*)k_convt_mfma_rw<2, 4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-                          hipFuncSetAttribute((const void*)k_convt_mfma_rw<2, 4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-                          hipFuncSetAttribute((const void*)k_convt_mfma_rw<2, 8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
+        static bool o1 = (hipFuncSetAttribute((const void*)k_convt_mfma_rw<2, 4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
                           hipFuncSetAttribute((const void*)k_convt_mfma_rw<2, 8, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), true);
         (void)o1;
-        if (src.C == 64 && G == 4)
-            hipLaunchKernelGGL((k_convt_mfma_rw<2, 4, 4>), dim3(gxr, gyr), dim3(256), ldsr, ctx->stream, a);
-        else if (src.C == 64)
+        if (src.C == 64)
             hipLaunchKernelGGL((k_convt_mfma_rw<2, 4, 2>), dim3(gxr, gyr), dim3(256), ldsr, ctx->stream, a);
-        else if (G == 4)
-            hipLaunchKernelGGL((k_convt_mfma_rw<2, 8, 4>), dim3(gxr, gyr), dim3(256), ldsr, ctx->stream, a);
         else
             hipLaunchKernelGGL((k_convt_mfma_rw<2, 8, 2>), dim3(gxr, gyr), dim3(256), ldsr, ctx->stream, a);
     } else if (s[2] == 2)
@@ -2127,8 +2092,7 @@ int launch_head(boa_ctx* ctx, const __half* act, const float* ss, int F0, const 
     size_t lds = ((size_t)C * F0 + C + 2 * F0) * 4;
     double bytes = (double)pv * (2.0 * F0 + (logits_out ? 4.0 * C : (4.0 * (C + 1) + 2.0)));
     KernelTimer tm(ctx, BOA_K_HEAD_ACCUM, 2.0 * pv * F0 * C, bytes);
-    static const bool mfma_off = getenv("BOA_HEAD_MFMA") && atoi(getenv("BOA_HEAD_MFMA")) == 0;
-    const bool mfma_shape = !mfma_off && F0 == 32 && C <= 31 && P[2] % 32 == 0 && ((uintptr_t)act) % 16 == 0;
+    const bool mfma_shape = F0 == 32 && C <= 31 && P[2] % 32 == 0 && ((uintptr_t)act) % 16 == 0;
     const unsigned mfma_grid = (unsigned)std::min<size_t>(std::max<size_t>(pv / 32 / 4, 1), (size_t)ctx->cu_count * 8);
     // 16-byte accumulator accesses: the tile's z origin, the volume's z extent and the buffers must be 8-voxel aligned
     if (!logits_out && mfma_shape && start[2] % 8 == 0 && PV[2] % 8 == 0 && ((uintptr_t)acc) % 16 == 0 &&

@@ -10,19 +10,18 @@
 //     base + lane offset, a ring of three (dy, dz) tap groups, prefetched two groups = 24 MFMAs ahead, across chunk and tile
 //     boundaries) -- no weight staging, no LDS space, no LDS reads for weights;
 //   * the input (B) fragments come from the LDS halo with reuse along x: per (dy, dz) group the wave reads the S * 3 + 3 input
-//     planes once and feeds 12 MFMAs (stride 1: plane j serves the outputs r = j - dx; stride 2: the planes 2 r + dx), 0.5 /
-//     0.75 KiB of LDS reads per MFMA;
+//     planes once and feeds 12 MFMAs (plane j serves the outputs r with 2 r + dx = j), 0.75 KiB of LDS reads per MFMA;
 //   * producers (waves 4-7), tile sequence / virtual workgroups / run tables, deferred InstanceNorm in the staging, bias as the
 //     first MFMA's C operand, register-transpose epilogue and batch-invariant statistics are k_conv_ws's (conv_ws_dev.h).
 // tools/consumer_ns.hip is the isolated consumer loop (1.4-1.6 PFLOP/s with random operands, weights up to 5 MB from L2).
-// Instantiated for 3x3x3 kernels with stride 1 or 2 on all axes; everything else stays on k_conv_ws.
+// Instantiated for 3x3x3 kernels with stride 2 on all axes; everything else stays on k_conv_ws.
 #include <stdlib.h>
 
 #include "conv.h"
 
 #include "conv_ws_dev.h"
 
-// ---- LDS halo layout of the stride-2 instantiations ("SW") ------------------------------------------------
+// ---- LDS halo layout ("SW") -----------------------------------------------------------------------------
 // A consumer lane's voxel of M-tile plane x is (y, z) = (2 ly + dy, 2 lz + dz): in the linear [x][y][z] halo the 32 lanes of a k-half
 // sit 32 bytes apart along z and 2 * 17 * 16 = 544 bytes apart along y, i.e. on EVEN 16-byte slots only and on the same slots (mod 256
 // bytes) in three of the four ly rows -- ds_read_b128 is serviced in four fixed 16-lane groups ({0-3, 12-15, 20-27}, ...: hardware
@@ -35,10 +34,6 @@
 // of a 256-byte bank row exactly once; the tap offsets stay compile-time immediates.  The producers' stores (8-lane groups = 4
 // consecutive voxels x 2 k-half planes, 128-byte bank rows) stay conflict-free with the odd columns at slot 10 (= 2 mod 8) and the
 // planes' 64-byte skew.  Lanes past the halo store into one dummy slot behind the plane.
-#ifndef NS_SW
-#define NS_SW 1   // 0: the linear layout for every stride (A/B builds)
-#endif
-#define NS_SWZ(S) (NS_SW && (S) == 2)
 #define NS_SW_ROW 24
 #define NS_SW_YODD 5
 #define NS_SW_ZODD 10
@@ -46,10 +41,6 @@ __host__ __device__ constexpr int ns_sw_yp(int y) { return (y & 1) * NS_SW_YODD 
 __host__ __device__ constexpr int ns_sw_zp(int z) { return (z & 1) * NS_SW_ZODD + (z >> 1); }
 __host__ __device__ constexpr int ns_sw_slots() { return 9 * 9 * NS_SW_ROW; }            // slots of one k-half plane (+ 8 of padding: the dummy slot)
 __host__ __device__ constexpr int ns_sw_plane_bytes() { return (ns_sw_slots() + 8) * 16 + 64; }   // = 64 mod 128: the k-half planes' stores interleave
-
-#ifndef NS_PF2
-#define NS_PF2 1   // two producer register sets: halo loads a whole chunk interval ahead (see the producer loop); 0 = never
-#endif
 
 // prod_commit / prod_commit_x3 (conv_ws_dev.h) with a per-item LDS offset instead of the linear voxel index
 template <bool X3, bool SS, bool EDGE>
@@ -120,13 +111,12 @@ __device__ __forceinline__ void ns_commit_sw(const ConvArgs& p, ChunkRegs& rg, u
 // X3 (split-precision mode, see k_conv_ws): the chunk is 8 fp32 channels as hi / lo fp16 planes, the weight fragments come in
 // hi / lo pairs (lo = `lo_off` bytes behind hi in the packed array: the part stride Cout * 16) and every (plane, dx) pair is two MFMAs.
 // NR: slots of the weight ring (3 or 9: a divisor of the 9 groups, so the slot of a group does not depend on the chunk); group g + NR - 1 is
-// fetched while group g is consumed.  NR = 9 for the S = 2, RM = 2 instantiation: its groups are 6 MFMAs (192 cycles) long, two groups ahead
+// fetched while group g is consumed.  NR = 9 for the RM = 2 instantiation: its groups are 6 MFMAs (192 cycles) long, two groups ahead
 // was less than an L2 round trip (BOA_WS_TRACE: 3 900 / 2 850 cycles per chunk of 54 MFMAs).
 template <int S, int RM, bool X3, int NR>
 __device__ __forceinline__ void consume_chunk_x(const unsigned char* b0p, f32x16 (&acc)[RM], f16x8 (&a)[NR][3], f16x8 (&al)[X3 ? NR : 1][3],
                                                 const WS_GLOBAL unsigned char* wb, unsigned vcur, unsigned vnext, unsigned gs, unsigned lo_off) {
     constexpr int NB = S * (RM - 1) + 3;
-    constexpr int H1 = 3 * S + 3, H2 = 7 * S + 3;
     constexpr int MM = X3 ? 2 : 1;
     f16x8 b[NB];
     auto fetch_a = [&](unsigned vchunk, int g, int slot) {  // group g = dy * 3 + dz: taps g + 9 dx
@@ -143,7 +133,7 @@ __device__ __forceinline__ void consume_chunk_x(const unsigned char* b0p, f32x16
         }
     };
 #pragma unroll
-    for (int jj = 0; jj < NB; ++jj) b[jj] = *(const f16x8*)(b0p + (NS_SWZ(S) ? jj * 9 * NS_SW_ROW : jj * H1 * H2) * 16);
+    for (int jj = 0; jj < NB; ++jj) b[jj] = *(const f16x8*)(b0p + jj * 9 * NS_SW_ROW * 16);
     __builtin_amdgcn_sched_group_barrier(0x100, NB, 0);
 #pragma unroll
     for (int g = 0; g < 9; ++g) {
@@ -173,17 +163,18 @@ __device__ __forceinline__ void consume_chunk_x(const unsigned char* b0p, f32x16
                 __builtin_amdgcn_sched_group_barrier(0x008, 3 * MM, 0);
             if (g + 1 < 9) {
                 const int gn = g + 1, dy = gn / 3, dz = gn % 3;
-                b[jj] = *(const f16x8*)(b0p + (NS_SWZ(S) ? (jj * 9 + ns_sw_yp(dy)) * NS_SW_ROW + ns_sw_zp(dz) : (jj * H1 + dy) * H2 + dz) * 16);
+                b[jj] = *(const f16x8*)(b0p + ((jj * 9 + ns_sw_yp(dy)) * NS_SW_ROW + ns_sw_zp(dz)) * 16);
                 __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
             }
         }
     }
 }
 
-// S: conv stride (all axes); WN: consumer waves along the cout axis (cout group = WN chunks), 4 / WN wave rows along x;
-// RM: M-tiles (x-planes of 4 x 8 output voxels) per wave.  Block tile = (4 / WN) * RM planes.
+// S: conv stride (all axes, 2: the SW halo layout); WN: consumer waves along the cout axis (cout group = WN chunks), 4 / WN wave rows
+// along x; RM: M-tiles (x-planes of 4 x 8 output voxels) per wave.  Block tile = (4 / WN) * RM planes.
 template <int S, int WN, int RM, bool X3>
 __global__ __launch_bounds__(WS_THREADS) void k_conv_ns(ConvArgs p, int dbg_arg, const int* __restrict__ desc, int desc_row) {
+    static_assert(S == 2, "k_conv_ns: the halo layout is the stride-2 one");
 #ifdef WS_WITH_TRACE
     const int dbg = dbg_arg;
 #else
@@ -198,7 +189,7 @@ __global__ __launch_bounds__(WS_THREADS) void k_conv_ns(ConvArgs p, int dbg_arg,
     const int l31 = lane & 31;
     const int kh = lane >> 5;
     const int HV = p.h0 * p.h1 * p.h2;
-    const int plane = NS_SWZ(S) ? ns_sw_plane_bytes() : ws_plane_bytes(HV);
+    const int plane = ns_sw_plane_bytes();
     const int ncc = (p.C0 + p.C1) / 16;
     const int buf_bytes = 2 * plane;  // LDS: [halo buf 0][halo buf 1], each two k-octet planes
     unsigned char* bufs = smem;
@@ -242,11 +233,7 @@ __global__ __launch_bounds__(WS_THREADS) void k_conv_ns(ConvArgs p, int dbg_arg,
         // without copies.  A/B on one box (tools/ab_layers.sh, batch 8): 64 -> 128 @64^3 -5 %, 128 -> 256 @32^3 -8 %, 256 -> 320 @16^3
         // -8 %; the 32 -> 64 layer at 128^3 (RM = 2: HBM-cold input, 3.6 TB/s of halo traffic) +16 % -- twice the loads in flight per
         // CU there only deepen the queue in front of the memory side -- so that instantiation keeps one set.
-#ifdef NS_PF2_ALL
-        constexpr bool PF2 = NS_PF2 != 0;   // (A/B builds)
-#else
-        constexpr bool PF2 = NS_PF2 && RM == 4;
-#endif
+        constexpr bool PF2 = RM == 4;
         ChunkRegs rgA, rgB;
         auto clear_regs = [&](ChunkRegs& rg) {
 #pragma unroll
@@ -287,12 +274,7 @@ __global__ __launch_bounds__(WS_THREADS) void k_conv_ns(ConvArgs p, int dbg_arg,
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 NS_PSTAMP(7);
             }
-            if constexpr (NS_SWZ(S))
-                ns_commit_sw<X3>(p, rg, dst, ldso, q, HV, plane, dbg);
-            else if constexpr (X3)
-                prod_commit_x3(p, rg, dst, q, HV, plane, dbg);
-            else
-                prod_commit(p, rg, dst, q, HV, plane, dbg);
+            ns_commit_sw<X3>(p, rg, dst, ldso, q, HV, plane, dbg);
             NS_PSTAMP(2);
         };
         if (live && my_chunks > 0) {
@@ -348,8 +330,7 @@ __global__ __launch_bounds__(WS_THREADS) void k_conv_ns(ConvArgs p, int dbg_arg,
     const int ly = l31 >> 3, lz = l31 & 7;
     const int nchunks_out = p.Cout / 32;
     // this lane's voxel in plane 0 of the wave's M-tiles, its k-half plane
-    constexpr int H1 = 3 * S + 3, H2 = 7 * S + 3;  // halo extents along y, z (host: conv_ns_tile)
-    const int hoff = (NS_SWZ(S) ? ((2 * (wm * RM)) * 9 + ly) * NS_SW_ROW + lz : ((S * (wm * RM)) * H1 + S * ly) * H2 + S * lz) * 16 + kh * plane;
+    const int hoff = (((2 * (wm * RM)) * 9 + ly) * NS_SW_ROW + lz) * 16 + kh * plane;
     const int srel0 = ly * p.Wo + lz;
     const size_t out_vox = (size_t)p.Do * p.Ho * p.Wo;
     const int nslots = p.nslots;
@@ -428,11 +409,7 @@ __global__ __launch_bounds__(WS_THREADS) void k_conv_ns(ConvArgs p, int dbg_arg,
                     for (int gq = 0; gq < 4; ++gq) {
                         unsigned ol = ((unsigned)srel0 * 32u + (unsigned)kh * 16u) + (unsigned)gq * ((unsigned)out_vox * 32u);
                         asm volatile("" : "+v"(ol));
-#ifndef WS_TEMPORAL_STORES
                         __builtin_nontemporal_store(f32x4_t{v[gq * 4 + 0], v[gq * 4 + 1], v[gq * 4 + 2], v[gq * 4 + 3]}, (WS_GLOBAL f32x4_t*)(dst + ol));
-#else
-                        *(WS_GLOBAL f32x4_t*)(dst + ol) = f32x4_t{v[gq * 4 + 0], v[gq * 4 + 1], v[gq * 4 + 2], v[gq * 4 + 3]};
-#endif
                     }
                 }
                 continue;
@@ -457,16 +434,11 @@ __global__ __launch_bounds__(WS_THREADS) void k_conv_ns(ConvArgs p, int dbg_arg,
                 WS_GLOBAL unsigned char* dst = sgpr_ptr(p.out + (obase + (size_t)mrel * 16));
                 unsigned ol = olane;
                 asm volatile("" : "+v"(ol));
-#ifndef WS_TEMPORAL_STORES
                 // non-temporal stores: the layer's output is not read again before the launch ends, so it need not displace halo lines from
                 // the XCD's L2 (A/B on one box with tools/build_alt.sh, layers repeated at the power cap: 1 780 -> 1 767, 957 -> 946,
                 // 823 -> 817 us; bench step 1 820 -> 1 806 ms; the HBM-bound first conv measured 0 ... -10 % with them and keeps plain stores)
                 __builtin_nontemporal_store(u32x4_t{w[0], w[1], w[2], w[3]}, (WS_GLOBAL u32x4_t*)(dst + ol));
                 __builtin_nontemporal_store(u32x4_t{w[4], w[5], w[6], w[7]}, (WS_GLOBAL u32x4_t*)(dst + ol + 16));
-#else
-                *(WS_GLOBAL u32x4_t*)(dst + ol) = u32x4_t{w[0], w[1], w[2], w[3]};
-                *(WS_GLOBAL u32x4_t*)(dst + ol + 16) = u32x4_t{w[4], w[5], w[6], w[7]};
-#endif
             }
         }
     };
@@ -477,7 +449,7 @@ __global__ __launch_bounds__(WS_THREADS) void k_conv_ns(ConvArgs p, int dbg_arg,
     const unsigned voff = X3 ? (unsigned)l31 * 16u : ((unsigned)kh * (unsigned)p.Cout + (unsigned)l31) * 16u;   // (X3: both k-halves read the same hi / lo fragments)
     const unsigned lo_off = (unsigned)p.Cout * 16u;
     auto woff = [&](int cc, int ch) -> unsigned { return voff + (unsigned)cc * 27u * gs + (unsigned)ch * 512u; };
-    constexpr int NR = (S == 2 && RM == 2 && !X3) ? 9 : 3;
+    constexpr int NR = (RM == 2 && !X3) ? 9 : 3;
     f16x8 a[NR][3];
     f16x8 al[X3 ? NR : 1][3];
 #pragma unroll
@@ -590,21 +562,15 @@ const int* ws_run_table(boa_ctx* ctx, const ConvArgs& a, int tiles_per_sample, i
 const int* ws_desc_table(boa_ctx* ctx, const ConvArgs& a, int tiles_per_sample, int grid, int* row_out);
 int conv_ws_vw(int tiles_per_sample, int cu_count);
 
-static size_t ns_plane_host(int HV) { return ((size_t)(HV + WS_PROD / 2 - 1) / (WS_PROD / 2)) * (WS_PROD / 2) * 16 + 64; }
-
 // The layers k_conv_ns takes (a function of the layer geometry only): 3x3x3 kernels with stride 2 on all axes, at least two cout
 // chunks and an output of at least 8^3 voxels -- measured per layer against k_conv_ws on the `total` geometry (8 tiles): 32 -> 64
 // @128^3, 64 -> 128 @64^3 453 -> 194 us, 128 -> 256 @32^3 224 -> 96 us, 256 -> 320 @16^3 114 -> 81 us.  The stride-1 layers with
 // Cout >= 128 run at par with k_conv_ws (the epilogue of four M-tiles per 128-voxel tile costs what the fourfold halo reuse
-// gains) and the 8^3 / 4^3 layers are latency-bound either way; BOA_NS_ALL=1 sends them here as well (experiments).
+// gains) and the 8^3 / 4^3 layers are latency-bound either way.
 bool conv_ns_applicable(const ConvGeom& g) {
-    static const bool off = getenv("BOA_NO_NS") != nullptr;
-    static const bool all = getenv("BOA_NS_ALL") != nullptr;
-    if (off) return false;
     const bool k333 = g.k[0] == 3 && g.k[1] == 3 && g.k[2] == 3;
-    const bool s1 = g.s[0] == 1 && g.s[1] == 1 && g.s[2] == 1, s2 = g.s[0] == 2 && g.s[1] == 2 && g.s[2] == 2;
+    const bool s2 = g.s[0] == 2 && g.s[1] == 2 && g.s[2] == 2;
     if (!k333 || g.Cout % 32 != 0) return false;
-    if (all) return (s1 || s2) && g.Cout >= 128 && g.Do >= 2 && g.Ho >= 2 && g.Wo >= 4;
     return s2 && g.Cout >= 64 && g.Do >= 8 && g.Ho >= 8 && g.Wo >= 8;
 }
 
@@ -619,14 +585,12 @@ void conv_ns_tile(const ConvGeom& g, ConvTile* t) {
     t->b[0] = 4; t->b[1] = 1; t->b[2] = 1;
     const int ext[3] = {4, 4, 8};
     const int dims[3] = {g.Do, g.Ho, g.Wo};
-    size_t HV = 1;
     for (int d = 0; d < 3; ++d) {
         t->h[d] = (ext[d] - 1) * g.s[d] + 3;
         t->tiles[d] = (dims[d] + ext[d] - 1) / ext[d];
-        HV *= (size_t)t->h[d];
     }
-    // two halo buffers (stride 2: the de-interleaved layout, see NS_SW_ROW) + the bias table
-    t->lds_bytes = 4 * (NS_SWZ(g.s[0]) ? (size_t)ns_sw_plane_bytes() : ns_plane_host((int)HV)) + (size_t)g.Cout * sizeof(float);
+    // two halo buffers (the de-interleaved layout, see NS_SW_ROW) + the bias table
+    t->lds_bytes = 4 * (size_t)ns_sw_plane_bytes() + (size_t)g.Cout * sizeof(float);
 }
 
 int conv_ns_ncy(int Cout) { return (Cout / 32 + ns_wn(Cout) - 1) / ns_wn(Cout); }
@@ -673,17 +637,14 @@ int launch_conv_ns(boa_ctx* ctx, const ConvArgs& a_in, const ConvTile& t, double
     BOA_REQUIRE(desc != nullptr, "conv_ns: could not allocate the tile descriptor table");
     KernelTimer tm(ctx, BOA_K_CONV_MFMA, flops, bytes);
     ctx->counters[x3 ? BOA_CNT_CONV_X3 : BOA_CNT_CONV_WS]++;
+    BOA_REQUIRE(a.s0 == 2, "conv_ns: instantiated for stride 2 only");
     if (x3) {
-        BOA_REQUIRE(a.s0 == 2, "conv_ns: the split-precision instantiations are stride 2 only");
         if (ns_wn(a.Cout) == 2)
             launch_ns<2, 2, 2, true>(ctx, a, t, grid, desc, desc_row);
         else
             launch_ns<2, 4, 4, true>(ctx, a, t, grid, desc, desc_row);
-    } else if (ns_wn(a.Cout) == 2) {
-        BOA_REQUIRE(a.s0 == 2, "conv_ns: the two-chunk cout group is instantiated for stride 2 only");
+    } else if (ns_wn(a.Cout) == 2)
         launch_ns<2, 2, 2>(ctx, a, t, grid, desc, desc_row);
-    } else if (a.s0 == 1)
-        launch_ns<1, 4, 4>(ctx, a, t, grid, desc, desc_row);
     else
         launch_ns<2, 4, 4>(ctx, a, t, grid, desc, desc_row);
     tm.stop();

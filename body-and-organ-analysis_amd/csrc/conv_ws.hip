@@ -31,12 +31,6 @@
 #include <stdlib.h>
 
 #include "conv.h"
-
-
-#ifndef WS_PF2
-#define WS_PF2 0   // (experiment, measured slower) two producer register sets: halo loads issued a whole chunk interval ahead
-#endif
-
 #include "conv_ws_dev.h"
 
 // Builds the descriptor rows of a launch: thread b walks physical workgroup b's tile sequence with the kernels' own code.
@@ -66,9 +60,7 @@ __global__ __launch_bounds__(64) void k_ws_build_desc(ConvArgs p, int grid, int 
 // ---- consumer ----------------------------------------------------------------------------------------
 // One 16-channel chunk: acc[r] += W[tap] x X[tap][r] for all taps.  bp[r]: LDS address of this lane's voxel of
 // M-tile r in this lane's k-half plane; ap: LDS address of this lane's row of the first A fragment.
-#ifndef WS_PF
-#define WS_PF 1  // fragment prefetch distance in taps (2 measured slower: 610 vs 664 TFLOP/s on 32->32 @128^3, batch 8)
-#endif
+constexpr int WS_PF = 1;  // fragment prefetch distance in taps (2 measured slower: 610 vs 664 TFLOP/s on 32->32 @128^3, batch 8)
 
 // X3 (split-precision mode, conv_x3 notes below): the chunk holds 8 fp32 channels as [hi plane | lo plane] fp16, the B fragment of a
 // lane is the hi (k-half 0) or lo (k-half 1) part of its voxel's 8 channels, and a tap is TWO MFMAs: [Wh | Wh] x [Xh ; Xl] and
@@ -127,7 +119,7 @@ __device__ __forceinline__ void consume_chunk(const unsigned char* const (&bp)[R
 // 3 weight fragments once and feeds 3 R MFMAs -- (R + 5) KiB of LDS reads per 3 R MFMAs instead of 3 (R + 1) KiB.
 // The per-tap form asks the LDS for 160 B/clk per CU at the full MFMA rate with R = 4 (4 waves x 5 KiB per 4 MFMAs of
 // 32 clk), more than the 128 B/clk it has; this form needs 96 B/clk.
-template <int R, int K0, int K2, bool FIRST, bool X3>
+template <int R, int K0, int K2, bool FIRST>
 __device__ __forceinline__ void consume_chunk_y(const unsigned char* b0p, const unsigned char* ap, int xs, int h2,
                                                 f32x16 (&acc)[R], const f32x16& c0) {
     // MFMAs run in input-row order (row j feeds the pairs r + dy = j), so row j's registers are dead after its last
@@ -136,17 +128,12 @@ __device__ __forceinline__ void consume_chunk_y(const unsigned char* b0p, const 
     constexpr int G = K0 * K2;
     constexpr int NB = R + 2;
     f16x8 a[2][3];
-    f16x8 al[X3 ? 2 : 1][3];
     f16x8 b[NB];
-    constexpr int NA = X3 ? 6 : 3;   // weight fragment reads per (dx, dz) group
-    constexpr int MM = X3 ? 2 : 1;   // MFMAs per (row, dy) pair
+    constexpr int NA = 3;   // weight fragment reads per (dx, dz) group
     auto fetch_a = [&](int g, int slot) {
         const int dz = g % K2, dx = g / K2;
 #pragma unroll
-        for (int dy = 0; dy < 3; ++dy) {
-            a[slot][dy] = *(const f16x8*)(ap + ((dx * 3 + dy) * K2 + dz) * 1024);
-            if constexpr (X3) al[slot][dy] = *(const f16x8*)(ap + ((dx * 3 + dy) * K2 + dz) * 1024 + 512);
-        }
+        for (int dy = 0; dy < 3; ++dy) a[slot][dy] = *(const f16x8*)(ap + ((dx * 3 + dy) * K2 + dz) * 1024);
     };
     auto fetch_b = [&](int g, int jj) {
         const int dz = g % K2, dx = g / K2;
@@ -177,21 +164,13 @@ __device__ __forceinline__ void consume_chunk_y(const unsigned char* b0p, const 
                     acc[r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[cb][dy], b[jj], acc[r], 0, 0, 0);
                 }
             }
-            if constexpr (X3) {   // the lo weight parts of the same (row, dy) pairs
-#pragma unroll
-                for (int dy = 0; dy < 3; ++dy) {
-                    const int r = jj - dy;
-                    if (r < 0 || r >= R) continue;
-                    acc[r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[cb][dy], b[jj], acc[r], 0, 0, 0);
-                }
-            }
             // row jj is used by min(jj, R - 1) - max(jj - 2, 0) + 1 MFMAs (compile-time per unrolled iteration)
             if (jj == 0 || jj == NB - 1)
-                __builtin_amdgcn_sched_group_barrier(0x008, MM, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
             else if (jj == 1 || jj == NB - 2)
-                __builtin_amdgcn_sched_group_barrier(0x008, (R >= 2 ? 2 : 1) * MM, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, R >= 2 ? 2 : 1, 0);
             else
-                __builtin_amdgcn_sched_group_barrier(0x008, 3 * MM, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
             (void)cnt;
             if (g + 1 < G) {
                 fetch_b(g + 1, jj);
@@ -210,7 +189,8 @@ __device__ __forceinline__ void consume_chunk_y(const unsigned char* b0p, const 
 // chunk.  Per two groups: 12 row fragments + 6 weight fragments (18 KiB of LDS reads, 24 before) feed 9 R MFMAs (12 R before).
 // The odd last group pairs its dy = 0 / 1 taps the same way (the kh = 1 lanes read the NEXT input row: R fragment pairs
 // [Xh_r ; Xh_r+1], [Xl_r ; Xl_r+1]) and runs dy = 2 in the old form ([Wh | Wh], [Wl | Wl] x [Xh ; Xl], which also carries its Wl Xl):
-// 5 R MFMAs instead of 6 R.  Per chunk of 27 taps: 41 R MFMAs (54 R in the round-4 form; 40.5 R is the floor of a 3-term product).
+// 5 R MFMAs instead of 6 R.  Per chunk of 27 taps: 41 R MFMAs (54 R in the round-4 form of two MFMAs per tap; 40.5 R is the floor of a
+// 3-term product).
 template <int R, int K0, int K2>
 __device__ __forceinline__ void consume_chunk_y_x3(const unsigned char* b0p, const unsigned char* ap, int xs, int h2, int plane, int kh,
                                                    f32x16 (&acc)[R]) {
@@ -342,11 +322,7 @@ __device__ __forceinline__ void consume_chunk_y_x3(const unsigned char* b0p, con
 // shared; the producers normalise in fp32 and split into hi / lo fp16 LDS planes, the consumers issue two MFMAs per tap
 // (consume_chunk), the epilogue un-scales the accumulators and stores fp32.  Measured against an fp32 FMA chain the product of
 // split operands is the more accurate of the two (tools/x3_probe.hip: rms error 3.2e-7 vs 5.3e-7 of the output rms at K = 864).
-// FX (experiment, -DWS_FIXED_SHAPE): the halo strides of the dominant tile shape (w = 1 x 1 x 32, b = 2 x 8 x 1: xs = 340, h2 = 34) as
-// compile-time constants in the consumers' fragment addresses (immediate offsets instead of 18 v_add + ~20 SGPRs per chunk)
-#define WS_FX_XS 340
-#define WS_FX_H2 34
-template <int R, int K0, int K1, int K2, bool YR, bool X3, bool FX = false>
+template <int R, int K0, int K1, int K2, bool YR, bool X3>
 __global__ __launch_bounds__(WS_THREADS) void k_conv_ws(ConvArgs p, int total_tiles, int resident_w, int dbg_arg, const int* __restrict__ desc,
                                                         int desc_row) {
     // (round 5, measured and not kept: hipcc re-loads kernel arguments from the kernarg segment in the per-tile paths instead of keeping
@@ -418,11 +394,11 @@ __global__ __launch_bounds__(WS_THREADS) void k_conv_ws(ConvArgs p, int total_ti
         for (int j = 0; j < WS_MAXV; ++j) items.gi[j] = 0;
         items.ok = 0;
         // One register set: the loads of chunk g + 2 are issued behind the commit of chunk g + 1 and have the rest of the interval
-        // and the barrier to land.  WS_PF2 (round 5, measured and not adopted) issues them at the HEAD of the interval into a second
-        // set, a whole interval ahead (interval loop unrolled by two so that the sets alternate without copies): the 128^3 layers,
-        // whose halos are HBM-cold, did not move (+0.2 / -1.5 %), the streamed-weight layers lost 4 .. 9 % (their end-of-commit
-        // vmcnt(0) for the weight DMA then also waits for the twelve fresh halo loads): +3.1 % per forward.
-        ChunkRegs rgA, rgB;
+        // and the barrier to land.  A second set (round 5, measured and not adopted) issued them at the HEAD of the interval, a whole
+        // interval ahead (interval loop unrolled by two so that the sets alternate without copies): the 128^3 layers, whose halos
+        // are HBM-cold, did not move (+0.2 / -1.5 %), the streamed-weight layers lost 4 .. 9 % (their end-of-commit vmcnt(0) for the
+        // weight DMA then also waits for the twelve fresh halo loads): +3.1 % per forward.
+        ChunkRegs rgA;
         auto clear_regs = [&](ChunkRegs& rg) {
 #pragma unroll
             for (int j = 0; j < WS_MAXV; ++j) rg.d[j] = make_uint4(0, 0, 0, 0);
@@ -434,7 +410,6 @@ __global__ __launch_bounds__(WS_THREADS) void k_conv_ws(ConvArgs p, int total_ti
             rg.cc = rg.cy = 0;
         };
         clear_regs(rgA);
-        clear_regs(rgB);
         // halo reuse across the cout chunks of one spatial tile (cy-fast order, 2 chunks = both stay resident)
         bool reuse = false;
         const bool want_w = !(resident_w || (dbg & 16));
@@ -486,21 +461,6 @@ __global__ __launch_bounds__(WS_THREADS) void k_conv_ws(ConvArgs p, int total_ti
             prod_setup_desc(p, pd, pc, items);
             issue_next(rgA, 1 < my_chunks);
         }
-#if WS_PF2
-        auto interval = [&](int g, ChunkRegs& cur, ChunkRegs& nxt) {
-            if (live && g + 1 < my_chunks) {
-                WS_STAMP(1);
-                if (g + 2 < my_chunks) issue_next(nxt, g + 3 < my_chunks);
-                WS_STAMP(3);
-                commit(cur, bufs + ((g + 1) & 1) * buf_bytes);
-            }
-            __syncthreads();
-        };
-        for (int g = -1; g < my_chunks; g += 2) {
-            interval(g, rgA, rgB);
-            if (g + 1 < my_chunks) interval(g + 1, rgB, rgA);
-        }
-#else
         for (int g = -1; g < my_chunks; ++g) {
             if (live && g + 1 < my_chunks) {
                 WS_STAMP(1);
@@ -510,7 +470,6 @@ __global__ __launch_bounds__(WS_THREADS) void k_conv_ws(ConvArgs p, int total_ti
             }
             __syncthreads();
         }
-#endif
         return;
     }
 
@@ -616,7 +575,7 @@ __global__ __launch_bounds__(WS_THREADS) void k_conv_ws(ConvArgs p, int total_ti
     }
     __syncthreads();  // chunk 0 staged (pairs with the producers' g = -1 barrier)
     // The epilogue of a tile (bias, statistics, transpose, stores: registers and global memory only, no LDS) is DEFERRED past
-    // the chunk barrier into the next tile's first interval (WS_DEFER_EPILOGUE): that interval is the producers' long one (they
+    // the chunk barrier into the next tile's first interval: that interval is the producers' long one (they
     // issue the HBM-cold loads of the tile after next), the interval of a tile's last chunk their short one, so the roles'
     // long and short intervals now coincide instead of alternating in opposite phase.
     f32x16 acc[R];
@@ -726,11 +685,7 @@ __global__ __launch_bounds__(WS_THREADS) void k_conv_ws(ConvArgs p, int total_ti
                     for (int gq = 0; gq < 4; ++gq) {
                         unsigned ol = ((unsigned)srel0 * 32u + (unsigned)kh * 16u) + (unsigned)gq * ((unsigned)out_vox * 32u);
                         asm volatile("" : "+v"(ol));
-#ifndef WS_TEMPORAL_STORES
                         __builtin_nontemporal_store(f32x4_t{v[gq * 4 + 0], v[gq * 4 + 1], v[gq * 4 + 2], v[gq * 4 + 3]}, (WS_GLOBAL f32x4_t*)(dst + ol));
-#else
-                        *(WS_GLOBAL f32x4_t*)(dst + ol) = f32x4_t{v[gq * 4 + 0], v[gq * 4 + 1], v[gq * 4 + 2], v[gq * 4 + 3]};
-#endif
                     }
                 }
                 continue;
@@ -762,21 +717,11 @@ __global__ __launch_bounds__(WS_THREADS) void k_conv_ws(ConvArgs p, int total_ti
                 WS_GLOBAL unsigned char* dst = sgpr_ptr(tile_dst + (unsigned)mrel * 32u);
                 unsigned ol = olane;
                 asm volatile("" : "+v"(ol));  // keep the 32 -> 64 bit extension in this block (instruction selection is per block)
-#ifndef WS_TEMPORAL_STORES
                 // non-temporal stores: the layer's output is not read again before the launch ends, so it need not displace halo lines from
                 // the XCD's L2 (A/B on one box with tools/build_alt.sh, layers repeated at the power cap: 1 780 -> 1 767, 957 -> 946,
                 // 823 -> 817 us; bench step 1 820 -> 1 806 ms; the HBM-bound first conv measured 0 ... -10 % with them and keeps plain stores)
                 __builtin_nontemporal_store(u32x4_t{w[0], w[1], w[2], w[3]}, (WS_GLOBAL u32x4_t*)(dst + ol));
-#if defined(WS_ABL_STORE_HALF)        // ablation: half the bytes, half the store instructions
-#elif defined(WS_ABL_STORE_SAME)      // ablation: both instructions, the same bytes (half the HBM bytes, all the requests)
-                __builtin_nontemporal_store(u32x4_t{w[4], w[5], w[6], w[7]}, (WS_GLOBAL u32x4_t*)(dst + ol));
-#else
                 __builtin_nontemporal_store(u32x4_t{w[4], w[5], w[6], w[7]}, (WS_GLOBAL u32x4_t*)(dst + ol + 16));
-#endif
-#else
-                *(WS_GLOBAL u32x4_t*)(dst + ol) = u32x4_t{w[0], w[1], w[2], w[3]};
-                *(WS_GLOBAL u32x4_t*)(dst + ol + 16) = u32x4_t{w[4], w[5], w[6], w[7]};
-#endif
             }
         }
 #ifdef WS_TRACE_EPILOGUE
@@ -791,7 +736,7 @@ __global__ __launch_bounds__(WS_THREADS) void k_conv_ws(ConvArgs p, int total_ti
     done_tc.n = done_tc.cy = done_tc.ox0 = done_tc.oy0 = done_tc.oz0 = done_tc.sp = 0;
     // (one extra iteration for the last tile's deferred epilogue: a single call site -- two inlined copies of the epilogue
     //  made hipcc's backend fail with "illegal VGPR to SGPR copy")
-    for (int k = 0; k < my_tiles + WS_DEFER_EPILOGUE; ++k) {
+    for (int k = 0; k < my_tiles + 1; ++k) {
         bool new_run = true;
         const bool more = k < my_tiles;
 #ifdef WS_TRACE_EPILOGUE
@@ -804,7 +749,6 @@ __global__ __launch_bounds__(WS_THREADS) void k_conv_ws(ConvArgs p, int total_ti
 #ifdef WS_TRACE_EPILOGUE
         WS_STAMP(14);
 #endif
-#if WS_DEFER_EPILOGUE
         if (!(dbg & 8)) epilogue(done_tc, done_fl, done_vo, k > 0);  // the previous tile's (its statistics belong to the previous run: before the flush)
         // The accumulators are dead from here (the tile's first MFMA / bias load overwrites them), which hipcc cannot see through the
         // chunk loop's `cc == 0` test: an empty asm "defines" them -- on EVERY path, so that no path has to carry the old values
@@ -813,7 +757,6 @@ __global__ __launch_bounds__(WS_THREADS) void k_conv_ws(ConvArgs p, int total_ti
 #pragma unroll
         for (int r = 0; r < R; ++r) asm volatile("" : "=v"(acc[r]));
         if (!more) break;
-#endif
         if (new_run) {  // the partial sums of a virtual workgroup go to its own slot
             flush_stats();
             st_n = -1;
@@ -863,32 +806,20 @@ __global__ __launch_bounds__(WS_THREADS) void k_conv_ws(ConvArgs p, int total_ti
                         }
                     }
                 }
-                if constexpr (YR) {
-#ifdef WS_X3_UNPAIRED   // (A/B: the round-4 form, 4 MFMAs per two taps)
-                    consume_chunk_y<R, K0, K2, false, X3>(bp[0], ap, p.xs, p.h2, acc, biasv);
-#else
+                if constexpr (YR)
                     consume_chunk_y_x3<R, K0, K2>(bp[0], ap, p.xs, p.h2, plane, kh, acc);
-#endif
-                } else
-                    consume_chunk<R, K0, K1, K2, false, X3>(bp, ap, p.xs, p.h2, acc, biasv);
-            } else if constexpr (YR && FX) {
-                if (cc == 0)
-                    consume_chunk_y<R, K0, K2, true, X3>(bp[0], ap, WS_FX_XS, WS_FX_H2, acc, biasv);
                 else
-                    consume_chunk_y<R, K0, K2, false, X3>(bp[0], ap, WS_FX_XS, WS_FX_H2, acc, biasv);
+                    consume_chunk<R, K0, K1, K2, false, X3>(bp, ap, p.xs, p.h2, acc, biasv);
             } else if constexpr (YR) {
                 if (cc == 0)
-                    consume_chunk_y<R, K0, K2, true, X3>(bp[0], ap, p.xs, p.h2, acc, biasv);
+                    consume_chunk_y<R, K0, K2, true>(bp[0], ap, p.xs, p.h2, acc, biasv);
                 else
-                    consume_chunk_y<R, K0, K2, false, X3>(bp[0], ap, p.xs, p.h2, acc, biasv);
+                    consume_chunk_y<R, K0, K2, false>(bp[0], ap, p.xs, p.h2, acc, biasv);
             } else if (cc == 0)
                 consume_chunk<R, K0, K1, K2, true, X3>(bp, ap, p.xs, p.h2, acc, biasv);
             else
                 consume_chunk<R, K0, K1, K2, false, X3>(bp, ap, p.xs, p.h2, acc, biasv);
             WS_STAMP(5);
-#if !WS_DEFER_EPILOGUE
-            if (cc == ncc - 1 && !(dbg & 8)) epilogue(tc, cd.flags, cd.vo, true);
-#endif
             WS_STAMP(6);
             __syncthreads();
         }
@@ -922,13 +853,10 @@ size_t conv_ws_lds_bytes(int HV, int taps, int ncc, int Cout) {
     return 2 * (2 * ws_plane_host(HV) + (size_t)taps * 1024);
 }
 
-// virtual workgroups per sample (a function of the layer geometry only; BOA_WS_VW: experiment hook, changes the statistics
-// grouping) and the statistics slots of a layer: one per (virtual workgroup, consumer wave) -- sized per layer, so that
-// k_norm_finalize reads and re-zeroes 4 vw entries per (n, cout), not 4 x CUs (the deep layers have 10-64 tiles per sample)
-int conv_ws_vw(int tiles_per_sample, int cu_count) {
-    static const int vw_cap = getenv("BOA_WS_VW") ? atoi(getenv("BOA_WS_VW")) : 0;
-    return std::min(tiles_per_sample, vw_cap > 0 ? std::min(vw_cap, cu_count) : cu_count);
-}
+// virtual workgroups per sample (a function of the layer geometry only) and the statistics slots of a layer: one per (virtual
+// workgroup, consumer wave) -- sized per layer, so that k_norm_finalize reads and re-zeroes 4 vw entries per (n, cout), not 4 x CUs
+// (the deep layers have 10-64 tiles per sample)
+int conv_ws_vw(int tiles_per_sample, int cu_count) { return std::min(tiles_per_sample, cu_count); }
 int conv_ws_nslots(int tiles_per_sample, int cu_count) { return conv_ws_vw(tiles_per_sample, cu_count) * 4; }
 
 bool conv_ws_supported(const int k[3], int HV) {
@@ -939,17 +867,6 @@ bool conv_ws_supported(const int k[3], int HV) {
 
 template <int R, int K0, int K1, int K2, bool YR, bool X3>
 static void launch_ws_y(boa_ctx* ctx, const ConvArgs& a, const ConvTile& t, int total, int grid, int resident, const int* desc, int desc_row) {
-#ifdef WS_FIXED_SHAPE
-    if constexpr (YR && R == 4 && !X3) {
-        if (a.xs == WS_FX_XS && a.h2 == WS_FX_H2) {
-            static bool once_fx = (hipFuncSetAttribute((const void*)k_conv_ws<R, K0, K1, K2, YR, X3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), true);
-            (void)once_fx;
-            hipLaunchKernelGGL((k_conv_ws<R, K0, K1, K2, YR, X3, true>), dim3(grid), dim3(WS_THREADS), t.lds_bytes + 2048, ctx->stream, a, total, resident,
-                               getenv("BOA_WS_DBG") ? atoi(getenv("BOA_WS_DBG")) : 0, desc, desc_row);
-            return;
-        }
-    }
-#endif
     static bool once = (hipFuncSetAttribute((const void*)k_conv_ws<R, K0, K1, K2, YR, X3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), true);
     (void)once;
     hipLaunchKernelGGL((k_conv_ws<R, K0, K1, K2, YR, X3>), dim3(grid), dim3(WS_THREADS), t.lds_bytes + 2048, ctx->stream, a, total, resident,
@@ -957,8 +874,7 @@ static void launch_ws_y(boa_ctx* ctx, const ConvArgs& a, const ConvTile& t, int 
 }
 
 bool conv_ws_row_reuse(int R, int k1, int s1, int w1, int b1, int b2) {
-    static const bool off = getenv("BOA_WS_NO_YREUSE") != nullptr;
-    return R > 1 && k1 == 3 && s1 == 1 && w1 == 1 && b2 == 1 && b1 % R == 0 && !off;
+    return R > 1 && k1 == 3 && s1 == 1 && w1 == 1 && b2 == 1 && b1 % R == 0;
 }
 
 template <int R, int K0, int K1, int K2, bool X3>
@@ -1103,7 +1019,7 @@ int launch_conv_ws(boa_ctx* ctx, const ConvArgs& a_in, const ConvTile& t, double
     a.vstep_n = grid / vw;
     a.vstep_j = grid % vw;
     a.ncy = a.Cout / 32;
-    a.cy_fast = ((a.C0 + a.C1) == 32 && a.Cout == 64 && t.R == 1 && !getenv("BOA_WS_NO_CYFAST")) ? 1 : 0;
+    a.cy_fast = ((a.C0 + a.C1) == 32 && a.Cout == 64 && t.R == 1) ? 1 : 0;
     a.runs = ws_run_table(ctx, a, total, vw);
     BOA_REQUIRE(a.runs != nullptr, "conv_ws: could not allocate the run table");
     const int* desc = nullptr;
@@ -1124,13 +1040,11 @@ int launch_conv_ws(boa_ctx* ctx, const ConvArgs& a_in, const ConvTile& t, double
     int rc;
     switch (t.R + (x3 ? 8 : 0)) {
         case 4: rc = launch_ws_r<4, false>(ctx, a, t, total, grid, resident, desc, desc_row); break;
-#ifndef WS_BISECT
         case 2: rc = launch_ws_r<2, false>(ctx, a, t, total, grid, resident, desc, desc_row); break;
         case 1: rc = launch_ws_r<1, false>(ctx, a, t, total, grid, resident, desc, desc_row); break;
         case 12: rc = launch_ws_r<4, true>(ctx, a, t, total, grid, resident, desc, desc_row); break;
         case 10: rc = launch_ws_r<2, true>(ctx, a, t, total, grid, resident, desc, desc_row); break;
         case 9: rc = launch_ws_r<1, true>(ctx, a, t, total, grid, resident, desc, desc_row); break;
-#endif
         default:
             boa_set_error("conv_ws: unsupported R=%d", t.R);
             rc = BOA_EINVAL;

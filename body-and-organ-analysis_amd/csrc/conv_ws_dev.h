@@ -3,13 +3,8 @@
 // global access helpers.  See conv_ws.hip for the design notes.
 #pragma once
 #include "conv.h"
-#ifndef WS_THREADS
 #define WS_THREADS 512  // 256 consumer threads (4 waves) + WS_PROD producer threads
-#endif
 #define WS_PROD (WS_THREADS - 256)
-#ifndef WS_DEFER_EPILOGUE
-#define WS_DEFER_EPILOGUE 1
-#endif
 #define WS_WB ((27 * 64 + WS_PROD - 1) / WS_PROD)  // weight items per producer thread (taps * 64 items, <= 27 taps)
 #define WS_TRACE_SLOTS 4096
 // timeline stamps (debug only): slot = event counter of the calling wave; wave 0 (consumer) and wave 4 (producer) of block tr_blk

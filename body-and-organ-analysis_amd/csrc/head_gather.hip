@@ -18,9 +18,6 @@
 // pass divides by the number of folds and takes the argmax (predict_from_raw_data.py:483-500).
 #include "conv.h"
 
-#ifndef GH_WAVES
-#define GH_WAVES 6   // (4: 8.5 ms, 5: 7.5, 6: 7.2, 8: 7.2 per 512^3 part model -- latency-bound: occupancy pays more than the ~20 spilled registers cost)
-#endif
 typedef _Float16 gh2_t __attribute__((ext_vector_type(2)));
 
 struct GatherArgs {
@@ -594,19 +591,11 @@ __device__ __forceinline__ void gather_head_body(const GatherArgs& p) {
     if (any_inf) atomicOr(p.inf_flag, 1);
 }
 
+// prefetching fp16 head: 20 KB of LDS slots per block + the (scale, shift) table: four blocks per CU
+// (fold variants: 3 waves per EU (round 5, tools/gh_fold_time.py, five-fold 154 x 512 x 512) gave 157 VGPRs and no spills instead of
+//  128 with 2 - 4 spilled, but 18.4 vs 17.3 ms per five fold launches: the occupancy is worth more than the spills, 4 stays.)
 template <bool GAUSS, bool SSLDS, bool MULTI>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GH_WAVES, 8))) void k_gather_head(GatherArgs p) {
-    gather_head_body<GAUSS, SSLDS, MULTI, false>(p);
-}
-
-// prefetching variant of the fp16 head: 20 KB of LDS slots per block + the (scale, shift) table: four blocks per CU
-#ifndef GH_PF_MULTI_WAVES
-#define GH_PF_MULTI_WAVES 4   // experiment hook.  3 waves per EU (round 5, tools/gh_fold_time.py, five-fold 154 x 512 x 512): 157 VGPRs
-                              // and no spills for the fold variants instead of 128 with 2 - 4 spilled, but 18.4 vs 17.3 ms per
-                              // five fold launches: the occupancy is worth more than the spills, 4 stays.
-#endif
-template <bool GAUSS, bool SSLDS, bool MULTI>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MULTI ? GH_PF_MULTI_WAVES : 4, 8))) void k_gather_head_pf(GatherArgs p) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_gather_head_pf(GatherArgs p) {
     gather_head_body<GAUSS, SSLDS, MULTI, false, true>(p);
 }
 
@@ -659,11 +648,7 @@ int launch_gather_head(boa_ctx* ctx, const __half* act, const unsigned* ssp, con
                                         : (double)tiles_total * pvd * (x3 ? 130.0 : 66.0) + vvd * (fold_mode == 0 ? 1.0 : (fold_mode == 1 ? 2.0 * C : 4.0 * C));
     const size_t ss_bytes = (size_t)tiles_total * (x3 ? 256 : 128);
     a.ss_in_lds = ss_bytes <= 96 * 1024 ? 1 : 0;
-    static bool once = (hipFuncSetAttribute((const void*)k_gather_head<true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024),
-                        hipFuncSetAttribute((const void*)k_gather_head<false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024),
-                        hipFuncSetAttribute((const void*)k_gather_head<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024),
-                        hipFuncSetAttribute((const void*)k_gather_head<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024),
-                        hipFuncSetAttribute((const void*)k_gather_head_pf<true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024),
+    static bool once = (hipFuncSetAttribute((const void*)k_gather_head_pf<true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024),
                         hipFuncSetAttribute((const void*)k_gather_head_pf<false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024),
                         hipFuncSetAttribute((const void*)k_gather_head_pf<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024),
                         hipFuncSetAttribute((const void*)k_gather_head_pf<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024),
@@ -678,13 +663,10 @@ int launch_gather_head(boa_ctx* ctx, const __half* act, const unsigned* ssp, con
     do {                                                                                                 \
         if (x3)                                                                                          \
             hipLaunchKernelGGL((k_gather_head_x3<G, S, M>), dim3(grid), dim3(256), lds, ctx->stream, a); \
-        else if (pf)                                                                                     \
-            hipLaunchKernelGGL((k_gather_head_pf<G, S, M>), dim3(grid), dim3(256), lds, ctx->stream, a); \
         else                                                                                             \
-            hipLaunchKernelGGL((k_gather_head<G, S, M>), dim3(grid), dim3(256), lds, ctx->stream, a);    \
+            hipLaunchKernelGGL((k_gather_head_pf<G, S, M>), dim3(grid), dim3(256), lds, ctx->stream, a); \
     } while (0)
     const bool multi = fold_mode != 0;
-    static const bool pf = !(getenv("BOA_GH_PF") && atoi(getenv("BOA_GH_PF")) == 0);   // 0: the round-3 kernel without the LDS-DMA prefetch
     if (gauss && a.ss_in_lds) {
         if (multi) GH_LAUNCH(true, true, true); else GH_LAUNCH(true, true, false);
     } else if (gauss) {

@@ -107,7 +107,7 @@ __device__ __forceinline__ void store_bits32(unsigned char* p, unsigned int v) {
 }
 
 __global__ __launch_bounds__(256) void k_fill_holes_bits(const unsigned char* __restrict__ mask, int Y, int X, int W,
-                                                         unsigned char* __restrict__ out, int sweep) {
+                                                         unsigned char* __restrict__ out) {
     extern __shared__ unsigned int fsm[];
     unsigned int* bg = fsm;                 // [Y][W]
     unsigned int* rc = fsm + (size_t)Y * W; // [Y][W]
@@ -159,60 +159,15 @@ __global__ __launch_bounds__(256) void k_fill_holes_bits(const unsigned char* __
             }
         }
         __syncthreads();
-        // vertical SWEEPS: thread w owns word column w (32 pixel columns at once) and carries the reached set down the whole
-        // slice, then up -- a background column open to the border is flooded in one iteration however long it is.  (The first
-        // version advanced one row per iteration: a 512-row slice of maze-like labels needed hundreds of iterations of three
-        // barriers each, 0.7 ... 7.5 ms per mask depending on the labels; the sweep's loads do not depend on the carried word,
-        // so the 2 Y steps pipeline.)
-        if (!sweep) {
-            for (int idx = tid; idx < nw; idx += 256) {   // vertical step (each word has one writer; neighbours are only read)
-                const int y = idx / W;
-                const unsigned int r = rc[idx];
-                const unsigned int up = y > 0 ? rc[idx - W] : 0u, dn = y < Y - 1 ? rc[idx + W] : 0u;
-                const unsigned int nr = r | ((up | dn) & bg[idx]);
-                if (nr != r) { rc[idx] = nr; ch = 1; }
-            }
-        } else
-        for (int wc = tid; wc < W; wc += 256) {
-            // 32 rows at a time through registers: the LDS reads of a chunk are independent (issued back to back), only the
-            // register chain carries the dependency -- a row-by-row loop pays one LDS round trip per row
-            constexpr int CH = 32;
-            unsigned int carry = 0;
-            for (int y0 = 0; y0 < Y; y0 += CH) {
-                unsigned int rr[CH], bb[CH];
-#pragma unroll
-                for (int k = 0; k < CH; ++k) {
-                    const int y = min(y0 + k, Y - 1);
-                    rr[k] = rc[y * W + wc];
-                    bb[k] = bg[y * W + wc];
-                }
-#pragma unroll
-                for (int k = 0; k < CH; ++k) {
-                    if (y0 + k < Y) {
-                        const unsigned int nr = rr[k] | (carry & bb[k]);
-                        if (nr != rr[k]) { rc[(y0 + k) * W + wc] = nr; ch = 1; }
-                        carry = nr;
-                    }
-                }
-            }
-            carry = 0;
-            for (int y1 = Y; y1 > 0; y1 -= CH) {
-                unsigned int rr[CH], bb[CH];
-#pragma unroll
-                for (int k = 0; k < CH; ++k) {
-                    const int y = max(y1 - 1 - k, 0);
-                    rr[k] = rc[y * W + wc];
-                    bb[k] = bg[y * W + wc];
-                }
-#pragma unroll
-                for (int k = 0; k < CH; ++k) {
-                    if (y1 - 1 - k >= 0) {
-                        const unsigned int nr = rr[k] | (carry & bb[k]);
-                        if (nr != rr[k]) { rc[(y1 - 1 - k) * W + wc] = nr; ch = 1; }
-                        carry = nr;
-                    }
-                }
-            }
+        // vertical step: one row per iteration.  (Sweeps that carry the reached set down a whole word column and back up flood an
+        // open column in one iteration; measured on 154 x 512 x 512 masks, tools/fill_time.py: 7.1 / 2.4 / 0.6 ms on maze-like / noise
+        // / dense masks against 8.5 / 1.0 / 0.4 ms for the one-row step -- not a win on the labels the bench produces.)
+        for (int idx = tid; idx < nw; idx += 256) {   // each word has one writer; neighbours are only read
+            const int y = idx / W;
+            const unsigned int r = rc[idx];
+            const unsigned int up = y > 0 ? rc[idx - W] : 0u, dn = y < Y - 1 ? rc[idx + W] : 0u;
+            const unsigned int nr = r | ((up | dn) & bg[idx]);
+            if (nr != r) { rc[idx] = nr; ch = 1; }
         }
         if (ch) changed = 1;
         __syncthreads();
@@ -242,15 +197,11 @@ extern "C" int boa_fill_holes_2d(boa_ctx* c, const uint8_t* dev_mask, int Z, int
     BOA_REQUIRE(n < (1ull << 31), "boa_fill_holes_2d: volume too large for int32 indices");
     const int W = (X + 31) / 32;
     const size_t lds = (size_t)Y * W * 8;
-    static const bool bits_off = getenv("BOA_FILL_BITS") && atoi(getenv("BOA_FILL_BITS")) == 0;
-    if (!bits_off && lds <= 150 * 1024) {
+    if (lds <= 150 * 1024) {   // (larger slices: the byte fill below)
         static bool once = (hipFuncSetAttribute((const void*)k_fill_holes_bits, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256), true);
         (void)once;
         KernelTimer tb(c, BOA_K_MORPH, 0, (double)n * 2.0);
-        // (measured on 154 x 512 x 512 masks, tools/fill_time.py: sweeps 7.1 / 2.4 / 0.6 ms on maze-like / noise / dense masks against 8.5 / 1.0 / 0.4 ms
-        //  for the one-row step: not a win on the labels the bench produces -- kept as an experiment hook)
-        static const int sweep = getenv("BOA_FILL_SWEEP") ? atoi(getenv("BOA_FILL_SWEEP")) : 0;
-        hipLaunchKernelGGL(k_fill_holes_bits, dim3(Z), dim3(256), lds, c->stream, dev_mask, Y, X, W, dev_out, sweep);
+        hipLaunchKernelGGL(k_fill_holes_bits, dim3(Z), dim3(256), lds, c->stream, dev_mask, Y, X, W, dev_out);
         tb.stop();
         BOA_HIP_TRY(hipGetLastError());
         return BOA_OK;

@@ -53,11 +53,8 @@ struct UpLayer {
 // decides how the InstanceNorm partial sums are grouped, and results must not depend on how many tiles share a launch.
 // 16 = the product's default tile batch (with 8, the value of rounds 1-2, the 8^3 layers got half-size tiles -- 2 x 10 workgroups
 // per sample -- which at the batches actually run (16, 25) only doubled the weight streaming: 116 -> 82, 200 -> 134, 111 -> 73 us
-// per 25 tiles for the three 8^3 convs).  BOA_TILE_REF_N: experiment hook.
-static int tile_ref_batch() {
-    static const int v = getenv("BOA_TILE_REF_N") ? std::max(1, atoi(getenv("BOA_TILE_REF_N"))) : 16;
-    return v;
-}
+// per 25 tiles for the three 8^3 convs).
+constexpr int TILE_REF_BATCH = 16;
 
 struct boa_net {
     boa_ctx* ctx = nullptr;
@@ -110,8 +107,6 @@ static int net_alloc(boa_net* net, size_t bytes, void** out) {
 
 // an activation buffer: a slice of the context's shared arena (bound by net_bind_arena)
 static int net_alloc_act(boa_net* net, size_t bytes, void** out) {
-    static const bool own = getenv("BOA_NO_ACT_ARENA") != nullptr;   // experiment hook: private buffers as in rounds 1-3
-    if (own) return net_alloc(net, bytes, out);
     *out = nullptr;
     net->act_slots.push_back({out, net->act_need});
     net->act_need += (bytes + 255) & ~(size_t)255;
@@ -213,7 +208,7 @@ static int setup_conv(boa_net* net, ConvLayer& L, int N, const int din[3], int c
             BOA_REQUIRE((cin0 % 8) == 0 && (cin1 % 8) == 0 && (cout % 32) == 0,
                         "conv %d+%d -> %d: channel counts must be multiples of 8 (in) / 32 (out)", cin0, cin1, cout);
             ConvGeom gref = L.g;
-            gref.N = tile_ref_batch();
+            gref.N = TILE_REF_BATCH;
             BOA_REQUIRE(choose_conv_tile(gref, net->ctx->cu_count, &L.t, true), "no split-precision tile configuration fits conv %dx%dx%d k=%dx%dx%d",
                         din[0], din[1], din[2], k[0], k[1], k[2]);
             L.nblk = conv_nblk(L.t, net->ctx->cu_count, cout);
@@ -231,10 +226,10 @@ static int setup_conv(boa_net* net, ConvLayer& L, int N, const int din[3], int c
         BOA_REQUIRE((cin0 % 16) == 0 && (cin1 % 16) == 0 && (cout % 32) == 0,
                     "conv %d+%d -> %d: channel counts must be multiples of 16 (in) / 32 (out)", cin0, cin1, cout);
         // the tile shape fixes the fp32 summation order inside the conv and the grouping of the InstanceNorm partial sums:
-        // it is chosen for a nominal batch (tile_ref_batch), never for the actual max_batch, so that a tile's result does not
+        // it is chosen for a nominal batch (TILE_REF_BATCH), never for the actual max_batch, so that a tile's result does not
         // depend on the batch size the network was created with
         ConvGeom gref = L.g;
-        gref.N = tile_ref_batch();
+        gref.N = TILE_REF_BATCH;
         BOA_REQUIRE(choose_conv_tile(gref, net->ctx->cu_count, &L.t), "no tile configuration fits conv %dx%dx%d", din[0],
                     din[1], din[2]);
         L.nblk = conv_nblk(L.t, net->ctx->cu_count, cout);
@@ -1056,10 +1051,9 @@ static int net_forward_into_stash(boa_net* net, const float* dev_volume, const i
 
 extern "C" int boa_net_labels_supported(boa_net* net, const int* host_origins, int n_tiles) {
     if (!net || !host_origins) return 0;
-    static const bool off = getenv("BOA_NO_GATHER_HEAD") != nullptr;
     // (patch z extent a multiple of 32 and <= 31 classes: the shapes for which the scatter loop's head runs on the matrix cores too,
     //  so that the label path and the logits API share one head arithmetic)
-    if (off || net->precision == 1 || net->mirror_mask != 0 || net->d.features[0] != 32 || net->d.num_classes > 31 || net->d.patch[2] % 32 != 0) return 0;
+    if (net->precision == 1 || net->mirror_mask != 0 || net->d.features[0] != 32 || net->d.num_classes > 31 || net->d.patch[2] % 32 != 0) return 0;
     std::vector<int> steps[3];
     return grid_origins(host_origins, n_tiles, steps) ? 1 : 0;
 }
@@ -1180,8 +1174,7 @@ extern "C" int boa_net_predict_sliding_window_deferred(boa_net* net, const float
     // read-modify-write per covering tile.  The planes below x_split are exactly the deferred ones (checked) and all belong to the
     // block's first tile row: they stay untouched until boa_net_apply_deferred adds them, with the same kernel, on top of the
     // lower rank's sums.  Same head arithmetic for every tile (the matrix-core head), whatever the tile origins' alignment.
-    static const bool shard_scatter = getenv("BOA_SHARD_SCATTER") != nullptr;   // experiment hook: the round-3 scatter loop
-    if (!shard_scatter && !f32 && n_tiles > 0 && boa_net_labels_supported(net, host_origins, n_tiles)) {
+    if (!f32 && n_tiles > 0 && boa_net_labels_supported(net, host_origins, n_tiles)) {
         // dp0 = the deepest deferral (the block's first row); rows that start further up defer fewer planes -- actual steps below
         // half a patch make the block's second row reach the lower block's last row too.  Every deferred tile keeps dp0 planes (the
         // later rows more than they defer: valid planes of the tile, never visited by the launch over [x0, x_split)).
@@ -1411,7 +1404,7 @@ extern "C" int boa_conv_block_test(boa_ctx* ctx, const float* dev_in, int N, int
     g.Do = dout[0]; g.Ho = dout[1]; g.Wo = dout[2];
     ConvTile t;
     ConvGeom gref = g;
-    gref.N = tile_ref_batch();  // as the network does: the tile shape must not depend on the batch size
+    gref.N = TILE_REF_BATCH;  // as the network does: the tile shape must not depend on the batch size
     BOA_REQUIRE(choose_conv_tile(gref, ctx->cu_count, &t), "conv test: no tile configuration");
     size_t vin = (size_t)dims[0] * dims[1] * dims[2], vout = (size_t)dout[0] * dout[1] * dout[2];
     __half *in16 = nullptr, *out16 = nullptr, *wpk = nullptr;

@@ -1,8 +1,8 @@
 #!/bin/bash
 # Build a second copy of libboa_hip.so with extra compiler flags (kernel A/B experiments on ONE GPU box: run-to-run /
 # box-to-box spread is +-5 %, so variants are compared inside the same gpurun call):
-#   tools/build_alt.sh alt1 -DWS_DEFER_EPILOGUE=0      -> body-and-organ-analysis_amd/boa_hip/libboa_hip_alt1.so
-#   BOA_HIP_LIB=$PWD/body-and-organ-analysis_amd/boa_hip/libboa_hip_alt1.so python bench.py ...
+#   tools/build_alt.sh trace -DWS_WITH_TRACE      -> body-and-organ-analysis_amd/boa_hip/libboa_hip_trace.so
+#   BOA_HIP_LIB=$PWD/body-and-organ-analysis_amd/boa_hip/libboa_hip_trace.so BOA_WS_TRACE=0 python bench.py ...
 set -e
 NAME=$1; shift
 PKG=$(cd "$(dirname "$0")/../body-and-organ-analysis_amd" && pwd)
