@@ -432,16 +432,10 @@ __global__ __launch_bounds__(256) void k_conv_mfma(ConvArgs p) {
     }
 }
 
-int launch_conv_mfma(boa_ctx* ctx, const ActSrc& s0, const ActSrc& s1, const ConvGeom& g, const ConvTile& t,
-                     const __half* wpk, const float* bias, float slope, __half* out, float* partials) {
-    BOA_REQUIRE(s0.C % 16 == 0 && s1.C % 16 == 0 && s0.C > 0, "conv: input channels (%d,%d) must be multiples of 16",
-                s0.C, s1.C);
-    BOA_REQUIRE(g.Cout % 32 == 0, "conv: Cout=%d must be a multiple of 32", g.Cout);
+// the ConvArgs of a conv's geometry, tile, weights and output (the sources are the caller's: their channel units differ)
+static ConvArgs conv_args(const ConvGeom& g, const ConvTile& t, const __half* wpk, const float* bias, float slope, __half* out,
+                          float* partials) {
     ConvArgs a;
-    a.src0 = s0.data; a.src1 = s1.data; a.ss0 = s0.ss; a.ss1 = s1.ss; a.C0 = s0.C; a.C1 = s1.C;
-    a.ss16_0 = s0.ss16; a.ss16_1 = s1.ss16;
-    BOA_REQUIRE((s0.ss == nullptr) == (s0.ss16 == nullptr) && (s1.ss == nullptr) == (s1.ss16 == nullptr),
-                "conv: ss and ss16 must be given together");
     a.N = g.N; a.Di = g.Di; a.Hi = g.Hi; a.Wi = g.Wi; a.Do = g.Do; a.Ho = g.Ho; a.Wo = g.Wo; a.Cout = g.Cout;
     a.k0 = g.k[0]; a.k1 = g.k[1]; a.k2 = g.k[2]; a.s0 = g.s[0]; a.s1 = g.s[1]; a.s2 = g.s[2];
     a.p0 = (g.k[0] - 1) / 2; a.p1 = (g.k[1] - 1) / 2; a.p2 = (g.k[2] - 1) / 2;
@@ -451,6 +445,19 @@ int launch_conv_mfma(boa_ctx* ctx, const ActSrc& s0, const ActSrc& s1, const Con
     auto ilog2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
     a.lw1 = ilog2(t.w[1]); a.lw2 = ilog2(t.w[2]); a.lb1 = ilog2(t.b[1]); a.lb2 = ilog2(t.b[2]);
     a.wpk = wpk; a.bias = bias; a.out = out; a.partials = partials; a.slope = slope;
+    return a;
+}
+
+int launch_conv_mfma(boa_ctx* ctx, const ActSrc& s0, const ActSrc& s1, const ConvGeom& g, const ConvTile& t,
+                     const __half* wpk, const float* bias, float slope, __half* out, float* partials) {
+    BOA_REQUIRE(s0.C % 16 == 0 && s1.C % 16 == 0 && s0.C > 0, "conv: input channels (%d,%d) must be multiples of 16",
+                s0.C, s1.C);
+    BOA_REQUIRE(g.Cout % 32 == 0, "conv: Cout=%d must be a multiple of 32", g.Cout);
+    BOA_REQUIRE((s0.ss == nullptr) == (s0.ss16 == nullptr) && (s1.ss == nullptr) == (s1.ss16 == nullptr),
+                "conv: ss and ss16 must be given together");
+    ConvArgs a = conv_args(g, t, wpk, bias, slope, out, partials);
+    a.src0 = s0.data; a.src1 = s1.data; a.ss0 = s0.ss; a.ss1 = s1.ss; a.C0 = s0.C; a.C1 = s1.C;
+    a.ss16_0 = s0.ss16; a.ss16_1 = s1.ss16;
     dim3 grid(t.tiles[0] * t.tiles[1] * t.tiles[2], g.Cout / 32, g.N);
     const int taps = g.k[0] * g.k[1] * g.k[2];
     const double vox = (double)g.N * g.Do * g.Ho * g.Wo;
@@ -496,18 +503,9 @@ int launch_conv_x3(boa_ctx* ctx, const float* src0, const float* ss0, int C0, co
     BOA_REQUIRE(C0 % 8 == 0 && C1 % 8 == 0 && C0 > 0, "conv_x3: input channels (%d,%d) must be multiples of 8", C0, C1);
     BOA_REQUIRE(g.Cout % 32 == 0, "conv_x3: Cout=%d must be a multiple of 32", g.Cout);
     BOA_REQUIRE(t.variant == 1 || t.variant == 2, "conv_x3: tile variant %d", t.variant);
-    ConvArgs a;
+    ConvArgs a = conv_args(g, t, wpk, bias, slope, (__half*)out, partials);
     a.src0 = (const __half*)src0; a.src1 = (const __half*)src1; a.ss0 = ss0; a.ss1 = ss1; a.C0 = 2 * C0; a.C1 = 2 * C1;
     a.ss16_0 = (const unsigned*)ss0; a.ss16_1 = (const unsigned*)ss1;   // read as 16 fp32 words per 8-channel chunk
-    a.N = g.N; a.Di = g.Di; a.Hi = g.Hi; a.Wi = g.Wi; a.Do = g.Do; a.Ho = g.Ho; a.Wo = g.Wo; a.Cout = g.Cout;
-    a.k0 = g.k[0]; a.k1 = g.k[1]; a.k2 = g.k[2]; a.s0 = g.s[0]; a.s1 = g.s[1]; a.s2 = g.s[2];
-    a.p0 = (g.k[0] - 1) / 2; a.p1 = (g.k[1] - 1) / 2; a.p2 = (g.k[2] - 1) / 2;
-    a.w0 = t.w[0]; a.w1 = t.w[1]; a.w2 = t.w[2]; a.b0 = t.b[0]; a.b1 = t.b[1]; a.b2 = t.b[2];
-    a.h0 = t.h[0]; a.h1 = t.h[1]; a.h2 = t.h[2]; a.t0 = t.tiles[0]; a.t1 = t.tiles[1]; a.t2 = t.tiles[2];
-    a.xs = t.xs > 0 ? t.xs : t.h[1] * t.h[2];
-    auto ilog2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
-    a.lw1 = ilog2(t.w[1]); a.lw2 = ilog2(t.w[2]); a.lb1 = ilog2(t.b[1]); a.lb2 = ilog2(t.b[2]);
-    a.wpk = wpk; a.bias = bias; a.out = (__half*)out; a.partials = partials; a.slope = slope;
     a.wscale = wscale; a.winv = 1.0f / wscale;
     const int taps = g.k[0] * g.k[1] * g.k[2];
     const double vox = (double)g.N * g.Do * g.Ho * g.Wo;

@@ -15,6 +15,73 @@ struct DevBuf {
     size_t bytes = 0;
 };
 
+// The network's arithmetic; the values are boa_net_create's `precision`.  F16: fp16 storage + f16 MFMA (production); F32Ref: the
+// fp32 reference mode (net_f32.hip); Split: split precision (fp32 storage, hi / lo fp16 operands on the matrix cores: k_conv_ws<X3>,
+// net_x3.hip).  Only the functions that answer the mode's questions look at it: in_granule, act_layout, conv_weight_piece /
+// convt_weight_piece, head_kernel and the forward's launch steps (net_forward_stack, conv_step, convt_step and their kernel reports),
+// besides boa_net_create's choice of the first conv's input buffer.
+enum class NetMode : int { F16 = 0, F32Ref = 1, Split = 2 };
+
+// input channels per staged MFMA chunk of a conv and of a transposed conv: 16 fp16 channels, 8 split-precision channels; the
+// fp32_ref kernels take any count (0)
+int in_granule(NetMode m) { return m == NetMode::F16 ? 16 : m == NetMode::Split ? 8 : 0; }
+
+// Record format of a layer's activation buffer of C channels.  fp16 chunk planes [N][C/16][voxel][16] and split-precision octet
+// planes [N][C/8][voxel][8] (fp32) both hold 32-byte records in planes that span all voxels of a tile; fp32_ref holds channels-last
+// records [N][voxel][C] (fp32) of 4 C bytes in one plane.
+struct ActLayout {
+    int C;
+    int esz;       // bytes per channel value
+    bool planar;   // 32-byte records in C * esz / 32 planes, else channels-last
+    size_t rec() const { return planar ? 32 : (size_t)C * esz; }
+    size_t bytes(size_t vox) const { return vox * C * esz; }              // one tile of `vox` voxels
+    size_t tile(size_t i, size_t vox) const { return i * bytes(vox); }    // byte offset of tile i
+    // byte offset, inside every record plane, that skips a tile's first n axis-0 planes of `plane` voxels
+    size_t skip(int n, size_t plane) const { return (size_t)n * plane * rec(); }
+    // the plane stride (voxels) the scatter-form heads take; 0 = channels-last
+    size_t plane_stride(size_t vox) const { return planar ? vox : 0; }
+    // copies the first dp axis-0 planes of a tile (vox voxels, `plane` per axis-0 plane) to dst, in the same format with dp * plane
+    // voxels per record plane
+    hipError_t copy_head(unsigned char* dst, const void* tile, int dp, size_t plane, size_t vox, hipStream_t s) const {
+        const size_t n = (size_t)dp * plane * rec();
+        const int planes = planar ? C * esz / 32 : 1;
+        hipError_t e = hipSuccess;
+        for (int k = 0; k < planes && e == hipSuccess; ++k)
+            e = hipMemcpyAsync(dst + k * n, (const unsigned char*)tile + k * vox * rec(), n, hipMemcpyDeviceToDevice, s);
+        return e;
+    }
+    // fp32 NCDHW of one tile through the (scale, shift) table ss (nullptr: raw) and LeakyReLU
+    int to_nchw(boa_ctx* c, const void* tile, const float* ss, float slope, size_t vox, float* out) const {
+        if (!planar) return launch_ndhwc32_to_nchw_f32(c, (const float*)tile, ss, slope, C, vox, out);
+        if (esz == 4) return launch_octet_to_nchw_f32(c, (const float*)tile, ss, slope, C, vox, out);
+        return launch_ndhwc_to_nchw_f32(c, (const __half*)tile, ss, slope, 1, C, vox, out);
+    }
+};
+
+ActLayout act_layout(NetMode m, int C) { return {C, m == NetMode::F16 ? 2 : 4, m != NetMode::F32Ref}; }
+
+// The pieces of a weight set in blob order, each in the device form its kernel reads.
+enum class Piece {
+    FirstW,    // first conv of the fp16 / split-precision modes: fp32 [Cin][taps][Cout]
+    ConvW16,   // packed fp16 (pack_conv_weights)
+    ConvWX3,   // split precision: hi / lo fp16 parts of w * 2^e (pack_conv_weights_x3)
+    ConvW32,   // fp32_ref: fp32 [taps][Cin][Cout]
+    Bias, Gamma, Beta,
+    UpW16,     // transposed conv: packed fp16 (pack_convt_weights)
+    UpWX3,     // split precision (pack_convt_weights_x3)
+    UpW32,     // fp32_ref: fp32 [taps][Cin][Cout]
+    UpBias,
+    HeadW, HeadB,
+};
+
+Piece conv_weight_piece(NetMode m, bool first) {
+    if (m == NetMode::F32Ref) return Piece::ConvW32;
+    if (first) return Piece::FirstW;
+    return m == NetMode::Split ? Piece::ConvWX3 : Piece::ConvW16;
+}
+
+Piece convt_weight_piece(NetMode m) { return m == NetMode::F32Ref ? Piece::UpW32 : m == NetMode::Split ? Piece::UpWX3 : Piece::UpW16; }
+
 struct ConvLayer {
     ConvGeom g{};
     ConvTile t{};
@@ -23,10 +90,9 @@ struct ConvLayer {
     __half* wpk = nullptr;   // MFMA layers
     float* wfirst = nullptr; // first layer [Cin][taps][Cout]
     float* w32 = nullptr;    // fp32 mode: [taps][Cin][Cout]
-    float* out32 = nullptr;  // fp32 mode: raw conv output [N][vox][Cout]; split-precision mode: octet planes [N][Cout/8][vox][8]
     float wscale = 1.f;      // split-precision mode: power-of-two scale of the packed weights (per weight set)
     float *bias = nullptr, *gamma = nullptr, *beta = nullptr;
-    __half* out = nullptr;
+    void* act = nullptr;     // raw conv output in the mode's ActLayout
     float* partials = nullptr;
     float* ss = nullptr;
     unsigned* ss16 = nullptr;
@@ -41,10 +107,9 @@ struct UpLayer {
     __half* wpk = nullptr;
     float* w32 = nullptr;    // fp32 mode: [taps][Cin][Cout]
     float* bias = nullptr;
-    __half* out = nullptr;
-    float* out32 = nullptr;  // fp32 / split-precision mode
+    void* act = nullptr;     // output in the mode's ActLayout
     float wscale = 1.f;      // split-precision mode
-    float fold = 1.f;        // split-precision mode: power of two folded into the stored output (out32 = fold * convT output)
+    float fold = 1.f;        // split-precision mode: power of two folded into the stored output (act = fold * convT output)
 };
 
 }  // namespace
@@ -60,8 +125,7 @@ struct boa_net {
     boa_ctx* ctx = nullptr;
     boa_net_desc d{};
     int maxN = 1;
-    int precision = 0;         // 0: fp16 storage + f16 MFMA (production); 1: fp32 reference mode (net_f32.hip); 2: split-precision
-                               // mode (fp32 storage, hi / lo fp16 operands on the matrix cores: k_conv_ws<X3>, net_x3.hip)
+    NetMode mode = NetMode::F16;
     int mirror_mask = 0;       // test-time mirroring axes (bit a = array axis a), predict_from_raw_data.py:541-557
     float* mirror_tmp = nullptr;  // [maxN][C][P] fp32 logits of one mirror variant
     float* mirror_sum = nullptr;  // [maxN][C][P] running sum / mean
@@ -191,60 +255,40 @@ static int setup_conv(boa_net* net, ConvLayer& L, int N, const int din[3], int c
     L.g.Do = dout[0]; L.g.Ho = dout[1]; L.g.Wo = dout[2];
     const int taps = k[0] * k[1] * k[2];
     L.w_elems = (size_t)cout * (cin0 + cin1) * taps;
-    if (net->precision == 1) {
+    const int gran = in_granule(net->mode);
+    if (gran == 0) {   // fp32_ref: statistics from the stored output (launch_stats_f32), no partial sums
         BOA_REQUIRE(cout % 32 == 0, "conv %d+%d -> %d: Cout must be a multiple of 32", cin0, cin1, cout);
-        size_t vox32 = (size_t)dout[0] * dout[1] * dout[2];
-        BOA_TRY(net_alloc_act(net, (size_t)N * vox32 * cout * sizeof(float), (void**)&L.out32));
-        BOA_TRY(net_alloc(net, (size_t)N * cout * 2 * sizeof(float), (void**)&L.ss));
-        return BOA_OK;
-    }
-    if (net->precision == 2) {
-        size_t vox2 = (size_t)dout[0] * dout[1] * dout[2];
-        if (first) {
-            BOA_REQUIRE(s[0] == 1 && s[1] == 1 && s[2] == 1, "first conv must have stride 1");
-            BOA_REQUIRE(cout % 32 == 0 && cin0 >= 1 && cin0 <= 4, "first conv %d -> %d unsupported", cin0, cout);
-            L.nblk = conv_first_nblk(dout, net->ctx->cu_count);
-        } else {
-            BOA_REQUIRE((cin0 % 8) == 0 && (cin1 % 8) == 0 && (cout % 32) == 0,
-                        "conv %d+%d -> %d: channel counts must be multiples of 8 (in) / 32 (out)", cin0, cin1, cout);
-            ConvGeom gref = L.g;
-            gref.N = TILE_REF_BATCH;
-            BOA_REQUIRE(choose_conv_tile(gref, net->ctx->cu_count, &L.t, true), "no split-precision tile configuration fits conv %dx%dx%d k=%dx%dx%d",
-                        din[0], din[1], din[2], k[0], k[1], k[2]);
-            L.nblk = conv_nblk(L.t, net->ctx->cu_count, cout);
-        }
-        BOA_TRY(net_alloc_act(net, (size_t)N * vox2 * cout * sizeof(float), (void**)&L.out32));
-        BOA_TRY(net_alloc(net, (size_t)N * cout * 2 * L.nblk * sizeof(float), (void**)&L.partials));
-        BOA_HIP_TRY(hipMemsetAsync(L.partials, 0, (size_t)N * cout * 2 * L.nblk * sizeof(float), net->ctx->stream));
-        BOA_TRY(net_alloc(net, (size_t)N * cout * 2 * sizeof(float), (void**)&L.ss));
-        return BOA_OK;
-    }
-    if (first) {
+    } else if (first) {
         BOA_REQUIRE(s[0] == 1 && s[1] == 1 && s[2] == 1, "first conv must have stride 1");
+        // (what launch_conv_first takes; refused here already, so that the split-precision caller can fall back to fp32_ref)
+        BOA_REQUIRE(cout % 32 == 0 && cin0 >= 1 && cin0 <= 4, "first conv %d -> %d unsupported", cin0, cout);
         L.nblk = conv_first_nblk(dout, net->ctx->cu_count);
     } else {
-        BOA_REQUIRE((cin0 % 16) == 0 && (cin1 % 16) == 0 && (cout % 32) == 0,
-                    "conv %d+%d -> %d: channel counts must be multiples of 16 (in) / 32 (out)", cin0, cin1, cout);
+        BOA_REQUIRE((cin0 % gran) == 0 && (cin1 % gran) == 0 && (cout % 32) == 0,
+                    "conv %d+%d -> %d: channel counts must be multiples of %d (in) / 32 (out)", cin0, cin1, cout, gran);
         // the tile shape fixes the fp32 summation order inside the conv and the grouping of the InstanceNorm partial sums:
         // it is chosen for a nominal batch (TILE_REF_BATCH), never for the actual max_batch, so that a tile's result does not
         // depend on the batch size the network was created with
         ConvGeom gref = L.g;
         gref.N = TILE_REF_BATCH;
-        BOA_REQUIRE(choose_conv_tile(gref, net->ctx->cu_count, &L.t), "no tile configuration fits conv %dx%dx%d", din[0],
-                    din[1], din[2]);
+        BOA_REQUIRE(choose_conv_tile(gref, net->ctx->cu_count, &L.t, gran == 8), "no tile configuration fits conv %dx%dx%d k=%dx%dx%d",
+                    din[0], din[1], din[2], k[0], k[1], k[2]);
         L.nblk = conv_nblk(L.t, net->ctx->cu_count, cout);
     }
-    size_t vox = (size_t)dout[0] * dout[1] * dout[2];
-    BOA_TRY(net_alloc_act(net, (size_t)N * vox * cout * sizeof(__half), (void**)&L.out));
-    BOA_TRY(net_alloc(net, (size_t)N * cout * 2 * L.nblk * sizeof(float), (void**)&L.partials));
-    BOA_HIP_TRY(hipMemsetAsync(L.partials, 0, (size_t)N * cout * 2 * L.nblk * sizeof(float), net->ctx->stream));
+    const ActLayout lay = act_layout(net->mode, cout);
+    BOA_TRY(net_alloc_act(net, N * lay.bytes((size_t)dout[0] * dout[1] * dout[2]), &L.act));
+    if (gran) {
+        BOA_TRY(net_alloc(net, (size_t)N * cout * 2 * L.nblk * sizeof(float), (void**)&L.partials));
+        BOA_HIP_TRY(hipMemsetAsync(L.partials, 0, (size_t)N * cout * 2 * L.nblk * sizeof(float), net->ctx->stream));
+    }
     BOA_TRY(net_alloc(net, (size_t)N * cout * 2 * sizeof(float), (void**)&L.ss));
-    BOA_TRY(net_alloc(net, (size_t)N * cout * sizeof(unsigned), (void**)&L.ss16));
+    if (lay.esz == 2)   // fp16 consumers read the (scale, shift) table packed to fp16 as well
+        BOA_TRY(net_alloc(net, (size_t)N * cout * sizeof(unsigned), (void**)&L.ss16));
     return BOA_OK;
 }
 
 // Device layout of one weight set: every tensor of the blob, in blob order, at a 256-byte aligned offset of one arena.
-// `visit(piece kind, layer pointers..., byte size)` is called in blob order; used both to size / fill the arena and
+// `visit(piece, layer pointers..., byte size)` is called in blob order; used both to size / fill the arena and
 // to point the layers at it.
 static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
@@ -252,51 +296,47 @@ template <typename F>
 static void for_each_weight_piece(boa_net* net, F&& f) {
     auto conv = [&](ConvLayer& L) {
         const int cin = L.Cin0 + L.Cin1, cout = L.g.Cout;
-        if (net->precision == 1)
-            f(9, &L, nullptr, L.w_elems * sizeof(float));
-        else if (net->precision == 2 && !L.first)
-            f(11, &L, nullptr, conv_wpk_halves_x3(cin, cout, L.g.k) * sizeof(__half));
-        else
-        f(L.first ? 0 : 1, &L, nullptr, L.first ? L.w_elems * sizeof(float) : conv_wpk_halves(cin, cout, L.g.k) * sizeof(__half));
-        f(2, &L, nullptr, cout * sizeof(float));  // bias
-        f(3, &L, nullptr, cout * sizeof(float));  // gamma
-        f(4, &L, nullptr, cout * sizeof(float));  // beta
+        const Piece w = conv_weight_piece(net->mode, L.first);
+        f(w, &L, nullptr, w == Piece::ConvWX3   ? conv_wpk_halves_x3(cin, cout, L.g.k) * sizeof(__half)
+                          : w == Piece::ConvW16 ? conv_wpk_halves(cin, cout, L.g.k) * sizeof(__half)
+                                                : L.w_elems * sizeof(float));
+        f(Piece::Bias, &L, nullptr, cout * sizeof(float));
+        f(Piece::Gamma, &L, nullptr, cout * sizeof(float));
+        f(Piece::Beta, &L, nullptr, cout * sizeof(float));
     };
     for (auto& st : net->enc)
         for (auto& L : st) conv(L);
     for (size_t k = 0; k < net->up.size(); ++k) {
         UpLayer& U = net->up[k];
-        if (net->precision == 1)
-            f(10, nullptr, &U, (size_t)U.Cin * U.Cout * U.s[0] * U.s[1] * U.s[2] * sizeof(float));
-        else if (net->precision == 2)
-            f(12, nullptr, &U, convt_wpk_halves_x3(U.Cin, U.Cout, U.s) * sizeof(__half));
-        else
-            f(5, nullptr, &U, convt_wpk_halves(U.Cin, U.Cout, U.s) * sizeof(__half));
-        f(6, nullptr, &U, U.Cout * sizeof(float));
+        const Piece w = convt_weight_piece(net->mode);
+        f(w, nullptr, &U, w == Piece::UpWX3   ? convt_wpk_halves_x3(U.Cin, U.Cout, U.s) * sizeof(__half)
+                          : w == Piece::UpW16 ? convt_wpk_halves(U.Cin, U.Cout, U.s) * sizeof(__half)
+                                              : (size_t)U.Cin * U.Cout * U.s[0] * U.s[1] * U.s[2] * sizeof(float));
+        f(Piece::UpBias, nullptr, &U, U.Cout * sizeof(float));
         for (auto& L : net->dec[k]) conv(L);
     }
-    f(7, nullptr, nullptr, (size_t)net->d.num_classes * net->d.features[0] * sizeof(float));
-    f(8, nullptr, nullptr, net->d.num_classes * sizeof(float));
+    f(Piece::HeadW, nullptr, nullptr, (size_t)net->d.num_classes * net->d.features[0] * sizeof(float));
+    f(Piece::HeadB, nullptr, nullptr, net->d.num_classes * sizeof(float));
 }
 
 static void point_layers_at(boa_net* net, unsigned char* arena, const std::vector<float>& scales) {
     size_t off = 0, si = 0;
-    for_each_weight_piece(net, [&](int kind, ConvLayer* L, UpLayer* U, size_t bytes) {
+    for_each_weight_piece(net, [&](Piece piece, ConvLayer* L, UpLayer* U, size_t bytes) {
         void* p = arena + off;
-        switch (kind) {
-            case 11: L->wpk = (__half*)p; L->wscale = scales[si++]; break;
-            case 12: U->wpk = (__half*)p; U->wscale = scales[si++]; U->fold = scales[si++]; break;
-            case 0: L->wfirst = (float*)p; break;
-            case 1: L->wpk = (__half*)p; break;
-            case 2: L->bias = (float*)p; break;
-            case 3: L->gamma = (float*)p; break;
-            case 4: L->beta = (float*)p; break;
-            case 5: U->wpk = (__half*)p; break;
-            case 6: U->bias = (float*)p; break;
-            case 7: net->head_w = (float*)p; break;
-            case 9: L->w32 = (float*)p; break;
-            case 10: U->w32 = (float*)p; break;
-            default: net->head_b = (float*)p; break;
+        switch (piece) {
+            case Piece::FirstW: L->wfirst = (float*)p; break;
+            case Piece::ConvW16: L->wpk = (__half*)p; break;
+            case Piece::ConvWX3: L->wpk = (__half*)p; L->wscale = scales[si++]; break;
+            case Piece::ConvW32: L->w32 = (float*)p; break;
+            case Piece::Bias: L->bias = (float*)p; break;
+            case Piece::Gamma: L->gamma = (float*)p; break;
+            case Piece::Beta: L->beta = (float*)p; break;
+            case Piece::UpW16: U->wpk = (__half*)p; break;
+            case Piece::UpWX3: U->wpk = (__half*)p; U->wscale = scales[si++]; U->fold = scales[si++]; break;
+            case Piece::UpW32: U->w32 = (float*)p; break;
+            case Piece::UpBias: U->bias = (float*)p; break;
+            case Piece::HeadW: net->head_w = (float*)p; break;
+            case Piece::HeadB: net->head_b = (float*)p; break;
         }
         off += align256(bytes);
     });
@@ -324,7 +364,7 @@ extern "C" int boa_net_load_weights(boa_net* net, const float* w, size_t n_float
         }
     BOA_HIP_TRY(hipStreamSynchronize(c->stream));
     size_t total = 0;
-    for_each_weight_piece(net, [&](int, ConvLayer*, UpLayer*, size_t bytes) { total += align256(bytes); });
+    for_each_weight_piece(net, [&](Piece, ConvLayer*, UpLayer*, size_t bytes) { total += align256(bytes); });
     std::vector<unsigned char> stage(total, 0);
     std::vector<float> scales;
     const float* p = w;
@@ -336,10 +376,10 @@ extern "C" int boa_net_load_weights(boa_net* net, const float* w, size_t n_float
     // the decoder conv that consumes it -- exact in binary, no instruction on the hot path.  (g = 1 for the usual Kaiming weights.)
     float up_fold = 1.f;
     const ConvLayer* fold_target = nullptr;
-    for_each_weight_piece(net, [&](int kind, ConvLayer* L, UpLayer* U, size_t bytes) {
+    for_each_weight_piece(net, [&](Piece piece, ConvLayer* L, UpLayer* U, size_t bytes) {
         unsigned char* dst = stage.data() + off;
-        switch (kind) {
-            case 0: {  // first conv: [cout][cin][taps] -> [cin][taps][cout] fp32
+        switch (piece) {
+            case Piece::FirstW: {  // [cout][cin][taps] -> [cin][taps][cout] fp32
                 const int cin = L->Cin0 + L->Cin1, cout = L->g.Cout, taps = L->g.k[0] * L->g.k[1] * L->g.k[2];
                 float* wf = (float*)dst;
                 for (int co = 0; co < cout; ++co)
@@ -348,15 +388,15 @@ extern "C" int boa_net_load_weights(boa_net* net, const float* w, size_t n_float
                 p += L->w_elems;
                 break;
             }
-            case 1:
+            case Piece::ConvW16:
                 pack_conv_weights(p, L->Cin0 + L->Cin1, L->g.Cout, L->g.k, (__half*)dst);
                 p += L->w_elems;
                 break;
-            case 5:
+            case Piece::UpW16:
                 pack_convt_weights(p, U->Cin, U->Cout, U->s, (__half*)dst);
                 p += (size_t)U->Cin * U->Cout * U->s[0] * U->s[1] * U->s[2];
                 break;
-            case 11: {  // split-precision conv: hi / lo fp16 parts of w * 2^e
+            case Piece::ConvWX3: {
                 const float* wl = p;
                 std::vector<float> folded;
                 if (L == fold_target && up_fold != 1.f) {   // [Cout][Cin0 + Cin1][taps]: the first Cin0 inputs are the transposed conv's
@@ -372,7 +412,7 @@ extern "C" int boa_net_load_weights(boa_net* net, const float* w, size_t n_float
                 p += L->w_elems;
                 break;
             }
-            case 12: {
+            case Piece::UpWX3: {
                 const size_t ne = (size_t)U->Cin * U->Cout * U->s[0] * U->s[1] * U->s[2];
                 const float sc = x3_weight_scale(p, ne);
                 up_fold = x3_output_fold(p, ne, U->Cin, p + ne, U->Cout);   // (the bias follows the weights in the blob)
@@ -383,13 +423,13 @@ extern "C" int boa_net_load_weights(boa_net* net, const float* w, size_t n_float
                 p += ne;
                 break;
             }
-            case 6:   // transposed-conv bias (times the output fold in the split-precision mode)
+            case Piece::UpBias:   // (times the output fold of the split-precision mode)
                 memcpy(dst, p, bytes);
-                if (net->precision == 2 && up_fold != 1.f)
+                if (up_fold != 1.f)
                     for (int i = 0; i < U->Cout; ++i) ((float*)dst)[i] *= up_fold;
                 p += bytes / sizeof(float);
                 break;
-            case 9: {  // fp32 mode conv: [cout][cin][taps] -> [tap][cin][cout]
+            case Piece::ConvW32: {  // [cout][cin][taps] -> [tap][cin][cout]
                 const int cin = L->Cin0 + L->Cin1, cout = L->g.Cout, taps = L->g.k[0] * L->g.k[1] * L->g.k[2];
                 float* wf = (float*)dst;
                 for (int co = 0; co < cout; ++co)
@@ -398,7 +438,7 @@ extern "C" int boa_net_load_weights(boa_net* net, const float* w, size_t n_float
                 p += L->w_elems;
                 break;
             }
-            case 10: {  // fp32 mode convT: [cin][cout][taps] -> [tap][cin][cout]
+            case Piece::UpW32: {  // [cin][cout][taps] -> [tap][cin][cout]
                 const int taps = U->s[0] * U->s[1] * U->s[2];
                 float* wf = (float*)dst;
                 for (int ci = 0; ci < U->Cin; ++ci)
@@ -407,7 +447,11 @@ extern "C" int boa_net_load_weights(boa_net* net, const float* w, size_t n_float
                 p += (size_t)U->Cin * U->Cout * taps;
                 break;
             }
-            default:  // fp32 vectors / head matrix, copied as they are
+            case Piece::Bias:
+            case Piece::Gamma:
+            case Piece::Beta:
+            case Piece::HeadW:
+            case Piece::HeadB:  // fp32 vectors / head matrix, copied as they are
                 memcpy(dst, p, bytes);
                 p += bytes / sizeof(float);
                 break;
@@ -454,7 +498,7 @@ extern "C" int boa_net_create(boa_ctx* ctx, const boa_net_desc* desc, const floa
     if (net->d.norm_eps <= 0.f) net->d.norm_eps = 1e-5f;
     if (net->d.lrelu_slope == 0.f) net->d.lrelu_slope = 0.01f;
     net->maxN = max_batch;
-    net->precision = precision;
+    net->mode = (NetMode)precision;
     const boa_net_desc& d = net->d;
     int rc = BOA_OK;
     auto fail = [&](int r) {
@@ -498,14 +542,12 @@ extern "C" int boa_net_create(boa_ctx* ctx, const boa_net_desc* desc, const floa
                               dup[a], net->dims[sb - 1][a]);
                 return fail(BOA_EINVAL);
             }
-        if ((precision == 0 && U.Cin % 16) || (precision == 2 && U.Cin % 8) || U.Cout % 32) {
+        const int gran = in_granule(net->mode);
+        if ((gran && U.Cin % gran) || U.Cout % 32) {
             boa_set_error("transposed conv %d -> %d: unsupported channel counts", U.Cin, U.Cout);
             return fail(BOA_EINVAL);
         }
-        size_t vox = (size_t)dup[0] * dup[1] * dup[2];
-        if (precision >= 1) {
-            if ((rc = net_alloc_act(net, (size_t)max_batch * vox * U.Cout * sizeof(float), (void**)&U.out32))) return fail(rc);
-        } else if ((rc = net_alloc_act(net, (size_t)max_batch * vox * U.Cout * sizeof(__half), (void**)&U.out)))
+        if ((rc = net_alloc_act(net, max_batch * act_layout(net->mode, U.Cout).bytes((size_t)dup[0] * dup[1] * dup[2]), &U.act)))
             return fail(rc);
         net->dec[k].resize(d.n_conv_dec[k]);
         int one[3] = {1, 1, 1};
@@ -516,7 +558,7 @@ extern "C" int boa_net_create(boa_ctx* ctx, const boa_net_desc* desc, const floa
         }
     }
     if ((rc = net_alloc(net, (size_t)max_batch * 3 * sizeof(int), (void**)&net->dev_origins))) return fail(rc);
-    if (precision == 1) {
+    if (net->mode == NetMode::F32Ref) {   // input of the forward's first conv: tiles gathered before the walk (net_forward_stack)
         if ((rc = net_alloc_act(net, (size_t)max_batch * d.in_channels * d.patch[0] * d.patch[1] * d.patch[2] * sizeof(float),
                                 (void**)&net->tiles32)))
             return fail(rc);
@@ -536,263 +578,247 @@ extern "C" int boa_net_create(boa_ctx* ctx, const boa_net_desc* desc, const floa
     return BOA_OK;
 }
 
-// fp32 mode: the same layer sequence through net_f32.hip; leaves the last decoder activation in dec.back().back().out32
-static int net_forward_stack_f32(boa_net* net, const float* volume, const int V[3], const int vol_off[3],
-                                 const int* host_origins, int N, int flip_mask) {
-    boa_ctx* c = net->ctx;
-    const boa_net_desc& d = net->d;
-    BOA_REQUIRE(N >= 1 && N <= net->maxN, "forward: batch %d exceeds max_batch %d", N, net->maxN);
-    BOA_HIP_TRY(hipMemcpyAsync(net->dev_origins, host_origins, (size_t)N * 3 * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    c->prof_break = true;
-    BOA_TRY(launch_gather_tiles_f32(c, volume, V, vol_off, net->dev_origins, N, d.in_channels, d.patch, net->tiles32, flip_mask));
-    struct Src {
-        const float* data = nullptr;
-        const float* ss = nullptr;
-        int C = 0;
-    };
-    auto run_conv = [&](ConvLayer& L, const Src& a, const Src& b) -> int {
-        const int din[3] = {L.g.Di, L.g.Hi, L.g.Wi}, dout[3] = {L.g.Do, L.g.Ho, L.g.Wo};
-        BOA_TRY(launch_conv_f32(c, a.data, a.ss, a.C, b.data, b.ss, b.C, N, din, dout, L.g.k, L.g.s, L.g.Cout, L.w32, L.bias,
-                                d.lrelu_slope, L.out32));
-        return launch_stats_f32(c, L.out32, N, (size_t)dout[0] * dout[1] * dout[2], L.g.Cout, L.gamma, L.beta, d.norm_eps, L.ss);
-    };
-    Src cur, none;
-    cur.data = net->tiles32;
-    cur.C = d.in_channels;
-    for (int s = 0; s < d.n_stages; ++s)
-        for (size_t i = 0; i < net->enc[s].size(); ++i) {
-            ConvLayer& L = net->enc[s][i];
-            BOA_TRY(run_conv(L, cur, none));
-            cur.data = L.out32; cur.ss = L.ss; cur.C = L.g.Cout;
-        }
-    for (int k = 0; k < d.n_stages - 1; ++k) {
-        int sb = d.n_stages - 1 - k;
-        UpLayer& U = net->up[k];
-        BOA_TRY(launch_convt_f32(c, cur.data, cur.ss, U.Cin, N, U.din, U.s, U.Cout, U.w32, U.bias, d.lrelu_slope, U.out32));
-        ConvLayer& SK = net->enc[sb - 1].back();
-        Src upsrc, skip;
-        upsrc.data = U.out32; upsrc.C = U.Cout;
-        skip.data = SK.out32; skip.ss = SK.ss; skip.C = SK.g.Cout;
-        for (size_t i = 0; i < net->dec[k].size(); ++i) {
-            ConvLayer& L = net->dec[k][i];
-            if (i == 0)
-                BOA_TRY(run_conv(L, upsrc, skip));
-            else
-                BOA_TRY(run_conv(L, cur, none));
-            cur.data = L.out32; cur.ss = L.ss; cur.C = L.g.Cout;
-        }
-    }
-    return BOA_OK;
-}
+// ------------------------------------------------------------------------------------------------------
+// The forward: ONE walk over the U-Net -- encoder, then per decoder stage the transposed conv and the convs on its output and the
+// skip -- in which conv_step / convt_step launch every layer the way the network's mode does.
 
-// split-precision mode: first conv on the fp32 VALU (k_conv_first<F32OUT>), 3x3x3 convs on k_conv_ws<X3>, transposed convs on
-// k_convt_x3; InstanceNorm statistics from the conv epilogues (fp32 partial sums, fp64 finalize).  Leaves the last decoder
-// activation (octet planes) in dec.back().back().out32.
-static int net_forward_stack_x3(boa_net* net, const float* volume, const int V[3], const int vol_off[3], const int* host_origins,
-                                int N, int flip_mask) {
-    boa_ctx* c = net->ctx;
-    const boa_net_desc& d = net->d;
-    BOA_REQUIRE(N >= 1 && N <= net->maxN, "forward: batch %d exceeds max_batch %d", N, net->maxN);
-    BOA_HIP_TRY(hipMemcpyAsync(net->dev_origins, host_origins, (size_t)N * 3 * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    c->prof_break = true;
-    static const bool layer_prof = getenv("BOA_LAYER_PROF") != nullptr;
-    auto prof_begin = [&]() {
-        if (layer_prof) hipEventRecord(c->t0[7], c->stream);
-    };
-    auto prof_end = [&](const char* what, const int* din, int cin, int cout, const int* k, const int* s, double flops, const ConvTile* t) {
-        if (!layer_prof) return;
+// inputs of one forward of N tiles
+struct Fwd {
+    const float* volume;
+    const int* V;
+    const int* vol_off;
+    int N, flip_mask;
+};
+
+// BOA_LAYER_PROF: device time of every layer of the forward on stderr, one "[layer]" line each (tools/ab_layers.sh parses them);
+// BOA_LAYER_PROF_REPEAT=n [BOA_LAYER_PROF_MATCH=Di,Cin,Cout]: a conv's launch n more times, timed as one block (sustained clocks;
+// tools/power_sample.sh samples the socket power meanwhile)
+struct LayerProf {
+    boa_ctx* c;
+    int N;
+    const char* tag;   // after "[layer] ": "x3 " for split precision, "f32 " for fp32_ref
+    bool variant;      // fp16 lines name the tile variant
+    static bool on() {
+        static const bool v = getenv("BOA_LAYER_PROF") != nullptr;
+        return v;
+    }
+    void begin() const {
+        if (on()) hipEventRecord(c->t0[7], c->stream);
+    }
+    float elapsed_ms() const {
         hipEventRecord(c->t1[7], c->stream);
         hipEventSynchronize(c->t1[7]);
         float ms = 0.f;
         hipEventElapsedTime(&ms, c->t0[7], c->t1[7]);
-        fprintf(stderr, "[layer] x3 %-6s N=%d in=%dx%dx%d cin=%d cout=%d k=%d%d%d s=%d%d%d ", what, N, din[0], din[1], din[2], cin, cout, k[0], k[1],
-                k[2], s[0], s[1], s[2]);
+        return ms;
+    }
+    void end(const char* what, const int* din, int cin, int cout, const int* k, const int* s, double flops, const ConvTile* t) const {
+        if (!on()) return;
+        const float ms = elapsed_ms();
+        fprintf(stderr, "[layer] %s%-6s N=%d in=%dx%dx%d cin=%d cout=%d k=%d%d%d s=%d%d%d ", tag, what, N, din[0], din[1], din[2], cin, cout,
+                k[0], k[1], k[2], s[0], s[1], s[2]);
+        if (t && variant) fprintf(stderr, "var=%d ", t->variant);
         if (t)
             fprintf(stderr, "R=%d w=%d,%d,%d b=%d,%d,%d tiles=%d lds=%zu ", t->R, t->w[0], t->w[1], t->w[2], t->b[0], t->b[1], t->b[2],
                     t->tiles[0] * t->tiles[1] * t->tiles[2], t->lds_bytes);
         fprintf(stderr, "%.1f us %.1f TFLOP/s\n", ms * 1e3, flops / (ms * 1e-3) / 1e12);
-    };
-    struct Src {
-        const float* data = nullptr;
-        const float* ss = nullptr;
-        int C = 0;
-    };
-    auto run_conv = [&](ConvLayer& L, const Src& a, const Src& b) -> int {
-        ConvGeom g = L.g;
-        g.N = N;
-        prof_begin();
-        if (L.first) {
-            int nblk = 0;
-            BOA_TRY(launch_conv_first(c, volume, V, vol_off, net->dev_origins, N, d.in_channels, d.patch, L.g.k, L.g.Cout, L.wfirst, L.bias,
-                                      net->first_padded, nullptr, L.partials, &nblk, flip_mask, L.out32));
-        } else {
-            BOA_TRY(launch_conv_x3(c, a.data, a.ss, a.C, b.data, b.ss, b.C, g, L.t, L.wpk, L.wscale, L.bias, d.lrelu_slope, L.out32, L.partials));
-        }
-        {
-            const int din[3] = {g.Di, g.Hi, g.Wi};
-            const double fl = 2.0 * N * (double)g.Do * g.Ho * g.Wo * g.k[0] * g.k[1] * g.k[2] * (L.Cin0 + L.Cin1) * g.Cout;
-            prof_end(L.first ? "first" : "conv", din, L.Cin0 + L.Cin1, g.Cout, g.k, g.s, fl, L.first ? nullptr : &L.t);
-        }
-        return launch_norm_finalize(c, L.partials, L.nblk, N, g.Cout, (double)g.Do * g.Ho * g.Wo, L.gamma, L.beta, d.norm_eps, L.ss, nullptr, 1);
-    };
-    Src cur, none;
-    for (int s = 0; s < d.n_stages; ++s)
-        for (size_t i = 0; i < net->enc[s].size(); ++i) {
-            ConvLayer& L = net->enc[s][i];
-            BOA_TRY(run_conv(L, cur, none));
-            cur.data = L.out32; cur.ss = L.ss; cur.C = L.g.Cout;
-        }
-    for (int k = 0; k < d.n_stages - 1; ++k) {
-        int sb = d.n_stages - 1 - k;
-        UpLayer& U = net->up[k];
-        prof_begin();
-        BOA_TRY(launch_convt_x3(c, cur.data, cur.ss, U.Cin, N, U.din, U.s, U.Cout, U.wpk, U.wscale, U.bias, d.lrelu_slope, U.out32));
-        prof_end("convT", U.din, U.Cin, U.Cout, U.s, U.s, 2.0 * N * (double)U.din[0] * U.din[1] * U.din[2] * U.s[0] * U.s[1] * U.s[2] * U.Cin * U.Cout,
-                 nullptr);
-        ConvLayer& SK = net->enc[sb - 1].back();
-        Src upsrc, skip;
-        upsrc.data = U.out32; upsrc.C = U.Cout;
-        skip.data = SK.out32; skip.ss = SK.ss; skip.C = SK.g.Cout;
-        for (size_t i = 0; i < net->dec[k].size(); ++i) {
-            ConvLayer& L = net->dec[k][i];
-            if (i == 0)
-                BOA_TRY(run_conv(L, upsrc, skip));
-            else
-                BOA_TRY(run_conv(L, cur, none));
-            cur.data = L.out32; cur.ss = L.ss; cur.C = L.g.Cout;
-        }
     }
+    // after the timed launch of a conv: `launch` n more times as one timed block, then once more for end()
+    template <typename F>
+    int repeat(const ConvGeom& g, int cin, F&& launch) const {
+        static const int n = getenv("BOA_LAYER_PROF_REPEAT") ? atoi(getenv("BOA_LAYER_PROF_REPEAT")) : 0;
+        static int m_di = -1, m_ci = -1, m_co = -1;
+        static const bool has_match = getenv("BOA_LAYER_PROF_MATCH") && sscanf(getenv("BOA_LAYER_PROF_MATCH"), "%d,%d,%d", &m_di, &m_ci, &m_co) == 3;
+        if (!on() || n <= 0 || (has_match && (g.Di != m_di || cin != m_ci || g.Cout != m_co))) return BOA_OK;
+        begin();
+        for (int rep = 0; rep < n; ++rep) BOA_TRY(launch());
+        const float ms = elapsed_ms();
+        fprintf(stderr, "[repeat] in=%d cin=%d cout=%d: %d launches, %.1f us each, %.3f s\n", g.Di, cin, g.Cout, n, ms * 1e3 / n, ms * 1e-3);
+        begin();
+        return launch();
+    }
+};
+
+// One conv of the walk (a, b: its two sources), then the (scale, shift) table of its InstanceNorm.  fp16: k_conv_first / the MFMA
+// convs, statistics from the conv epilogues; split precision: the same with fp32 octet planes (k_conv_first<F32OUT>, k_conv_ws<X3>);
+// fp32_ref: net_f32.hip's conv and statistics kernels.
+static int conv_step(boa_net* net, const Fwd& f, const LayerProf& prof, ConvLayer& L, const ActSrc& a, const ActSrc& b) {
+    boa_ctx* c = net->ctx;
+    const boa_net_desc& d = net->d;
+    ConvGeom g = L.g;
+    g.N = f.N;
+    int nblk = 0;
+    auto launch = [&]() -> int {
+        switch (net->mode) {
+            case NetMode::F16:
+                if (L.first)
+                    return launch_conv_first(c, f.volume, f.V, f.vol_off, net->dev_origins, f.N, d.in_channels, d.patch, g.k, g.Cout, L.wfirst,
+                                             L.bias, net->first_padded, (__half*)L.act, L.partials, &nblk, f.flip_mask);
+                return launch_conv_mfma(c, a, b, g, L.t, L.wpk, L.bias, d.lrelu_slope, (__half*)L.act, L.partials);
+            case NetMode::Split:
+                if (L.first)
+                    return launch_conv_first(c, f.volume, f.V, f.vol_off, net->dev_origins, f.N, d.in_channels, d.patch, g.k, g.Cout, L.wfirst,
+                                             L.bias, net->first_padded, nullptr, L.partials, &nblk, f.flip_mask, (float*)L.act);
+                return launch_conv_x3(c, (const float*)a.data, a.ss, a.C, (const float*)b.data, b.ss, b.C, g, L.t, L.wpk, L.wscale, L.bias,
+                                      d.lrelu_slope, (float*)L.act, L.partials);
+            case NetMode::F32Ref: {
+                const int din[3] = {g.Di, g.Hi, g.Wi}, dout[3] = {g.Do, g.Ho, g.Wo};
+                return launch_conv_f32(c, (const float*)a.data, a.ss, a.C, (const float*)b.data, b.ss, b.C, f.N, din, dout, g.k, g.s, g.Cout,
+                                       L.w32, L.bias, d.lrelu_slope, (float*)L.act);
+            }
+        }
+        return BOA_EINVAL;
+    };
+    const int cin = L.Cin0 + L.Cin1, din[3] = {g.Di, g.Hi, g.Wi};
+    prof.begin();
+    BOA_TRY(launch());
+    if (!L.first) BOA_TRY(prof.repeat(g, cin, launch));
+    prof.end(L.first ? "first" : "conv", din, cin, g.Cout, g.k, g.s, 2.0 * f.N * (double)g.Do * g.Ho * g.Wo * g.k[0] * g.k[1] * g.k[2] * cin * g.Cout,
+             L.t.R ? &L.t : nullptr);   // (the first conv and fp32_ref have no MFMA tile)
+    const double vox = (double)g.Do * g.Ho * g.Wo;
+    if (net->mode == NetMode::F32Ref)
+        return launch_stats_f32(c, (const float*)L.act, f.N, (size_t)vox, g.Cout, L.gamma, L.beta, d.norm_eps, L.ss);
+    return launch_norm_finalize(c, L.partials, L.nblk, f.N, g.Cout, vox, L.gamma, L.beta, d.norm_eps, L.ss, L.ss16, 1);
+}
+
+// One transposed conv of the walk (src: the normalised output of the stage below).
+static int convt_step(boa_net* net, const Fwd& f, const LayerProf& prof, UpLayer& U, const ActSrc& src) {
+    boa_ctx* c = net->ctx;
+    const float slope = net->d.lrelu_slope;
+    prof.begin();
+    switch (net->mode) {
+        case NetMode::F16:
+            BOA_TRY(launch_convt_mfma(c, src, f.N, U.din, U.s, U.Cout, U.wpk, U.bias, slope, (__half*)U.act));
+            break;
+        case NetMode::Split:
+            BOA_TRY(launch_convt_x3(c, (const float*)src.data, src.ss, U.Cin, f.N, U.din, U.s, U.Cout, U.wpk, U.wscale, U.bias, slope,
+                                    (float*)U.act));
+            break;
+        case NetMode::F32Ref:
+            BOA_TRY(launch_convt_f32(c, (const float*)src.data, src.ss, U.Cin, f.N, U.din, U.s, U.Cout, U.w32, U.bias, slope, (float*)U.act));
+            break;
+    }
+    prof.end("convT", U.din, U.Cin, U.Cout, U.s, U.s, 2.0 * f.N * (double)U.din[0] * U.din[1] * U.din[2] * U.s[0] * U.s[1] * U.s[2] * U.Cin * U.Cout,
+             nullptr);
     return BOA_OK;
 }
 
-// split-precision mode: the MFMA head (k_head_x3, the gather head's arithmetic) for F0 = 32 and up to 32 classes, else the fp32 head
-static bool head_x3(const boa_net* net) { return net->precision == 2 && net->d.features[0] == 32 && net->d.num_classes <= 32; }
-
-// head of tile i of the current batch (either precision)
-static int net_head(boa_net* net, int i, const int P[3], int plane_skip, float* logits_out, const uint16_t* gauss, uint16_t* acc,
-                    uint16_t* nacc, const int PV[3], const int start[3]) {
-    const boa_net_desc& d = net->d;
-    ConvLayer& last = net->dec.back().back();
-    const size_t pv = (size_t)d.patch[0] * d.patch[1] * d.patch[2];
-    const float* ss = last.ss + (size_t)i * d.features[0] * 2;
-    if (net->precision == 1)   // fp32 mode: channels-last records
-        return launch_head_f32(net->ctx, last.out32 + (size_t)i * pv * d.features[0] + (size_t)plane_skip * d.patch[1] * d.patch[2] * d.features[0],
-                               ss, d.features[0], P, d.num_classes, net->head_w, net->head_b, d.lrelu_slope, logits_out, gauss, acc,
-                               nacc, PV, start);
-    if (net->precision == 2) {  // split-precision mode: fp32 octet planes; skipped axis-0 planes are an offset inside every plane
-        const float* a32 = last.out32 + (size_t)i * pv * d.features[0] + (size_t)plane_skip * d.patch[1] * d.patch[2] * 8;
-        if (head_x3(net))   // the gather head's arithmetic (label path == logits API, bit for bit)
-            return launch_head_x3(net->ctx, a32, ss, d.features[0], P, d.num_classes, net->head_w, net->head_b, d.lrelu_slope, logits_out, gauss, acc,
-                                  nacc, PV, start, pv);
-        return launch_head_f32(net->ctx, a32, ss, d.features[0], P, d.num_classes, net->head_w, net->head_b, d.lrelu_slope, logits_out, gauss, acc, nacc,
-                               PV, start, pv);
+// what conv_step / convt_step launch for a layer, as boa_net_debug_layer reports it: {BOA_LK_* kernel, R (MT of k_convt_x3), row reuse
+// of k_conv_ws (log2 of a split-precision transposed conv's output fold)}
+static void conv_kernel_info(const boa_net* net, const ConvLayer& L, int info[3]) {
+    if (net->mode == NetMode::F32Ref) {
+        info[0] = BOA_LK_CONV_F32;
+    } else if (L.first) {
+        info[0] = first_mfma_ok(net->d.in_channels, net->d.patch, L.g.k, L.g.Cout) ? BOA_LK_FIRST_MFMA : BOA_LK_FIRST_VALU;
+    } else {
+        const ConvTile& t = L.t;
+        info[0] = t.variant == 2 ? BOA_LK_CONV_NS : t.variant == 1 ? BOA_LK_CONV_WS : BOA_LK_CONV_MFMA;
+        info[1] = t.R;
+        info[2] = t.variant == 1 && conv_ws_row_reuse(t.R, L.g.k[1], L.g.s[1], t.w[1], t.b[1], t.b[2]) ? 1 : 0;
     }
-    // chunk-planar fp16: skipping leading axis-0 planes is an offset inside every 16-channel plane; plane stride = whole tile
-    return launch_head(net->ctx, last.out + (size_t)i * pv * d.features[0] + (size_t)plane_skip * d.patch[1] * d.patch[2] * 16, ss,
-                       d.features[0], P, d.num_classes, net->head_w, net->head_b, d.lrelu_slope, logits_out, gauss, acc, nacc, PV,
-                       start, pv);
+}
+
+static void convt_kernel_info(const boa_net* net, const UpLayer& U, int info[3]) {
+    switch (net->mode) {
+        case NetMode::F16: {
+            const int form = convt_mfma_form(U.Cin, U.s, true);   // (the source of a transposed conv is always a normalised conv output)
+            info[0] = form == 2 ? BOA_LK_CONVT_DEEP : form == 1 ? BOA_LK_CONVT_RW : BOA_LK_CONVT_MFMA;
+            break;
+        }
+        case NetMode::Split:
+            info[0] = BOA_LK_CONVT_X3;
+            info[1] = convt_x3_mt((size_t)U.din[0] * U.din[1] * U.din[2]);
+            info[2] = (int)std::lround(std::log2((double)U.fold));
+            break;
+        case NetMode::F32Ref:
+            info[0] = BOA_LK_CONVT_F32;
+            break;
+    }
 }
 
 // run the conv stack for N tiles; leaves the last decoder activation (+ its ss) in net->dec.back().back()
 static int net_forward_stack(boa_net* net, const float* volume, const int V[3], const int vol_off[3],
                              const int* host_origins, int N, int flip_mask = 0) {
-    if (net->precision == 1) return net_forward_stack_f32(net, volume, V, vol_off, host_origins, N, flip_mask);
-    if (net->precision == 2) return net_forward_stack_x3(net, volume, V, vol_off, host_origins, N, flip_mask);
     boa_ctx* c = net->ctx;
     const boa_net_desc& d = net->d;
     BOA_REQUIRE(N >= 1 && N <= net->maxN, "forward: batch %d exceeds max_batch %d", N, net->maxN);
     BOA_HIP_TRY(hipMemcpyAsync(net->dev_origins, host_origins, (size_t)N * 3 * sizeof(int), hipMemcpyHostToDevice,
                                c->stream));
-    static const bool layer_prof = getenv("BOA_LAYER_PROF") != nullptr;
-    auto prof_begin = [&]() {
-        if (layer_prof) hipEventRecord(c->t0[7], c->stream);
-    };
-    auto prof_end = [&](const char* what, const int* din, int cin, int cout, const int* k, const int* s, double flops,
-                        const ConvTile* t) {
-        if (!layer_prof) return;
-        hipEventRecord(c->t1[7], c->stream);
-        hipEventSynchronize(c->t1[7]);
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, c->t0[7], c->t1[7]);
-        fprintf(stderr, "[layer] %-6s N=%d in=%dx%dx%d cin=%d cout=%d k=%d%d%d s=%d%d%d ", what, N, din[0], din[1], din[2], cin,
-                cout, k[0], k[1], k[2], s[0], s[1], s[2]);
-        if (t)
-            fprintf(stderr, "var=%d R=%d w=%d,%d,%d b=%d,%d,%d tiles=%d lds=%zu ", t->variant, t->R, t->w[0], t->w[1], t->w[2],
-                    t->b[0], t->b[1], t->b[2], t->tiles[0] * t->tiles[1] * t->tiles[2], t->lds_bytes);
-        fprintf(stderr, "%.1f us %.1f TFLOP/s\n", ms * 1e3, flops / (ms * 1e-3) / 1e12);
-    };
-    auto run_conv = [&](ConvLayer& L, const ActSrc& a, const ActSrc& b) -> int {
-        ConvGeom g = L.g;
-        g.N = N;
-        prof_begin();
-        if (L.first) {
-            int nblk = 0;
-            BOA_TRY(launch_conv_first(c, volume, V, vol_off, net->dev_origins, N, d.in_channels, d.patch, L.g.k, L.g.Cout,
-                                      L.wfirst, L.bias, net->first_padded, L.out, L.partials, &nblk, flip_mask));
-        } else {
-            BOA_TRY(launch_conv_mfma(c, a, b, g, L.t, L.wpk, L.bias, d.lrelu_slope, L.out, L.partials));
-            // BOA_LAYER_PROF_REPEAT=n [BOA_LAYER_PROF_MATCH=Di,Cin,Cout]: the same launch n more times, timed as one block (sustained
-            // clocks; tools/power_sample.sh samples the socket power meanwhile)
-            static const int prof_repeat = getenv("BOA_LAYER_PROF_REPEAT") ? atoi(getenv("BOA_LAYER_PROF_REPEAT")) : 0;
-            static int m_di = -1, m_ci = -1, m_co = -1;
-            static const bool has_match = getenv("BOA_LAYER_PROF_MATCH") && sscanf(getenv("BOA_LAYER_PROF_MATCH"), "%d,%d,%d", &m_di, &m_ci, &m_co) == 3;
-            if (layer_prof && prof_repeat > 0 && (!has_match || (g.Di == m_di && L.Cin0 + L.Cin1 == m_ci && g.Cout == m_co))) {
-                prof_begin();
-                for (int rep = 0; rep < prof_repeat; ++rep)
-                    BOA_TRY(launch_conv_mfma(c, a, b, g, L.t, L.wpk, L.bias, d.lrelu_slope, L.out, L.partials));
-                hipEventRecord(c->t1[7], c->stream);
-                hipEventSynchronize(c->t1[7]);
-                float ms = 0.f;
-                hipEventElapsedTime(&ms, c->t0[7], c->t1[7]);
-                fprintf(stderr, "[repeat] in=%d cin=%d cout=%d: %d launches, %.1f us each, %.3f s\n", g.Di, L.Cin0 + L.Cin1, g.Cout, prof_repeat,
-                        ms * 1e3 / prof_repeat, ms * 1e-3);
-                prof_begin();
-                BOA_TRY(launch_conv_mfma(c, a, b, g, L.t, L.wpk, L.bias, d.lrelu_slope, L.out, L.partials));
-            }
-        }
-        {
-            const int din[3] = {g.Di, g.Hi, g.Wi};
-            const double fl = 2.0 * N * (double)g.Do * g.Ho * g.Wo * g.k[0] * g.k[1] * g.k[2] * (L.Cin0 + L.Cin1) * g.Cout;
-            prof_end(L.first ? "first" : "conv", din, L.Cin0 + L.Cin1, g.Cout, g.k, g.s, fl, L.first ? nullptr : &L.t);
-        }
-        double count = (double)g.Do * g.Ho * g.Wo;
-        BOA_TRY(launch_norm_finalize(c, L.partials, L.nblk, N, g.Cout, count, L.gamma, L.beta, d.norm_eps, L.ss, L.ss16, 1));
-        return BOA_OK;
+    // (the fp16 mode sets no profiling break after the upload, the others do: bench.py's per-class times depend on that)
+    if (net->mode != NetMode::F16) c->prof_break = true;
+    // fp32_ref's first conv reads the tiles gathered here, the other modes' first conv reads the volume itself
+    if (net->mode == NetMode::F32Ref)
+        BOA_TRY(launch_gather_tiles_f32(c, volume, V, vol_off, net->dev_origins, N, d.in_channels, d.patch, net->tiles32, flip_mask));
+    const Fwd f{volume, V, vol_off, N, flip_mask};
+    const LayerProf prof{c, N, net->mode == NetMode::Split ? "x3 " : net->mode == NetMode::F32Ref ? "f32 " : "", net->mode == NetMode::F16};
+    auto out_of = [](const ConvLayer& L) {
+        ActSrc s;
+        s.data = (const __half*)L.act;
+        s.ss = L.ss;
+        s.ss16 = L.ss16;
+        s.C = L.g.Cout;
+        return s;
     };
     ActSrc cur, none;
+    cur.data = (const __half*)net->tiles32;
+    cur.C = d.in_channels;
     for (int s = 0; s < d.n_stages; ++s)
-        for (size_t i = 0; i < net->enc[s].size(); ++i) {
-            ConvLayer& L = net->enc[s][i];
-            BOA_TRY(run_conv(L, cur, none));
-            cur.data = L.out;
-            cur.ss = L.ss;
-            cur.ss16 = L.ss16;
-            cur.C = L.g.Cout;
+        for (ConvLayer& L : net->enc[s]) {
+            BOA_TRY(conv_step(net, f, prof, L, cur, none));
+            cur = out_of(L);
         }
     for (int k = 0; k < d.n_stages - 1; ++k) {
-        int sb = d.n_stages - 1 - k;
         UpLayer& U = net->up[k];
-        prof_begin();
-        BOA_TRY(launch_convt_mfma(c, cur, N, U.din, U.s, U.Cout, U.wpk, U.bias, d.lrelu_slope, U.out));
-        prof_end("convT", U.din, U.Cin, U.Cout, U.s, U.s,
-                 2.0 * N * (double)U.din[0] * U.din[1] * U.din[2] * U.s[0] * U.s[1] * U.s[2] * U.Cin * U.Cout, nullptr);
-        ConvLayer& SK = net->enc[sb - 1].back();
-        ActSrc upsrc, skip;
-        upsrc.data = U.out; upsrc.ss = nullptr; upsrc.ss16 = nullptr; upsrc.C = U.Cout;
-        skip.data = SK.out; skip.ss = SK.ss; skip.ss16 = SK.ss16; skip.C = SK.g.Cout;
+        BOA_TRY(convt_step(net, f, prof, U, cur));
+        ActSrc up;
+        up.data = (const __half*)U.act;
+        up.C = U.Cout;
+        const ActSrc skip = out_of(net->enc[d.n_stages - 2 - k].back());
         for (size_t i = 0; i < net->dec[k].size(); ++i) {
             ConvLayer& L = net->dec[k][i];
-            if (i == 0)
-                BOA_TRY(run_conv(L, upsrc, skip));
-            else
-                BOA_TRY(run_conv(L, cur, none));
-            cur.data = L.out;
-            cur.ss = L.ss;
-            cur.ss16 = L.ss16;
-            cur.C = L.g.Cout;
+            BOA_TRY(i == 0 ? conv_step(net, f, prof, L, up, skip) : conv_step(net, f, prof, L, cur, none));
+            cur = out_of(L);
         }
     }
     return BOA_OK;
+}
+
+// The scatter-form head (one launch per tile) of a network, as its BOA_LK_* code: fp16 -> the MFMA head; split precision -> k_head_x3
+// (the gather head's arithmetic: label path == logits API, bit for bit) for F0 = 32 and up to 32 classes, else the fp32 head;
+// fp32_ref -> the fp32 head.
+static int head_kernel(const boa_net* net) {
+    const boa_net_desc& d = net->d;
+    if (net->mode == NetMode::F16) return BOA_LK_HEAD_MFMA;
+    return net->mode == NetMode::Split && d.features[0] == 32 && d.num_classes <= 32 ? BOA_LK_HEAD_X3 : BOA_LK_HEAD_F32;
+}
+
+// runs it on one tile: `act` at the first record it reads, `plane_stride` as ActLayout::plane_stride
+static int scatter_head(const boa_net* net, const void* act, const float* ss, const int P[3], size_t plane_stride, const float* w,
+                        const float* b, float* logits_out, const uint16_t* gauss, uint16_t* acc, uint16_t* nacc, const int PV[3],
+                        const int start[3]) {
+    const boa_net_desc& d = net->d;
+    switch (head_kernel(net)) {
+        case BOA_LK_HEAD_MFMA:
+            return launch_head(net->ctx, (const __half*)act, ss, d.features[0], P, d.num_classes, w, b, d.lrelu_slope, logits_out, gauss, acc,
+                               nacc, PV, start, plane_stride);
+        case BOA_LK_HEAD_X3:
+            return launch_head_x3(net->ctx, (const float*)act, ss, d.features[0], P, d.num_classes, w, b, d.lrelu_slope, logits_out, gauss,
+                                  acc, nacc, PV, start, plane_stride);
+        default:
+            return launch_head_f32(net->ctx, (const float*)act, ss, d.features[0], P, d.num_classes, w, b, d.lrelu_slope, logits_out, gauss,
+                                   acc, nacc, PV, start, plane_stride);
+    }
+}
+
+// head of tile i of the current batch without its first plane_skip axis-0 planes
+static int net_head(boa_net* net, int i, const int P[3], int plane_skip, float* logits_out, const uint16_t* gauss, uint16_t* acc,
+                    uint16_t* nacc, const int PV[3], const int start[3]) {
+    const boa_net_desc& d = net->d;
+    const ConvLayer& last = net->dec.back().back();
+    const ActLayout lay = act_layout(net->mode, d.features[0]);
+    const size_t plane = (size_t)d.patch[1] * d.patch[2], pv = d.patch[0] * plane;
+    return scatter_head(net, (const unsigned char*)last.act + lay.tile(i, pv) + lay.skip(plane_skip, plane), last.ss + (size_t)i * d.features[0] * 2,
+                        P, lay.plane_stride(pv), net->head_w, net->head_b, logits_out, gauss, acc, nacc, PV, start);
 }
 
 // `_internal_maybe_mirror_and_predict` (predict_from_raw_data.py:541-557) for the nb tiles of one batch: the fp32 logits of
@@ -862,6 +888,14 @@ extern "C" int boa_net_forward(boa_net* net, const float* dev_volume, const int 
     return BOA_OK;
 }
 
+// the sliding-window entry points' padded volume PV must hold a patch and the volume V at offset `off`, along every axis
+static int check_padded(const boa_net* net, const int V[3], const int PV[3], const int off[3], const char* who) {
+    for (int a = 0; a < 3; ++a)
+        BOA_REQUIRE(PV[a] >= net->d.patch[a] && off[a] >= 0 && off[a] + V[a] <= PV[a],
+                    "%s: padded dim %d (%d) must cover patch (%d) and volume (%d at %d)", who, a, PV[a], net->d.patch[a], V[a], off[a]);
+    return BOA_OK;
+}
+
 extern "C" int boa_net_predict_sliding_window(boa_net* net, const float* dev_volume, const int V[3], const int PV[3],
                                               const int* vol_off, const int* host_origins, int n_tiles,
                                               const uint16_t* dev_gauss, uint16_t* dev_acc, uint16_t* dev_n) {
@@ -871,10 +905,7 @@ extern "C" int boa_net_predict_sliding_window(boa_net* net, const float* dev_vol
     const boa_net_desc& d = net->d;
     const int zero[3] = {0, 0, 0};
     const int* off = vol_off ? vol_off : zero;
-    for (int a = 0; a < 3; ++a)
-        BOA_REQUIRE(PV[a] >= d.patch[a] && off[a] >= 0 && off[a] + V[a] <= PV[a],
-                    "sliding window: padded dim %d (%d) must cover patch (%d) and volume (%d at %d)", a, PV[a],
-                    d.patch[a], V[a], off[a]);
+    BOA_TRY(check_padded(net, V, PV, off, "sliding window"));
     const size_t pv = (size_t)d.patch[0] * d.patch[1] * d.patch[2];
     for (int t0 = 0; t0 < n_tiles; t0 += net->maxN) {
         int nb = std::min(net->maxN, n_tiles - t0);
@@ -936,6 +967,43 @@ struct TileStash {
     std::vector<int> steps[3];     // tile origins per axis
 };
 
+// byte offsets of a gather-head stash's sub-buffers after act_bytes of activations (the ss16 slot only when `ss16`) and its size
+struct StashOffsets {
+    size_t ss, ss16, ssp, tab, bytes;
+};
+
+static StashOffsets stash_offsets(size_t act_bytes, int n_tiles, int F, bool ss16, size_t tab_ints) {
+    StashOffsets o;
+    o.ss = align256(act_bytes);
+    o.ss16 = align256(o.ss + (size_t)n_tiles * F * 2 * sizeof(float));
+    o.ssp = ss16 ? align256(o.ss16 + (size_t)n_tiles * F * sizeof(unsigned)) : o.ss16;
+    o.tab = align256(o.ssp + (size_t)n_tiles * 32 * sizeof(unsigned));
+    o.bytes = align256(o.tab + tab_ints * sizeof(int));
+    return o;
+}
+
+// The gather head's walk table: the tile origins per axis, then per coordinate the first covering tile and the count (x, y), per
+// 32-voxel z run the tiles that intersect the run, as `first | count << 8` (a tile at origin o covers [o, o + ext[a]) along axis a)
+static std::vector<int> walk_table(const std::vector<int>& s0, const std::vector<int>& s1, const std::vector<int>& s2, const int ext[3],
+                                   const int PV[3]) {
+    const std::vector<int>* steps[3] = {&s0, &s1, &s2};
+    std::vector<int> tab;
+    for (const std::vector<int>* s : steps) tab.insert(tab.end(), s->begin(), s->end());
+    auto cover = [&](int a, int lo, int hi) {
+        const std::vector<int>& st = *steps[a];
+        int first = 0, cnt = 0;
+        for (size_t i = 0; i < st.size(); ++i)
+            if (st[i] <= hi && st[i] + ext[a] > lo) {
+                if (!cnt) first = (int)i;
+                ++cnt;
+            }
+        return first | (cnt << 8);
+    };
+    for (int x = 0; x < PV[0]; ++x) tab.push_back(cover(0, x, x));
+    for (int y = 0; y < PV[1]; ++y) tab.push_back(cover(1, y, y));
+    for (int zb = 0; zb < PV[2]; zb += 32) tab.push_back(cover(2, zb, std::min(zb + 31, PV[2] - 1)));
+    return tab;
+}
 
 // Keeps the context's tile stash out of boa_trim's reach (an allocation that fails under memory pressure trims, and a trim frees an
 // idle stash) from before the tiles are written until the LAST consumer of the TileStash pointers -- the deferred planes' copies, the
@@ -958,12 +1026,9 @@ static int net_forward_into_stash(boa_net* net, const float* dev_volume, const i
     grid_origins(host_origins, n_tiles, steps);
     const int F0 = d.features[0];
     const size_t pv = (size_t)d.patch[0] * d.patch[1] * d.patch[2];
-    // stash layout: [activations][fp32 ss][packed ss16 of the conv stack][head ss table][steps]
-    auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const bool x3 = net->precision == 2;   // split-precision mode: the stash holds the fp32 octet planes, the head reads the fp32 (scale, shift)
-    const size_t o_act = 0, o_ss = align((size_t)n_tiles * pv * F0 * (x3 ? sizeof(float) : sizeof(__half))), o_ss16 = align(o_ss + (size_t)n_tiles * F0 * 2 * sizeof(float)),
-                 o_ssp = align(o_ss16 + (size_t)n_tiles * F0 * sizeof(unsigned)), o_steps = align(o_ssp + (size_t)n_tiles * 32 * sizeof(unsigned)),
-                 need = align(o_steps + ((size_t)n_tiles + PV[0] + PV[1] + PV[2] + 64) * sizeof(int));
+    const ActLayout lay = act_layout(net->mode, F0);
+    const StashOffsets o = stash_offsets(lay.tile(n_tiles, pv), n_tiles, F0, true, (size_t)n_tiles + PV[0] + PV[1] + PV[2] + 64);
+    const size_t need = o.bytes;
     if (c->stash_bytes < need) {
         BOA_HIP_TRY(hipStreamSynchronize(c->stream));
         if (c->stash) hipFree(c->stash);
@@ -991,15 +1056,13 @@ static int net_forward_into_stash(boa_net* net, const float* dev_volume, const i
         c->stash_bytes = need;
     }
     unsigned char* base = (unsigned char*)c->stash;
-    __half* s_act = (__half*)(base + o_act);
-    ts.x3 = x3;
-    float* s_ss = (float*)(base + o_ss);
-    unsigned* s_ss16 = (unsigned*)(base + o_ss16);
-    unsigned* s_ssp = (unsigned*)(base + o_ssp);
-    int* s_steps = (int*)(base + o_steps);
+    ts.x3 = lay.esz == 4;   // split-precision mode: the stash holds the fp32 octet planes, the head reads the fp32 (scale, shift)
+    float* s_ss = (float*)(base + o.ss);
+    unsigned* s_ss16 = (unsigned*)(base + o.ss16);
+    unsigned* s_ssp = (unsigned*)(base + o.ssp);
+    int* s_steps = (int*)(base + o.tab);
     ConvLayer& last = net->dec.back().back();
-    __half* keep_out = last.out;
-    float* keep_out32 = last.out32;
+    void* keep_act = last.act;
     float* keep_ss = last.ss;
     unsigned* keep_ss16 = last.ss16;
     int rc = BOA_OK;
@@ -1008,41 +1071,21 @@ static int net_forward_into_stash(boa_net* net, const float* dev_volume, const i
     for (int t0 = 0; t0 < n_tiles && rc == BOA_OK; t0 += net->maxN) {
         const int nb = std::min(net->maxN, n_tiles - t0);
         // the last decoder conv of this batch writes straight into the stash slots of its tiles
-        if (x3)
-            last.out32 = (float*)s_act + (size_t)t0 * pv * F0;
-        else
-            last.out = s_act + (size_t)t0 * pv * F0;
+        last.act = base + lay.tile(t0, pv);
         last.ss = s_ss + (size_t)t0 * F0 * 2;
-        last.ss16 = s_ss16 + (size_t)t0 * F0;
+        last.ss16 = keep_ss16 ? s_ss16 + (size_t)t0 * F0 : nullptr;
         rc = net_forward_stack(net, dev_volume, V, off, host_origins + (size_t)t0 * 3, nb);
     }
-    last.out = keep_out;
-    last.out32 = keep_out32;
+    last.act = keep_act;
     last.ss = keep_ss;
     last.ss16 = keep_ss16;
     if (rc) return rc;
-    if (!x3) BOA_TRY(launch_pack_head_ss(c, s_ss, s_ssp, n_tiles));
-    // walk table: tile origins per axis, then per coordinate the first covering tile and the count (x, y), per 32-voxel z run the
-    // tiles that intersect the run
-    std::vector<int> tab;
-    for (int a = 0; a < 3; ++a)
-        for (int v : steps[a]) tab.push_back(v);
-    auto cover = [&](int a, int lo, int hi) {
-        int first = 0, cnt = 0;
-        for (size_t i = 0; i < steps[a].size(); ++i)
-            if (steps[a][i] <= hi && steps[a][i] + d.patch[a] > lo) {
-                if (!cnt) first = (int)i;
-                ++cnt;
-            }
-        return first | (cnt << 8);
-    };
-    for (int x = 0; x < PV[0]; ++x) tab.push_back(cover(0, x, x));
-    for (int y = 0; y < PV[1]; ++y) tab.push_back(cover(1, y, y));
-    for (int zb = 0; zb < PV[2]; zb += 32) tab.push_back(cover(2, zb, std::min(zb + 31, PV[2] - 1)));
+    if (!ts.x3) BOA_TRY(launch_pack_head_ss(c, s_ss, s_ssp, n_tiles));
+    const std::vector<int> tab = walk_table(steps[0], steps[1], steps[2], d.patch, PV);
     BOA_HIP_TRY(hipMemcpyAsync(s_steps, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     BOA_HIP_TRY(hipStreamSynchronize(c->stream));   // (the table is a stack-lifetime host vector)
     c->prof_break = true;
-    ts.act = s_act;
+    ts.act = (const __half*)base;
     ts.ss = s_ss;
     ts.ssp = s_ssp;
     ts.tab = s_steps;
@@ -1051,9 +1094,9 @@ static int net_forward_into_stash(boa_net* net, const float* dev_volume, const i
 
 extern "C" int boa_net_labels_supported(boa_net* net, const int* host_origins, int n_tiles) {
     if (!net || !host_origins) return 0;
-    // (patch z extent a multiple of 32 and <= 31 classes: the shapes for which the scatter loop's head runs on the matrix cores too,
-    //  so that the label path and the logits API share one head arithmetic)
-    if (net->precision == 1 || net->mirror_mask != 0 || net->d.features[0] != 32 || net->d.num_classes > 31 || net->d.patch[2] % 32 != 0) return 0;
+    // (record planes -- not fp32_ref's channels-last records --, patch z extent a multiple of 32 and <= 31 classes: the shapes for which
+    //  the scatter loop's head runs on the matrix cores too, so that the label path and the logits API share one head arithmetic)
+    if (!act_layout(net->mode, net->d.features[0]).planar || net->mirror_mask != 0 || net->d.features[0] != 32 || net->d.num_classes > 31 || net->d.patch[2] % 32 != 0) return 0;
     std::vector<int> steps[3];
     return grid_origins(host_origins, n_tiles, steps) ? 1 : 0;
 }
@@ -1071,9 +1114,7 @@ extern "C" int boa_net_predict_labels_fold(boa_net* net, const float* dev_volume
     const boa_net_desc& d = net->d;
     const int zero[3] = {0, 0, 0};
     const int* off = vol_off ? vol_off : zero;
-    for (int a = 0; a < 3; ++a)
-        BOA_REQUIRE(PV[a] >= d.patch[a] && off[a] >= 0 && off[a] + V[a] <= PV[a],
-                    "fused sliding window: padded dim %d (%d) must cover patch (%d) and volume (%d at %d)", a, PV[a], d.patch[a], V[a], off[a]);
+    BOA_TRY(check_padded(net, V, PV, off, "fused sliding window"));
     TileStash ts;
     StashHold hold(net->ctx);   // until launch_gather_head below is queued
     BOA_TRY(net_forward_into_stash(net, dev_volume, V, PV, off, host_origins, n_tiles, ts));
@@ -1115,7 +1156,7 @@ struct boa_stash {
     // boa_net_apply_deferred is ONE more k_gather_head launch over planes [x0, x_split), started from the lower rank's sums
     bool gather = false, x3 = false;
     int dp = 0, x0 = 0, x_split = 0, n0 = 0, n1 = 0, n2 = 0, n_items = 0;
-    size_t o_ss = 0, o_ssp = 0, o_tab = 0;
+    StashOffsets o{};
 };
 
 extern "C" void boa_stash_destroy(boa_stash* st) {
@@ -1136,16 +1177,11 @@ extern "C" int boa_net_predict_sliding_window_deferred(boa_net* net, const float
     BOA_REQUIRE(net->mirror_mask == 0, "deferred sliding window (tile sharding) is not available with test-time mirroring");
     const int zero[3] = {0, 0, 0};
     const int* off = vol_off ? vol_off : zero;
-    for (int a = 0; a < 3; ++a)
-        BOA_REQUIRE(PV[a] >= d.patch[a] && off[a] >= 0 && off[a] + V[a] <= PV[a],
-                    "sliding window: padded dim %d (%d) must cover patch (%d) and volume (%d at %d)", a, PV[a],
-                    d.patch[a], V[a], off[a]);
+    BOA_TRY(check_padded(net, V, PV, off, "sliding window"));
     const int F = d.features[0];
     const size_t plane = (size_t)d.patch[1] * d.patch[2];
     const size_t pv = (size_t)d.patch[0] * plane;
-    const bool f32 = net->precision == 1;   // fp32 reference mode: channels-last fp32 records, the first dp planes are a contiguous prefix
-    const bool x3 = net->precision == 2;    // split-precision mode: fp32 octet planes (F / 8 planes of 32 bytes per voxel)
-    const size_t esz = (f32 || x3) ? 4 : 2;
+    const ActLayout lay = act_layout(net->mode, F);
     boa_stash* st = new boa_stash;
     st->ctx = net->ctx;
     st->head_w = net->head_w;
@@ -1160,7 +1196,7 @@ extern "C" int boa_net_predict_sliding_window_deferred(boa_net* net, const float
         if (dp == 0) continue;
         boa_stash::Item it;
         it.act_off = bytes;
-        bytes += ((size_t)dp * plane * F * esz + 255) / 256 * 256;
+        bytes += align256(lay.bytes((size_t)dp * plane));
         it.ss_off = bytes;
         bytes += 256 * ((F * 2 * 4 + 255) / 256);
         it.planes = dp;
@@ -1174,7 +1210,7 @@ extern "C" int boa_net_predict_sliding_window_deferred(boa_net* net, const float
     // read-modify-write per covering tile.  The planes below x_split are exactly the deferred ones (checked) and all belong to the
     // block's first tile row: they stay untouched until boa_net_apply_deferred adds them, with the same kernel, on top of the
     // lower rank's sums.  Same head arithmetic for every tile (the matrix-core head), whatever the tile origins' alignment.
-    if (!f32 && n_tiles > 0 && boa_net_labels_supported(net, host_origins, n_tiles)) {
+    if (n_tiles > 0 && boa_net_labels_supported(net, host_origins, n_tiles)) {
         // dp0 = the deepest deferral (the block's first row); rows that start further up defer fewer planes -- actual steps below
         // half a patch make the block's second row reach the lower block's last row too.  Every deferred tile keeps dp0 planes (the
         // later rows more than they defer: valid planes of the tile, never visited by the launch over [x0, x_split)).
@@ -1208,22 +1244,19 @@ extern "C" int boa_net_predict_sliding_window_deferred(boa_net* net, const float
             boa_ctx* c = net->ctx;
             // the deferred planes in the gather head's layout
             st->gather = true;
-            st->x3 = x3;
+            st->x3 = ts.x3;
             st->dp = dp0;
             st->x0 = x0;
             st->n1 = (int)ts.steps[1].size();
             st->n2 = (int)ts.steps[2].size();
             st->n_items = n_def;
-            auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
-            const size_t item_act = (size_t)dp0 * plane * F * esz;
-            st->o_ss = align((size_t)n_def * item_act);
-            st->o_ssp = align(st->o_ss + (size_t)n_def * F * 2 * sizeof(float));
-            st->o_tab = align(st->o_ssp + (size_t)n_def * 32 * sizeof(unsigned));
+            const size_t item_act = lay.bytes((size_t)dp0 * plane);
+            st->o = stash_offsets((size_t)n_def * item_act, n_def, F, false,
+                                  def_rows.size() + st->n1 + st->n2 + PV[0] + PV[1] + PV[2] / 32 + 8);
             st->n0 = (int)def_rows.size();
             st->x_split = x_split;
-            const size_t gbytes = align(st->o_tab + (def_rows.size() + st->n1 + st->n2 + PV[0] + PV[1] + PV[2] / 32 + 8) * sizeof(int));
             if (n_def > 0) {
-                if ((rc = boa_malloc(c, gbytes, (void**)&st->arena)) != BOA_OK) {
+                if ((rc = boa_malloc(c, st->o.bytes, (void**)&st->arena)) != BOA_OK) {
                     boa_stash_destroy(st);
                     return rc;
                 }
@@ -1234,14 +1267,11 @@ extern "C" int boa_net_predict_sliding_window_deferred(boa_net* net, const float
                 }
                 bool ok_copy = true;
                 int item = 0;
-                const int nplanes = x3 ? F / 8 : F / 16;   // 32-byte records per voxel and plane in both layouts
                 for (int i = 0; i < n_tiles && ok_copy; ++i) {
                     if (host_defer_planes[i] == 0) continue;
-                    const unsigned char* tile_act = (const unsigned char*)ts.act + (size_t)i * pv * F * esz;
-                    for (int k = 0; k < nplanes && ok_copy; ++k)
-                        ok_copy = hipMemcpyAsync(st->arena + (size_t)item * item_act + (size_t)k * dp0 * plane * 32, tile_act + (size_t)k * pv * 32,
-                                                 (size_t)dp0 * plane * 32, hipMemcpyDeviceToDevice, c->stream) == hipSuccess;
-                    ok_copy = ok_copy && hipMemcpyAsync(st->arena + st->o_ss + (size_t)item * F * 2 * sizeof(float), ts.ss + (size_t)i * F * 2,
+                    ok_copy = lay.copy_head(st->arena + (size_t)item * item_act, (const unsigned char*)ts.act + lay.tile(i, pv), dp0, plane, pv,
+                                            c->stream) == hipSuccess;
+                    ok_copy = ok_copy && hipMemcpyAsync(st->arena + st->o.ss + (size_t)item * F * 2 * sizeof(float), ts.ss + (size_t)i * F * 2,
                                                         (size_t)F * 2 * sizeof(float), hipMemcpyDeviceToDevice, c->stream) == hipSuccess;
                     ++item;
                 }
@@ -1250,29 +1280,14 @@ extern "C" int boa_net_predict_sliding_window_deferred(boa_net* net, const float
                     boa_set_error("deferred sliding window: stash copy failed");
                     return BOA_EHIP;
                 }
-                if (!x3 && (rc = launch_pack_head_ss(c, (const float*)(st->arena + st->o_ss), (unsigned*)(st->arena + st->o_ssp), n_def)) != BOA_OK) {
+                if (!ts.x3 && (rc = launch_pack_head_ss(c, (const float*)(st->arena + st->o.ss), (unsigned*)(st->arena + st->o.ssp), n_def)) != BOA_OK) {
                     boa_stash_destroy(st);
                     return rc;
                 }
-                // walk table of the one-row tile grid with dp planes per tile
-                std::vector<int> tab;
-                for (int v : def_rows) tab.push_back(v);
-                for (int v : ts.steps[1]) tab.push_back(v);
-                for (int v : ts.steps[2]) tab.push_back(v);
-                auto cover = [&](int a, int ext, int lo, int hi) {
-                    const std::vector<int>& stp = a == 0 ? def_rows : ts.steps[a];
-                    int first = 0, cnt = 0;
-                    for (size_t k = 0; k < stp.size(); ++k)
-                        if (stp[k] <= hi && stp[k] + ext > lo) {
-                            if (!cnt) first = (int)k;
-                            ++cnt;
-                        }
-                    return first | (cnt << 8);
-                };
-                for (int x = 0; x < PV[0]; ++x) tab.push_back(cover(0, dp0, x, x));
-                for (int y = 0; y < PV[1]; ++y) tab.push_back(cover(1, d.patch[1], y, y));
-                for (int zb = 0; zb < PV[2]; zb += 32) tab.push_back(cover(2, d.patch[2], zb, std::min(zb + 31, PV[2] - 1)));
-                if (hipMemcpyAsync(st->arena + st->o_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+                // walk table of the deferring tile rows with dp0 planes per tile
+                const int ext[3] = {dp0, d.patch[1], d.patch[2]};
+                const std::vector<int> tab = walk_table(def_rows, ts.steps[1], ts.steps[2], ext, PV);
+                if (hipMemcpyAsync(st->arena + st->o.tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
                     hipStreamSynchronize(c->stream) != hipSuccess) {   // (the table is a stack-lifetime host vector)
                     boa_stash_destroy(st);
                     boa_set_error("deferred sliding window: walk table copy failed");
@@ -1282,8 +1297,8 @@ extern "C" int boa_net_predict_sliding_window_deferred(boa_net* net, const float
             c->prof_break = true;
             const int ntile[3] = {(int)ts.steps[0].size(), (int)ts.steps[1].size(), (int)ts.steps[2].size()};
             const int xr[2] = {x_split, std::min(x_end, PV[0])};
-            rc = launch_gather_head(c, ts.act, x3 ? (const unsigned*)ts.ss : ts.ssp, net->head_w, net->head_b, dev_gauss, d.num_classes, d.patch, PV, ntile,
-                                    ts.tab, dev_acc, 4, 1, nullptr, 0, nullptr, nullptr, nullptr, nullptr, d.lrelu_slope, n_tiles, x3, xr, dev_n, 0);
+            rc = launch_gather_head(c, ts.act, ts.x3 ? (const unsigned*)ts.ss : ts.ssp, net->head_w, net->head_b, dev_gauss, d.num_classes, d.patch, PV, ntile,
+                                    ts.tab, dev_acc, 4, 1, nullptr, 0, nullptr, nullptr, nullptr, nullptr, d.lrelu_slope, n_tiles, ts.x3, xr, dev_n, 0);
             if (rc != BOA_OK) {
                 boa_stash_destroy(st);
                 return rc;
@@ -1309,23 +1324,13 @@ extern "C" int boa_net_predict_sliding_window_deferred(boa_net* net, const float
         ConvLayer& last = net->dec.back().back();
         for (int i = 0; i < nb && rc == BOA_OK; ++i) {
             const int* stt = host_origins + (size_t)(t0 + i) * 3;
-            const __half* act = (f32 || x3) ? nullptr : last.out + (size_t)i * pv * F;
             const float* ss = last.ss + (size_t)i * F * 2;
             int dp = host_defer_planes[t0 + i];
             if (dp > 0) {
                 const boa_stash::Item& it = st->items[item++];
-                // chunk-planar: the first dp axis-0 planes of every 16-channel plane; the stash keeps them planar with its own
-                // plane stride (dp * plane voxels)
-                bool ok_copy = true;
-                if (f32)
-                    ok_copy = hipMemcpyAsync(st->arena + it.act_off, last.out32 + (size_t)i * pv * F, (size_t)dp * plane * F * 4,
-                                             hipMemcpyDeviceToDevice, net->ctx->stream) == hipSuccess;
-                for (int k = 0; x3 && k < F / 8 && ok_copy; ++k)
-                    ok_copy = hipMemcpyAsync(st->arena + it.act_off + (size_t)k * dp * plane * 32, last.out32 + (size_t)i * pv * F + (size_t)k * pv * 8,
-                                             (size_t)dp * plane * 32, hipMemcpyDeviceToDevice, net->ctx->stream) == hipSuccess;
-                for (int k = 0; !f32 && !x3 && k < F / 16 && ok_copy; ++k)
-                    ok_copy = hipMemcpyAsync(st->arena + it.act_off + (size_t)k * dp * plane * 32, act + (size_t)k * pv * 16,
-                                             (size_t)dp * plane * 32, hipMemcpyDeviceToDevice, net->ctx->stream) == hipSuccess;
+                // the first dp axis-0 planes in the stash, with its own plane stride (dp * plane voxels)
+                const bool ok_copy = lay.copy_head(st->arena + it.act_off, (const unsigned char*)last.act + lay.tile(i, pv), dp, plane, pv,
+                                                   net->ctx->stream) == hipSuccess;
                 if (!ok_copy ||
                     hipMemcpyAsync(st->arena + it.ss_off, ss, (size_t)F * 2 * 4, hipMemcpyDeviceToDevice,
                                    net->ctx->stream) != hipSuccess) {
@@ -1359,28 +1364,16 @@ extern "C" int boa_net_apply_deferred(boa_net* net, const boa_stash* st, const u
         const int P[3] = {st->dp, d.patch[1], d.patch[2]};
         const int ntile[3] = {st->n0, st->n1, st->n2};
         const int xr[2] = {st->x0, std::min(st->x_split, PV[0])};
-        return launch_gather_head(net->ctx, (const __half*)st->arena, (const unsigned*)(st->arena + (st->x3 ? st->o_ss : st->o_ssp)), st->head_w, st->head_b,
-                                  dev_gauss, d.num_classes, P, PV, ntile, (const int*)(st->arena + st->o_tab), dev_acc, 4, 1, nullptr, 0, nullptr, nullptr,
+        return launch_gather_head(net->ctx, (const __half*)st->arena, (const unsigned*)(st->arena + (st->x3 ? st->o.ss : st->o.ssp)), st->head_w, st->head_b,
+                                  dev_gauss, d.num_classes, P, PV, ntile, (const int*)(st->arena + st->o.tab), dev_acc, 4, 1, nullptr, 0, nullptr, nullptr,
                                   nullptr, nullptr, d.lrelu_slope, st->n_items, st->x3, xr, dev_n, 1);
     }
+    const ActLayout lay = act_layout(net->mode, d.features[0]);
     for (const boa_stash::Item& it : st->items) {  // the stash keeps the canonical tile order
         int P[3] = {it.planes, d.patch[1], d.patch[2]};
-        if (net->precision == 1)
-            BOA_TRY(launch_head_f32(net->ctx, (const float*)(st->arena + it.act_off), (const float*)(st->arena + it.ss_off),
-                                    d.features[0], P, d.num_classes, st->head_w, st->head_b, d.lrelu_slope, nullptr, dev_gauss,
-                                    dev_acc, dev_n, PV, it.start));
-        else if (net->precision == 2 && d.features[0] == 32 && d.num_classes <= 32)
-            BOA_TRY(launch_head_x3(net->ctx, (const float*)(st->arena + it.act_off), (const float*)(st->arena + it.ss_off),
-                                   d.features[0], P, d.num_classes, st->head_w, st->head_b, d.lrelu_slope, nullptr, dev_gauss,
-                                   dev_acc, dev_n, PV, it.start, (size_t)it.planes * d.patch[1] * d.patch[2]));
-        else if (net->precision == 2)
-            BOA_TRY(launch_head_f32(net->ctx, (const float*)(st->arena + it.act_off), (const float*)(st->arena + it.ss_off),
-                                    d.features[0], P, d.num_classes, st->head_w, st->head_b, d.lrelu_slope, nullptr, dev_gauss,
-                                    dev_acc, dev_n, PV, it.start, (size_t)it.planes * d.patch[1] * d.patch[2]));
-        else
-            BOA_TRY(launch_head(net->ctx, (const __half*)(st->arena + it.act_off), (const float*)(st->arena + it.ss_off),
-                                d.features[0], P, d.num_classes, st->head_w, st->head_b, d.lrelu_slope, nullptr, dev_gauss,
-                                dev_acc, dev_n, PV, it.start, (size_t)it.planes * d.patch[1] * d.patch[2]));
+        BOA_TRY(scatter_head(net, st->arena + it.act_off, (const float*)(st->arena + it.ss_off), P,
+                             lay.plane_stride((size_t)it.planes * d.patch[1] * d.patch[2]), st->head_w, st->head_b, nullptr, dev_gauss,
+                             dev_acc, dev_n, PV, it.start));
     }
     return BOA_OK;
 }
@@ -1441,19 +1434,19 @@ extern "C" int boa_conv_block_test(boa_ctx* ctx, const float* dev_in, int N, int
     return rc;
 }
 
-// octet planes -> fp32 NCDHW for the debug seams, with a transposed conv's output fold taken out again (x / fold is exact): through
+// fp32 NCDHW of one stored tile for the debug seams, with a transposed conv's output fold taken out again (x / fold is exact): through
 // the conversion's (scale, shift) path with scale 1 / fold, shift 0 and slope 1 (LeakyReLU with slope 1 is the identity)
-static int octet_to_nchw_unfold(boa_net* net, const float* a32, float fold, int C, size_t vox, float* out) {
-    if (fold == 1.f) return launch_octet_to_nchw_f32(net->ctx, a32, nullptr, net->d.lrelu_slope, C, vox, out);
-    std::vector<float> tab((size_t)C * 2);
-    for (int i = 0; i < C; ++i) {
+static int debug_to_nchw(boa_net* net, const ActLayout& lay, const void* tile, const float* ss, float fold, size_t vox, float* out) {
+    if (fold == 1.f) return lay.to_nchw(net->ctx, tile, ss, net->d.lrelu_slope, vox, out);
+    std::vector<float> tab((size_t)lay.C * 2);
+    for (int i = 0; i < lay.C; ++i) {
         tab[2 * i] = 1.f / fold;
         tab[2 * i + 1] = 0.f;
     }
     float* dss = nullptr;
     BOA_TRY(boa_malloc(net->ctx, tab.size() * sizeof(float), (void**)&dss));
     int rc = boa_h2d(net->ctx, dss, tab.data(), tab.size() * sizeof(float));
-    if (rc == BOA_OK) rc = launch_octet_to_nchw_f32(net->ctx, a32, dss, 1.f, C, vox, out);
+    if (rc == BOA_OK) rc = lay.to_nchw(net->ctx, tile, dss, 1.f, vox, out);
     if (rc == BOA_OK) rc = boa_sync(net->ctx);
     boa_free(net->ctx, dss);
     return rc;
@@ -1465,8 +1458,7 @@ extern "C" int boa_net_debug_activation(boa_net* net, int kind, int stage, int c
     BOA_REQUIRE(tile >= 0 && tile < net->maxN, "boa_net_debug_activation: tile %d outside the batch", tile);
     BOA_TRY(net_bind_arena(net));
     const float* ss = nullptr;
-    const __half* a16 = nullptr;
-    const float* a32 = nullptr;
+    const void* act = nullptr;
     float fold = 1.f;
     int Cc = 0, dm[3] = {0, 0, 0};
     if (kind == 1) {
@@ -1474,8 +1466,7 @@ extern "C" int boa_net_debug_activation(boa_net* net, int kind, int stage, int c
         const UpLayer& U = net->up[stage];
         Cc = U.Cout;
         for (int a = 0; a < 3; ++a) dm[a] = U.din[a] * U.s[a];
-        a16 = U.out;
-        a32 = U.out32;
+        act = U.act;
         fold = U.fold;
     } else {
         auto& stages = kind == 0 ? net->enc : net->dec;
@@ -1484,20 +1475,15 @@ extern "C" int boa_net_debug_activation(boa_net* net, int kind, int stage, int c
         const ConvLayer& L = stages[stage][conv];
         Cc = L.g.Cout;
         dm[0] = L.g.Do; dm[1] = L.g.Ho; dm[2] = L.g.Wo;
-        a16 = L.out;
-        a32 = L.out32;
+        act = L.act;
         ss = L.ss + (size_t)tile * Cc * 2;
     }
     *channels_out = Cc;
     for (int a = 0; a < 3; ++a) dims_out[a] = dm[a];
     if (!dev_out) return BOA_OK;  // size query
     const size_t vox = (size_t)dm[0] * dm[1] * dm[2];
-    if (net->precision == 1)
-        return launch_ndhwc32_to_nchw_f32(net->ctx, a32 + (size_t)tile * vox * Cc, ss, net->d.lrelu_slope, Cc, vox, dev_out);
-    if (net->precision == 2)
-        return ss ? launch_octet_to_nchw_f32(net->ctx, a32 + (size_t)tile * vox * Cc, ss, net->d.lrelu_slope, Cc, vox, dev_out)
-                  : octet_to_nchw_unfold(net, a32 + (size_t)tile * vox * Cc, fold, Cc, vox, dev_out);
-    return launch_ndhwc_to_nchw_f32(net->ctx, a16 + (size_t)tile * vox * Cc, ss, net->d.lrelu_slope, 1, Cc, vox, dev_out);
+    const ActLayout lay = act_layout(net->mode, Cc);
+    return debug_to_nchw(net, lay, (const unsigned char*)act + lay.tile(tile, vox), ss, fold, vox, dev_out);
 }
 
 extern "C" int boa_net_debug_layer(boa_net* net, int kind, int stage, int conv, int tile, float* dev_raw, float* host_ss,
@@ -1506,8 +1492,7 @@ extern "C" int boa_net_debug_layer(boa_net* net, int kind, int stage, int conv, 
     BOA_REQUIRE(tile >= 0 && tile < net->maxN, "boa_net_debug_layer: tile %d outside the batch", tile);
     BOA_TRY(net_bind_arena(net));
     const boa_net_desc& d = net->d;
-    const __half* a16 = nullptr;
-    const float* a32 = nullptr;
+    const void* act = nullptr;
     const ConvLayer* L = nullptr;
     float fold = 1.f;
     int Cc = 0, dm[3] = {0, 0, 0}, info[3] = {0, 0, 0};
@@ -1516,7 +1501,7 @@ extern "C" int boa_net_debug_layer(boa_net* net, int kind, int stage, int conv, 
         *channels_out = d.num_classes;
         for (int a = 0; a < 3; ++a) dims_out[a] = d.patch[a];
         if (host_info) {
-            host_info[0] = net->precision == 0 ? BOA_LK_HEAD_MFMA : head_x3(net) ? BOA_LK_HEAD_X3 : BOA_LK_HEAD_F32;
+            host_info[0] = head_kernel(net);
             host_info[1] = host_info[2] = 0;
         }
         return BOA_OK;
@@ -1526,19 +1511,9 @@ extern "C" int boa_net_debug_layer(boa_net* net, int kind, int stage, int conv, 
         const UpLayer& U = net->up[stage];
         Cc = U.Cout;
         for (int a = 0; a < 3; ++a) dm[a] = U.din[a] * U.s[a];
-        a16 = U.out;
-        a32 = U.out32;
-        if (net->precision == 1) {
-            info[0] = BOA_LK_CONVT_F32;
-        } else if (net->precision == 2) {
-            info[0] = BOA_LK_CONVT_X3;
-            info[1] = convt_x3_mt((size_t)U.din[0] * U.din[1] * U.din[2]);
-            info[2] = (int)std::lround(std::log2((double)U.fold));
-            fold = U.fold;
-        } else {
-            const int form = convt_mfma_form(U.Cin, U.s, true);   // (the source of a transposed conv is always a normalised conv output)
-            info[0] = form == 2 ? BOA_LK_CONVT_DEEP : form == 1 ? BOA_LK_CONVT_RW : BOA_LK_CONVT_MFMA;
-        }
+        act = U.act;
+        fold = U.fold;
+        convt_kernel_info(net, U, info);
     } else {
         auto& stages = kind == 0 ? net->enc : net->dec;
         BOA_REQUIRE((kind == 0 || kind == 2) && stage >= 0 && stage < (int)stages.size() && conv >= 0 && conv < (int)stages[stage].size(),
@@ -1546,18 +1521,8 @@ extern "C" int boa_net_debug_layer(boa_net* net, int kind, int stage, int conv, 
         L = &stages[stage][conv];
         Cc = L->g.Cout;
         dm[0] = L->g.Do; dm[1] = L->g.Ho; dm[2] = L->g.Wo;
-        a16 = L->out;
-        a32 = L->out32;
-        if (net->precision == 1) {
-            info[0] = BOA_LK_CONV_F32;
-        } else if (L->first) {
-            info[0] = first_mfma_ok(d.in_channels, d.patch, L->g.k, L->g.Cout) ? BOA_LK_FIRST_MFMA : BOA_LK_FIRST_VALU;
-        } else {
-            const ConvTile& t = L->t;
-            info[0] = t.variant == 2 ? BOA_LK_CONV_NS : t.variant == 1 ? BOA_LK_CONV_WS : BOA_LK_CONV_MFMA;
-            info[1] = t.R;
-            info[2] = t.variant == 1 && conv_ws_row_reuse(t.R, L->g.k[1], L->g.s[1], t.w[1], t.b[1], t.b[2]) ? 1 : 0;
-        }
+        act = L->act;
+        conv_kernel_info(net, *L, info);
     }
     *channels_out = Cc;
     for (int a = 0; a < 3; ++a) dims_out[a] = dm[a];
@@ -1578,11 +1543,8 @@ extern "C" int boa_net_debug_layer(boa_net* net, int kind, int stage, int conv, 
     }
     if (!dev_raw) return BOA_OK;
     const size_t vox = (size_t)dm[0] * dm[1] * dm[2];
-    if (net->precision == 1)
-        return launch_ndhwc32_to_nchw_f32(net->ctx, a32 + (size_t)tile * vox * Cc, nullptr, d.lrelu_slope, Cc, vox, dev_raw);
-    if (net->precision == 2)
-        return octet_to_nchw_unfold(net, a32 + (size_t)tile * vox * Cc, fold, Cc, vox, dev_raw);
-    return launch_ndhwc_to_nchw_f32(net->ctx, a16 + (size_t)tile * vox * Cc, nullptr, d.lrelu_slope, 1, Cc, vox, dev_raw);
+    const ActLayout lay = act_layout(net->mode, Cc);
+    return debug_to_nchw(net, lay, (const unsigned char*)act + lay.tile(tile, vox), nullptr, fold, vox, dev_raw);
 }
 
 extern "C" int boa_head_tile(boa_ctx* ctx, const uint16_t* dev_act, const float* dev_ss, int F0, const int P[3], int C,

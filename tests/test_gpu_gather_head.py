@@ -237,7 +237,7 @@ def test_gather_ties_and_small_class_counts(ctx, nc, precision):
     np.testing.assert_array_equal(got, want)
 
 
-@pytest.mark.parametrize("precision", ["fp16", "fp32"])
+@pytest.mark.parametrize("precision", ["fp16", "fp32", "fp32_ref"])
 @pytest.mark.parametrize("split_row", [None, 1, 2])
 def test_raw_partial_sums_equal_the_scatter_accumulators(ctx, precision, split_row):
     """The gather head's raw mode (tile sharding, the resampled label path): the fp16 accumulator planes and the weight plane it writes
@@ -263,7 +263,10 @@ def test_raw_partial_sums_equal_the_scatter_accumulators(ctx, precision, split_r
         ctx.counters(reset=True)
         p._run_fold(dvol, V, PV, below, origins, acc_s, n_s, 0)             # scatter loop
         cs = ctx.counters(reset=True)
-        assert cs["head_gather"] == 0 and (cs["head_mfma"] > 0 or cs["x3"] > 0) and cs["head_valu"] == 0, cs
+        if precision == "fp32_ref":   # no gather head in the fp32 reference mode: every head is the fp32 one
+            assert cs["head_gather"] == 0 and cs["head_mfma"] == 0 and cs["x3"] == 0 and cs["f32"] > 0 and cs["head_valu"] == 0, cs
+        else:
+            assert cs["head_gather"] == 0 and (cs["head_mfma"] > 0 or cs["x3"] > 0) and cs["head_valu"] == 0, cs
         p._ensure_net(0)
         acc_g.zero()
         n_g.zero()
@@ -289,7 +292,10 @@ def test_raw_partial_sums_equal_the_scatter_accumulators(ctx, precision, split_r
             check(p.lib.boa_net_apply_deferred(p._net, st, g.vp if g else None, acc_g.vp, n_g.vp, int3(PV)), "apply")
             p.lib.boa_stash_destroy(st)
         cg = ctx.counters(reset=True)
-        assert cg["head_gather"] == (1 if split_row is None else 3) and cg["head_mfma"] == 0 and cg["head_valu"] == 0, cg
+        if precision == "fp32_ref":   # the deferred calls take the scatter form: the same fp32 head per tile
+            assert cg["head_gather"] == 0 and cg["head_mfma"] == 0 and cg["x3"] == 0 and cg["f32"] > 0 and cg["head_valu"] == 0, cg
+        else:
+            assert cg["head_gather"] == (1 if split_row is None else 3) and cg["head_mfma"] == 0 and cg["head_valu"] == 0, cg
         np.testing.assert_array_equal(acc_g.download((nc, *PV), np.uint16), acc_s.download((nc, *PV), np.uint16))
         np.testing.assert_array_equal(n_g.download(tuple(PV), np.uint16), n_s.download(tuple(PV), np.uint16))
     finally:
