@@ -121,7 +121,8 @@ extern "C" int boa_tissue_aggregate(boa_ctx* c, const int16_t* dev_ct, const int
     BOA_HIP_TRY(hipMemsetAsync(dev_counts, 0, (size_t)Z * 16 * sizeof(uint32_t), c->stream));
     BOA_HIP_TRY(hipMemsetAsync(dev_hu_sums, 0, (size_t)Z * 16 * sizeof(int64_t), c->stream));
     const int sv = Y * X;
-    const bool vec8 = (sv % 8 == 0) && (((uintptr_t)dev_ct) % 16 == 0) && (((uintptr_t)dev_regions) % 8 == 0) &&
+    // (NULL optional arrays pass; ct_rules is read with the same 16-byte loads as ct)
+    const bool vec8 = (sv % 8 == 0) && (((uintptr_t)dev_ct) % 16 == 0) && (((uintptr_t)dev_ct_rules) % 16 == 0) && (((uintptr_t)dev_regions) % 8 == 0) &&
                       (((uintptr_t)dev_parts) % 8 == 0) && (((uintptr_t)dev_tissues_out) % 8 == 0);
     const int nvec = vec8 ? sv / 8 : sv;
     // workgroups per slice: 16 (each thread reduces >= 64 voxels before the wave / block reduction and its 14 global atomics; 64
@@ -408,8 +409,14 @@ __global__ __launch_bounds__(HT) void k_label_hist(const short* __restrict__ ct,
                 }
             }
         }
+        // The flush decision must be the same in all 16 waves: flush() holds barriers and empties slots.  The first barrier ends
+        // this iteration's inserts, so every thread latches the same nkeys; the second keeps the next iteration's inserts (which
+        // increment nkeys) behind the last of those reads.  Without it a wave that read nkeys <= HIST_FLUSH could insert a new key
+        // before a slower wave's read, which then saw nkeys > HIST_FLUSH and flushed alone.
         __syncthreads();
-        if (nkeys > HIST_FLUSH) flush();   // (uniform: nkeys is read after the barrier by everyone)
+        const bool full = nkeys > HIST_FLUSH;
+        __syncthreads();
+        if (full) flush();
     }
     // tail (n % 16 voxels) and head, one by one straight into the global table
     if (blockIdx.x == 0) {

@@ -156,6 +156,13 @@ def test_voxel_aggregation_config3_vs_numpy(ctx):
     hu = np.arange(hist.shape[1], dtype=np.int64) + M.HU_MIN
     sums = np.bincount(lab.ravel(), weights=ct.ravel().astype(np.float64), minlength=256)   # exact: |sum| < 2^53
     np.testing.assert_array_equal((hist.astype(np.int64) * hu[None]).sum(axis=1)[1:], sums[1:].astype(np.int64))
+    # every bin (the two sums above do not see counts that moved between bins of one label symmetrically about their mean)
+    assert M.HU_MIN == -32768 and hist.shape == (256, 65536)              # the full int16 range: no clamp in the key below
+    key = lab.ravel().astype(np.int32) * hist.shape[1] + (ct.ravel().astype(np.int32) - M.HU_MIN)
+    bins = np.bincount(key, minlength=hist.size).reshape(hist.shape)
+    del key
+    bins[0] = 0
+    np.testing.assert_array_equal(hist, bins)
     # tissues: regions from the label pattern (values 1..11), parts all TORSO -> slice tables must add up to the volume
     regions = (lab % 12).astype(np.uint8)
     d_reg = ctx.from_numpy(regions)
