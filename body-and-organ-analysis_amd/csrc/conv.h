@@ -34,6 +34,7 @@ struct ConvTile {
     size_t lds_bytes;
 };
 
+// ---- conv.hip: weight packers, tile selection, the variant-0 conv, InstanceNorm finalize (layout helpers: end of this file) ----------
 bool choose_conv_tile(const ConvGeom& g, int cu_count, ConvTile* out, bool x3 = false);
 
 // packed weight sizes / packers (host side)
@@ -56,17 +57,17 @@ int launch_conv_mfma(boa_ctx* ctx, const ActSrc& s0, const ActSrc& s1, const Con
                      const __half* wpk, const float* bias, float slope, __half* out, float* partials);
 int conv_nblk(const ConvTile& t, int cu_count, int Cout);
 int conv_ws_nslots(int tiles_per_sample, int cu_count);
-
-// First conv: reads tiles straight out of the resident fp32 volume [Cin][V0][V1][V2] (zero outside the volume
-// and outside the tile), fp32 VALU, stride 1.  w: dev fp32 [Cin][taps][Cout].
-int launch_conv_first(boa_ctx* ctx, const float* volume, const int V[3], const int vol_off[3], const int* dev_origins,
-                      int N, int Cin, const int P[3], const int k[3], int Cout, const float* w, const float* bias,
-                      float* padded_scratch, __half* out, float* partials, int* nblk_out, int flip_mask = 0, float* out32 = nullptr);
 // split-precision conv (k_conv_ws<..., X3>): fp32 octet-planar sources / output, fp32 (scale, shift) tables
 int launch_conv_x3(boa_ctx* ctx, const float* src0, const float* ss0, int C0, const float* src1, const float* ss1, int C1,
                    const ConvGeom& g, const ConvTile& t, const __half* wpk, float wscale, const float* bias, float slope, float* out,
                    float* partials);
-int conv_first_nblk(const int P[3], int cu_count);
+
+// InstanceNorm statistics -> (scale, shift) per (n, c):  scale = gamma * rsqrt(var + eps), shift = beta - mean * scale
+// clear != 0: zero the partials after reading them (k_conv_ws expects a zeroed table: it only writes the slots of waves
+// that worked on an (n, cout) -- the table is zeroed once at allocation and kept zeroed by the finalize).
+int launch_norm_finalize(boa_ctx* ctx, float* partials, int nblk, int N, int C, double count,
+                         const float* gamma, const float* beta, float eps, float* ss_out, unsigned* ss16_out, int clear);
+
 // which form the launchers pick (shared with the per-layer test seam boa_net_debug_layer, so that it reports what ran):
 // first conv on k_conv_first_mfma (else the fp32 VALU k_conv_first); k_conv_ws in its row-reuse form (X3: the tap-paired
 // consume_chunk_y_x3; else the per-tap consume_chunk); fp16 transposed conv 0 = k_convt_mfma, 1 = k_convt_mfma_rw, 2 = k_convt_deep;
@@ -75,18 +76,22 @@ bool first_mfma_ok(int Cin, const int P[3], const int k[3], int Cout);
 bool conv_ws_row_reuse(int R, int k1, int s1, int w1, int b1, int b2);
 int convt_mfma_form(int Cin, const int s[3], bool norm_src);
 int convt_x3_mt(size_t vin);
+
+// ---- conv_first.hip --------------------------------------------------------------------------------------------------------------
+// First conv: reads tiles straight out of the resident fp32 volume [Cin][V0][V1][V2] (zero outside the volume
+// and outside the tile), fp32 VALU, stride 1.  w: dev fp32 [Cin][taps][Cout].
+int launch_conv_first(boa_ctx* ctx, const float* volume, const int V[3], const int vol_off[3], const int* dev_origins,
+                      int N, int Cin, const int P[3], const int k[3], int Cout, const float* w, const float* bias,
+                      float* padded_scratch, __half* out, float* partials, int* nblk_out, int flip_mask = 0, float* out32 = nullptr);
+int conv_first_nblk(const int P[3], int cu_count);
 void conv_first_padded_dims(const int P[3], const int k[3], int out[3]);
 
-// InstanceNorm statistics -> (scale, shift) per (n, c):  scale = gamma * rsqrt(var + eps), shift = beta - mean * scale
-// clear != 0: zero the partials after reading them (k_conv_ws expects a zeroed table: it only writes the slots of waves
-// that worked on an (n, cout) -- the table is zeroed once at allocation and kept zeroed by the finalize).
-int launch_norm_finalize(boa_ctx* ctx, float* partials, int nblk, int N, int C, double count,
-                         const float* gamma, const float* beta, float eps, float* ss_out, unsigned* ss16_out, int clear);
-
+// ---- convt.hip -------------------------------------------------------------------------------------------------------------------
 // ConvTranspose3d with kernel == stride, + bias; input source with deferred norm; out fp16 raw.
 int launch_convt_mfma(boa_ctx* ctx, const ActSrc& src, int N, const int din[3], const int s[3], int Cout,
                       const __half* wpk, const float* bias, float slope, __half* out);
 
+// ---- head.hip --------------------------------------------------------------------------------------------------------------------
 // 1x1x1 head on the last decoder activation.  mode 0: write fp32 logits [C][P0][P1][P2];
 // mode 1: pred * gauss accumulated into fp16 acc/n at `start` (NN/inference/predict_from_raw_data.py:611-614).
 int launch_head(boa_ctx* ctx, const __half* act, const float* ss, int F0, const int P[3], int C, const float* w,
@@ -184,7 +189,7 @@ int launch_octet_to_nchw_f32(boa_ctx* ctx, const float* in, const float* ss, flo
 
 int launch_ndhwc32_to_nchw_f32(boa_ctx* ctx, const float* in, const float* ss, float slope, int C, size_t vox, float* out);
 
-// layout helpers (tests / debug)
+// layout helpers (conv.hip; tests / debug)
 int launch_nchw_to_ndhwc_f16(boa_ctx* ctx, const float* in, int N, int C, size_t vox, __half* out);
 int launch_ndhwc_to_nchw_f32(boa_ctx* ctx, const __half* in, const float* ss, float slope, int N, int C, size_t vox,
                              float* out);

@@ -1,7 +1,9 @@
 // 3-D convolution stack for gfx950: implicit-GEMM 3x3x3 / strided conv on f16 MFMA (32x32x16) with the
 // producer's InstanceNorm+LeakyReLU applied while staging the LDS halo tile, InstanceNorm statistics reduced in
-// the epilogue (deterministic per-block partials), first-layer fp32 VALU conv reading tiles out of the resident
-// volume, transposed conv (kernel == stride) on MFMA, fused 1x1x1 head + Gaussian fp16 accumulation.
+// the epilogue (deterministic per-block partials).  This file: the weight packers, tile selection, the variant-0 conv
+// k_conv_mfma, the InstanceNorm finalize and the layout helpers.  The other kernel families have files of their own:
+// conv_ws.hip / conv_ns.hip (the producer/consumer and N-split convs), conv_first.hip (first layer, tiles read out of the
+// resident volume), convt.hip (transposed conv, kernel == stride), head.hip (1x1x1 head + Gaussian fp16 accumulation).
 //
 // Replaces `self.network(x)` (NN/inference/predict_from_raw_data.py:543), i.e. dynamic_network_architectures'
 // PlainConvUNet as configured by NN/utilities/plans_handling/plans_handler.py:59-92.
@@ -448,6 +450,13 @@ static ConvArgs conv_args(const ConvGeom& g, const ConvTile& t, const __half* wp
     return a;
 }
 
+template <int R>
+static void launch_conv_mfma_r(boa_ctx* ctx, dim3 grid, size_t lds_bytes, const ConvArgs& a) {
+    static bool once = (hipFuncSetAttribute((const void*)k_conv_mfma<R>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), true);
+    (void)once;
+    hipLaunchKernelGGL(k_conv_mfma<R>, grid, dim3(256), lds_bytes, ctx->stream, a);
+}
+
 int launch_conv_mfma(boa_ctx* ctx, const ActSrc& s0, const ActSrc& s1, const ConvGeom& g, const ConvTile& t,
                      const __half* wpk, const float* bias, float slope, __half* out, float* partials) {
     BOA_REQUIRE(s0.C % 16 == 0 && s1.C % 16 == 0 && s0.C > 0, "conv: input channels (%d,%d) must be multiples of 16",
@@ -468,24 +477,9 @@ int launch_conv_mfma(boa_ctx* ctx, const ActSrc& s0, const ActSrc& s1, const Con
     ctx->counters[BOA_CNT_CONV_SIMPLE]++;
     KernelTimer tm(ctx, BOA_K_CONV_MFMA, flops, bytes);
     switch (t.R) {
-        case 4: {
-            static bool once = (hipFuncSetAttribute((const void*)k_conv_mfma<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), true);
-            (void)once;
-            hipLaunchKernelGGL(k_conv_mfma<4>, grid, dim3(256), t.lds_bytes, ctx->stream, a);
-            break;
-        }
-        case 2: {
-            static bool once = (hipFuncSetAttribute((const void*)k_conv_mfma<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), true);
-            (void)once;
-            hipLaunchKernelGGL(k_conv_mfma<2>, grid, dim3(256), t.lds_bytes, ctx->stream, a);
-            break;
-        }
-        case 1: {
-            static bool once = (hipFuncSetAttribute((const void*)k_conv_mfma<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), true);
-            (void)once;
-            hipLaunchKernelGGL(k_conv_mfma<1>, grid, dim3(256), t.lds_bytes, ctx->stream, a);
-            break;
-        }
+        case 4: launch_conv_mfma_r<4>(ctx, grid, t.lds_bytes, a); break;
+        case 2: launch_conv_mfma_r<2>(ctx, grid, t.lds_bytes, a); break;
+        case 1: launch_conv_mfma_r<1>(ctx, grid, t.lds_bytes, a); break;
         default:
             boa_set_error("conv: unsupported R=%d", t.R);
             return BOA_EINVAL;
@@ -513,640 +507,6 @@ int launch_conv_x3(boa_ctx* ctx, const float* src0, const float* ss0, int C0, co
     const double bytes = 4.0 * ((double)g.N * g.Di * g.Hi * g.Wi * (C0 + C1) + vox * g.Cout);
     if (t.variant == 2) return launch_conv_ns(ctx, a, t, flops, bytes, true);
     return launch_conv_ws(ctx, a, t, flops, bytes, true);
-}
-
-// ======================================================================================================
-// first conv: fp32 VALU, tiles gathered from the resident volume
-// Stage 1: k_gather_patches copies the N tiles out of the resident volume into a zero-padded dense fp32 buffer
-// [N][Cin][PX][PY][PZ] (conv padding + pad_nd_image zeros + tile overhang), so that stage 2 has no bounds logic.
-// Stage 2: k_conv_first<K0,K1,K2>: each thread computes FV consecutive voxels along the contiguous axis x 32 output
-// channels, so one LDS read of a weight quad feeds 4 * FV FMAs and one input value feeds up to 3 taps x 32
-// channels.  Weights live in LDS ([Cin][tap][32] floats, broadcast reads); a block covers FT0 x FT1 x FT2 voxels.
-#define FT0 4
-#define FT1 4
-#define FT2 64
-#define FV 4
-
-__global__ __launch_bounds__(256) void k_gather_patches(const float* __restrict__ vol, const int* __restrict__ origins,
-                                                        int V0, int V1, int V2, int o0, int o1, int o2, int Cin, int P0,
-                                                        int P1, int P2, int pad0, int pad1, int pad2, int PX, int PY, int PZ,
-                                                        int flip, float* __restrict__ out) {
-    const int n = blockIdx.z, ci = blockIdx.y;
-    const unsigned pvol = (unsigned)(PX * PY * PZ);  // (a padded tile is far below 2^31 voxels: 32-bit index divisions)
-    const unsigned i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= pvol) return;
-    const unsigned r = i / (unsigned)PZ;
-    const int z = (int)(i - r * (unsigned)PZ), x = (int)(r / (unsigned)PY), y = (int)(r - (unsigned)x * (unsigned)PY);
-    const int px = x - pad0, py = y - pad1, pz = z - pad2;  // patch coordinates
-    float v = 0.f;
-    if (px >= 0 && px < P0 && py >= 0 && py < P1 && pz >= 0 && pz < P2) {
-        // test-time mirroring (predict_from_raw_data.py:541-557): the network sees torch.flip(tile, axes)
-        const int qx = (flip & 1) ? P0 - 1 - px : px, qy = (flip & 2) ? P1 - 1 - py : py, qz = (flip & 4) ? P2 - 1 - pz : pz;
-        const int vx = origins[n * 3 + 0] + qx - o0, vy = origins[n * 3 + 1] + qy - o1, vz = origins[n * 3 + 2] + qz - o2;
-        if (vx >= 0 && vx < V0 && vy >= 0 && vy < V1 && vz >= 0 && vz < V2)
-            v = vol[(size_t)ci * V0 * V1 * V2 + ((size_t)vx * V1 + vy) * V2 + vz];
-    }
-    out[((size_t)n * Cin + ci) * pvol + i] = v;
-}
-
-struct FirstArgs {
-    const float* padded;  // [N][Cin][PX][PY][PZ]
-    int PX, PY, PZ;
-    int N, Cin, P0, P1, P2, Cout;
-    const float* w;  // [Cin][taps][Cout]
-    const float* bias;
-    __half* out;
-    float* partials;
-    int t0, t1, t2;
-    int nblk;  // stride of the partials table (>= number of entries a launch writes)
-    float* out32;  // F32OUT: fp32 octet planes [N][Cout/8][voxel][8] (split-precision mode)
-};
-
-template <int K0, int K1, int K2, bool F32OUT>
-__global__ __launch_bounds__(256) void k_conv_first(FirstArgs p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x;
-    const int n = blockIdx.z;
-    const int cout0 = blockIdx.y * 32;
-    int bt = blockIdx.x;
-    const int tz = bt % p.t2;
-    bt /= p.t2;
-    const int ty = bt % p.t1;
-    const int tx = bt / p.t1;
-    constexpr int h0 = FT0 + K0 - 1, h1 = FT1 + K1 - 1, h2 = FT2 + K2 - 1;
-    constexpr int HV = h0 * h1 * h2;
-    constexpr int taps = K0 * K1 * K2;
-    float* lds_w = (float*)smem;                // [Cin][taps][32]
-    float* lds_in = lds_w + p.Cin * taps * 32;  // [Cin][HV]
-    float* lds_red = lds_in + ((p.Cin * HV + 3) & ~3);
-    for (int i = tid; i < p.Cin * taps * 32; i += 256) lds_w[i] = p.w[(size_t)(i >> 5) * p.Cout + cout0 + (i & 31)];
-    {
-        // halo tile from the padded buffer: always in bounds, compile-time index arithmetic, 4 loads in flight
-        const size_t pvol = (size_t)p.PX * p.PY * p.PZ;
-        const float* src = p.padded + (size_t)n * p.Cin * pvol;
-        const int total = p.Cin * HV;
-        for (int i0 = tid; i0 < total; i0 += 256 * 4) {
-            float v[4];
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const int i = min(i0 + b * 256, total - 1);
-                const int ci = i / HV, r = i % HV;
-                const int hz = r % h2, hy = (r / h2) % h1, hx = r / (h2 * h1);
-                v[b] = src[(size_t)ci * pvol + ((size_t)(tx * FT0 + hx) * p.PY + (ty * FT1 + hy)) * p.PZ + tz * FT2 + hz];
-            }
-#pragma unroll
-            for (int b = 0; b < 4; ++b) lds_in[min(i0 + b * 256, total - 1)] = v[b];
-        }
-    }
-    __syncthreads();
-    const int lzq = tid % (FT2 / FV);
-    const int ly = (tid / (FT2 / FV)) % FT1;
-    const int lx = tid / ((FT2 / FV) * FT1);
-    const int lz = lzq * FV;
-    const int ox = tx * FT0 + lx, oy = ty * FT1 + ly, oz = tz * FT2 + lz;
-    float acc[FV][32];
-#pragma unroll
-    for (int c = 0; c < 32; ++c) {
-        const float b = p.bias[cout0 + c];
-#pragma unroll
-        for (int v = 0; v < FV; ++v) acc[v][c] = b;
-    }
-    // The weight reads are wave-uniform; hipcc would scalarise all 27 x 32 of them (v_readfirstlane into SGPRs,
-    // ~2700 SGPR spills, occupancy 1).  A lane-opaque zero keeps them as plain broadcast LDS reads.
-    int lane_zero = 0;
-    asm volatile("" : "+v"(lane_zero));
-    for (int ci = 0; ci < p.Cin; ++ci) {
-        for (int dx = 0; dx < K0; ++dx)
-            for (int dy = 0; dy < K1; ++dy) {
-                const float* row = lds_in + ci * HV + ((lx + dx) * h1 + (ly + dy)) * h2 + lz;
-                float xin[FV + K2 - 1];
-#pragma unroll
-                for (int j = 0; j < FV + K2 - 1; ++j) xin[j] = row[j];
-                const float* wrow = lds_w + ((ci * taps) + (dx * K1 + dy) * K2) * 32 + lane_zero;
-#pragma unroll
-                for (int dz = 0; dz < K2; ++dz) {
-#pragma unroll
-                    for (int c4 = 0; c4 < 8; ++c4) {
-                        const float4 w4 = *(const float4*)(wrow + dz * 32 + c4 * 4);  // broadcast read
-#pragma unroll
-                        for (int v = 0; v < FV; ++v) {
-                            acc[v][c4 * 4 + 0] = __builtin_fmaf(xin[v + dz], w4.x, acc[v][c4 * 4 + 0]);
-                            acc[v][c4 * 4 + 1] = __builtin_fmaf(xin[v + dz], w4.y, acc[v][c4 * 4 + 1]);
-                            acc[v][c4 * 4 + 2] = __builtin_fmaf(xin[v + dz], w4.z, acc[v][c4 * 4 + 2]);
-                            acc[v][c4 * 4 + 3] = __builtin_fmaf(xin[v + dz], w4.w, acc[v][c4 * 4 + 3]);
-                        }
-                    }
-                }
-            }
-    }
-    float s[32], q[32];
-#pragma unroll
-    for (int c = 0; c < 32; ++c) s[c] = q[c] = 0.f;
-#pragma unroll
-    for (int v = 0; v < FV; ++v) {
-        if (F32OUT && ox < p.P0 && oy < p.P1 && oz + v < p.P2) {
-            // split-precision mode: the fp32 sums are stored as they are (statistics of the stored values)
-            const size_t pvox = (size_t)p.P0 * p.P1 * p.P2;
-            float* op = p.out32 + ((size_t)n * p.Cout + cout0) * pvox + ((((size_t)ox) * p.P1 + oy) * (size_t)p.P2 + (oz + v)) * 8;
-#pragma unroll
-            for (int c = 0; c < 32; ++c) {
-                s[c] += acc[v][c];
-                q[c] = __builtin_fmaf(acc[v][c], acc[v][c], q[c]);
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                *(float4*)(op + (size_t)(j >> 1) * 8 * pvox + 4 * (j & 1)) = make_float4(acc[v][4 * j], acc[v][4 * j + 1], acc[v][4 * j + 2], acc[v][4 * j + 3]);
-        } else if (!F32OUT && ox < p.P0 && oy < p.P1 && oz + v < p.P2) {
-            const size_t pvox = (size_t)p.P0 * p.P1 * p.P2;
-            __half* op = p.out + ((size_t)n * p.Cout + cout0) * pvox + ((((size_t)ox) * p.P1 + oy) * (size_t)p.P2 + (oz + v)) * 16;
-            union {
-                uint4 u[4];
-                __half h[32];
-            } pk;
-#pragma unroll
-            for (int c = 0; c < 32; ++c) {
-                __half hv = __float2half_rn(acc[v][c]);
-                pk.h[c] = hv;
-                float vr = __half2float(hv);
-                s[c] += vr;
-                q[c] = __builtin_fmaf(vr, vr, q[c]);
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) *(uint4*)(op + (size_t)(j >> 1) * 16 * pvox + 8 * (j & 1)) = pk.u[j];  // chunk-planar
-        }
-    }
-    // recursive-halving reduction over the wave: after step m a lane keeps half of its channels, summed with its
-    // partner's copy; 16 + 8 + ... shuffles per quantity instead of 6 x 32.  Lane l ends up owning channel
-    // 16*b0 + 8*b1 + 4*b2 + 2*b3 + b4 (b_i = bit i of the lane id).
-    const int lane_ = tid & 63;
-#define HALVE_STEP(M, HALF)                                                                  \
-    {                                                                                        \
-        const bool up = (lane_ & (M)) != 0;                                                  \
-        _Pragma("unroll") for (int i = 0; i < (HALF); ++i) {                                 \
-            const float ks = up ? s[i + (HALF)] : s[i], ss_ = up ? s[i] : s[i + (HALF)];     \
-            const float kq = up ? q[i + (HALF)] : q[i], sq_ = up ? q[i] : q[i + (HALF)];     \
-            s[i] = ks + __shfl_xor(ss_, (M));                                                \
-            q[i] = kq + __shfl_xor(sq_, (M));                                                \
-        }                                                                                    \
-    }
-    HALVE_STEP(1, 16)
-    HALVE_STEP(2, 8)
-    HALVE_STEP(4, 4)
-    HALVE_STEP(8, 2)
-    HALVE_STEP(16, 1)
-#undef HALVE_STEP
-    s[0] += __shfl_xor(s[0], 32);
-    q[0] += __shfl_xor(q[0], 32);
-    const int wave = tid >> 6;
-    if (lane_ < 32) {
-        const int c = ((lane_ & 1) << 4) | ((lane_ & 2) << 2) | (lane_ & 4) | ((lane_ & 8) >> 2) | ((lane_ & 16) >> 4);
-        lds_red[(wave * 32 + c) * 2 + 0] = s[0];
-        lds_red[(wave * 32 + c) * 2 + 1] = q[0];
-    }
-    __syncthreads();
-    if (tid < 64) {
-        int row = tid >> 1, j = tid & 1;
-        float v = lds_red[(0 * 32 + row) * 2 + j] + lds_red[(1 * 32 + row) * 2 + j];
-        v += lds_red[(2 * 32 + row) * 2 + j];
-        v += lds_red[(3 * 32 + row) * 2 + j];
-        p.partials[(((size_t)n * p.Cout + cout0 + row) * 2 + j) * p.nblk + blockIdx.x] = v;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------
-// First conv on the matrix cores (Cin == 1, 3x3x3, Cout == 32): the 27 taps are the K dimension (padded to 32 = two
-// v_mfma_f32_32x32x16_f16 steps).  A = weights [cout][k] in registers for the whole kernel, B = im2col fragment gathered
-// from an fp16 halo tile in LDS (lane (voxel z, k-half) reads its 8 taps with 2-byte LDS loads), D[cout][voxel] goes
-// through the same epilogue as k_conv_ws (bias, fp32 InstanceNorm partial sums, v_permlane32_swap transpose, two 16-byte
-// stores per lane).  864 fp32 FMAs per voxel become 2 MFMAs per 32 voxels: the kernel is bound by the 64 B/voxel store.
-// Persistent blocks walk block tiles of MF0 x MF1 x 32 voxels; M-tile = 32 consecutive z at fixed (x, y).
-#define MF0 4
-#define MF1 8
-#define MF2 32
-
-struct FirstMfmaArgs {
-    const float* padded;  // [N][PX][PY][PZ] fp32, conv padding included
-    int PX, PY, PZ;
-    int N, P0, P1, P2;
-    const float* w;  // [27][32] fp32
-    const float* bias;
-    __half* out;      // [N][P0][P1][P2][32]
-    float* partials;  // [N][32][2][nslots]
-    int nslots;
-    int t0, t1, t2;  // block tiles per axis
-    int vw;          // virtual workgroups per sample
-    // fused tile gather (vol != NULL): the halo is read straight out of the resident volume -- tile origin, pad_nd_image zeros,
-    // conv padding, tile overhang and the test-time flip resolved per element -- instead of from the dense `padded` copy that
-    // k_gather_patches made (one kernel and a 4.3 B / voxel round trip less per batch)
-    const float* vol;
-    const int* origins;  // [N][3]
-    int V0, V1, V2, o0, o1, o2, flip;
-    float* out32;        // X3: fp32 octet planes [N][4][voxel][8]
-    float wscale, winv;  // X3: power-of-two scale of the split weights
-};
-
-// X3 (split-precision mode): the fp32 input is staged as hi / lo fp16 halo tiles, a K step covers 8 taps ([Wh | Wh] x [Xh ; Xl] +
-// [Wl | Wl] x [Xh ; Xl], 4 steps = 8 MFMAs per 32 voxels), the epilogue stores fp32 octet planes (128 B per voxel: the kernel
-// stays store-bound).
-template <bool X3>
-__global__ __launch_bounds__(256) void k_conv_first_mfma(FirstMfmaArgs p) {
-    constexpr int H0 = MF0 + 2, H1 = MF1 + 2, H2 = MF2 + 2, HV = H0 * H1 * H2;
-    __shared__ _Float16 halo[X3 ? 4 : 2][HV + 8];   // [buffer][X3: hi, lo]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, kh = lane >> 5;
-    // A fragments: lane (cout = l31, kh) holds k = 8 kh + i (step 0) and 16 + 8 kh + i (step 1); taps >= 27 are zero
-    f16x8 a0, a1;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int k0 = 8 * kh + i, k1 = 16 + 8 * kh + i;
-        a0[i] = (_Float16)p.w[k0 * 32 + l31];
-        a1[i] = k1 < 27 ? (_Float16)p.w[k1 * 32 + l31] : (_Float16)0.f;
-    }
-    f16x8 xah[X3 ? 4 : 1], xal[X3 ? 4 : 1];
-    if constexpr (X3) {
-#pragma unroll
-        for (int st = 0; st < 4; ++st)
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int k = 8 * st + i;
-                const float wv = k < 27 ? p.w[k * 32 + l31] * p.wscale : 0.f;
-                const _Float16 h = (_Float16)wv;
-                xah[st][i] = h;
-                xal[st][i] = (_Float16)(wv - (float)h);
-            }
-    }
-    // MFMA column (lane l31) <-> voxel lv of the 32-voxel row: even lanes take voxels 0-15, odd lanes 16-31, so that after the
-    // register transpose the lane pair (2m, 2m + 1) can exchange one 16-byte piece and ONE store instruction writes the complete
-    // 32-byte records of voxels 0-15 (the next one 16-31): whole 64-byte lines per instruction in this write-bound kernel
-    // (column = voxel made every instruction write bytes [0, 16) or [16, 32) of all 32 records)
-    const int lv = X3 ? l31 : (l31 >> 1) + ((l31 & 1) << 4);   // (X3: column = voxel, 16-byte stores of a half-wave are 1 KiB contiguous)
-    const bool odd = (l31 & 1) != 0;
-    // LDS offsets (in halves) of this lane's 16 taps relative to the M-tile's first halo voxel
-    int toff[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        int t = (i < 8 ? 8 * kh + i : 16 + 8 * kh + (i - 8));
-        t = t < 27 ? t : 26;  // padded taps: any finite value (their weights are zero)
-        toff[i] = ((t / 9) * H1 + (t / 3) % 3) * H2 + t % 3 + lv;
-    }
-    int xoff[X3 ? 32 : 1];   // X3: taps 8 st + i for both k-halves (the k-half selects the hi / lo tile)
-    if constexpr (X3) {
-#pragma unroll
-        for (int i = 0; i < 32; ++i) {
-            const int t = i < 27 ? i : 26;
-            xoff[i] = ((t / 9) * H1 + (t / 3) % 3) * H2 + t % 3 + lv;
-        }
-    }
-    float4 bq[4];
-#pragma unroll
-    for (int gq = 0; gq < 4; ++gq) bq[gq] = *(const float4*)(p.bias + 8 * gq + 4 * kh);
-    float st_s[16], st_q[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) st_s[i] = st_q[i] = 0.f;
-    int st_n = -1;
-    auto flush = [&](int slot) {
-        if (st_n < 0) return;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-#pragma unroll
-            for (int mm = 1; mm < 32; mm <<= 1) {
-                st_s[i] += __shfl_xor(st_s[i], mm);
-                st_q[i] += __shfl_xor(st_q[i], mm);
-            }
-        }
-        if (l31 == 0) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int row = 8 * (i >> 2) + 4 * kh + (i & 3);
-                float* pp = p.partials + (((size_t)st_n * 32 + row) * 2) * p.nslots + slot;
-                pp[0] = st_s[i];
-                pp[p.nslots] = st_q[i];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 16; ++i) st_s[i] = st_q[i] = 0.f;
-    };
-    const int nsp = p.t0 * p.t1 * p.t2;
-    const size_t pvol = (size_t)p.PX * p.PY * p.PZ, ovox = (size_t)p.P0 * p.P1 * p.P2;
-    // Tile sequence: the spatial tiles of ONE sample are dealt out to vw = min(nsp, CUs) virtual workgroups (j takes
-    // sp = j, j + vw, ...), whose partial sums go to statistics slot 4 j + wave of that sample -- a function of the sample
-    // alone, not of the batch it shares the launch with (batch-invariant results, as in k_conv_ws).  Physical workgroup b
-    // executes the virtual workgroups b, b + G, ...
-    const int vw = p.vw, nvirt = p.N * vw;
-    struct Seq {
-        int v, n, j, sp;
-    };
-    auto seq_valid = [&](const Seq& q) { return q.v < nvirt; };
-    auto seq_first = [&]() {
-        Seq q;
-        q.v = (int)blockIdx.x;
-        q.n = q.v / vw;
-        q.j = q.v - q.n * vw;
-        q.sp = q.j;
-        return q;
-    };
-    auto seq_next = [&](Seq q) {
-        q.sp += vw;
-        if (q.sp >= nsp) {
-            q.v += (int)gridDim.x;
-            q.n = q.v / vw;
-            q.j = q.v - q.n * vw;
-            q.sp = q.j;
-        }
-        return q;
-    };
-    // halo staging is split in two halves so that the global round trip of the NEXT tile overlaps this tile's compute:
-    // fetch() issues the loads into registers, commit() converts and writes them to the other LDS buffer afterwards
-    constexpr int NPRE = (HV + 255) / 256;
-    float pre[NPRE];
-    // this thread's halo voxels (tile independent): packed coordinates x | y << 8 | z << 16 and the voxel's linear offset in the
-    // volume relative to the halo origin -- the per-tile gather is then three range tests and one add per element (the first
-    // version decomposed the index and rebuilt a 64-bit address per element and tile: ~80 instructions each, as much as the
-    // tile's MFMA + epilogue work)
-    int hc[NPRE], hrel[NPRE];
-#pragma unroll
-    for (int j = 0; j < NPRE; ++j) {
-        const int i = min(tid + 256 * j, HV - 1);
-        const int z = i % H2, r = i / H2, y = r % H1, x = r / H1;
-        hc[j] = x | (y << 8) | (z << 16);
-        hrel[j] = (x * p.V1 + y) * p.V2 + z;
-    }
-    auto fetch = [&](const Seq& q) {
-        int sp = q.sp;
-        const int tz = sp % p.t2;
-        sp /= p.t2;
-        const int ty = sp % p.t1, tx = sp / p.t1;
-        if (p.vol && p.flip == 0) {
-            // halo origin in patch coordinates (conv padding 1) and in the volume; valid halo range per axis: inside the patch
-            // (conv / tile padding reads zero) and inside the volume (pad_nd_image zeros)
-            const int bx = tx * MF0 - 1, by = ty * MF1 - 1, bz = tz * MF2 - 1;
-            const int ox = p.origins[q.n * 3 + 0] - p.o0 + bx, oy = p.origins[q.n * 3 + 1] - p.o1 + by, oz = p.origins[q.n * 3 + 2] - p.o2 + bz;
-            const int xl = max(-bx, -ox), xh = min(p.P0 - bx, p.V0 - ox);      // halo x valid iff xl <= x < xh
-            const int yl = max(-by, -oy), yh = min(p.P1 - by, p.V1 - oy);
-            const int zl = max(-bz, -oz), zh = min(p.P2 - bz, p.V2 - oz);
-            const float* base = p.vol + ((ptrdiff_t)ox * p.V1 + oy) * p.V2 + oz;
-#pragma unroll
-            for (int j = 0; j < NPRE; ++j) {
-                const int x = hc[j] & 255, y = (hc[j] >> 8) & 255, z = hc[j] >> 16;
-                const bool ok = (unsigned)(x - xl) < (unsigned)max(xh - xl, 0) && (unsigned)(y - yl) < (unsigned)max(yh - yl, 0) &&
-                                (unsigned)(z - zl) < (unsigned)max(zh - zl, 0);
-                pre[j] = ok ? base[hrel[j]] : 0.f;
-            }
-            return;
-        }
-        if (p.vol) {
-            // patch coordinates of the halo origin (conv padding 1) and the tile's position in the volume
-            const int bx = tx * MF0 - 1, by = ty * MF1 - 1, bz = tz * MF2 - 1;
-            const int ox = p.origins[q.n * 3 + 0] - p.o0, oy = p.origins[q.n * 3 + 1] - p.o1, oz = p.origins[q.n * 3 + 2] - p.o2;
-#pragma unroll
-            for (int j = 0; j < NPRE; ++j) {
-                const int i = min(tid + 256 * j, HV - 1);
-                const int z = i % H2, r = i / H2, y = r % H1, x = r / H1;
-                const int px = bx + x, py = by + y, pz = bz + z;
-                float v = 0.f;
-                if ((unsigned)px < (unsigned)p.P0 && (unsigned)py < (unsigned)p.P1 && (unsigned)pz < (unsigned)p.P2) {
-                    // test-time mirroring (predict_from_raw_data.py:541-557): the network sees torch.flip(tile, axes)
-                    const int qx = (p.flip & 1) ? p.P0 - 1 - px : px, qy = (p.flip & 2) ? p.P1 - 1 - py : py,
-                              qz = (p.flip & 4) ? p.P2 - 1 - pz : pz;
-                    const int vx = ox + qx, vy = oy + qy, vz = oz + qz;
-                    if ((unsigned)vx < (unsigned)p.V0 && (unsigned)vy < (unsigned)p.V1 && (unsigned)vz < (unsigned)p.V2)
-                        v = p.vol[((size_t)vx * p.V1 + vy) * p.V2 + vz];
-                }
-                pre[j] = v;
-            }
-            return;
-        }
-        const float* src = p.padded + (size_t)q.n * pvol + ((size_t)(tx * MF0) * p.PY + ty * MF1) * p.PZ + tz * MF2;
-#pragma unroll
-        for (int j = 0; j < NPRE; ++j) {
-            const int i = min(tid + 256 * j, HV - 1);
-            const int z = i % H2, r = i / H2, y = r % H1, x = r / H1;
-            pre[j] = src[((size_t)x * p.PY + y) * p.PZ + z];
-        }
-    };
-    auto commit = [&](int buf) {
-#pragma unroll
-        for (int j = 0; j < NPRE; ++j) {
-            const int i = tid + 256 * j;
-            if constexpr (X3) {
-                if (i < HV) {
-                    const _Float16 h = (_Float16)pre[j];
-                    halo[2 * buf][i] = h;
-                    halo[2 * buf + 1][i] = (_Float16)(pre[j] - (float)h);
-                }
-            } else {
-                if (i < HV) halo[buf][i] = (_Float16)pre[j];
-            }
-        }
-    };
-    Seq cur = seq_first();
-    if (seq_valid(cur)) {
-        fetch(cur);
-        commit(0);
-    }
-    __syncthreads();
-    int st_v = -1, slot = 0;
-    for (int it = 0; seq_valid(cur); ++it) {
-        const int buf = it & 1;
-        const Seq nxt = seq_next(cur);
-        const bool more = seq_valid(nxt);
-        if (more) fetch(nxt);
-        const int n = cur.n;
-        int sp = cur.sp;
-        const int tz = sp % p.t2;
-        sp /= p.t2;
-        const int ty = sp % p.t1, tx = sp / p.t1;
-        if (cur.v != st_v) {
-            flush(slot);
-            st_v = cur.v;
-            st_n = n;
-            slot = cur.j * 4 + wave;
-        }
-        const _Float16* hb = X3 ? halo[2 * buf + kh] : halo[buf];
-#pragma unroll 2
-        for (int r = 0; r < (MF0 * MF1) / 4; ++r) {
-            const int row = wave * ((MF0 * MF1) / 4) + r;  // (x, y) row of the block tile
-            const int x = row / MF1, y = row % MF1;
-            const _Float16* hr = hb + (x * H1 + y) * H2;
-            const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            f32x16 acc;
-            if constexpr (X3) {
-                acc = zero;
-#pragma unroll
-                for (int st = 0; st < 4; ++st) {
-                    f16x8 b;
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) b[i] = hr[xoff[8 * st + i]];
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(xah[st], b, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(xal[st], b, acc, 0, 0, 0);
-                }
-            } else {
-                f16x8 b0, b1;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    b0[i] = hr[toff[i]];
-                    b1[i] = hr[toff[8 + i]];
-                }
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0, zero, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b1, acc, 0, 0, 0);
-            }
-            float v[16];
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                v[gq * 4 + 0] = (X3 ? acc[gq * 4 + 0] * p.winv : acc[gq * 4 + 0]) + bq[gq].x;
-                v[gq * 4 + 1] = (X3 ? acc[gq * 4 + 1] * p.winv : acc[gq * 4 + 1]) + bq[gq].y;
-                v[gq * 4 + 2] = (X3 ? acc[gq * 4 + 2] * p.winv : acc[gq * 4 + 2]) + bq[gq].z;
-                v[gq * 4 + 3] = (X3 ? acc[gq * 4 + 3] * p.winv : acc[gq * 4 + 3]) + bq[gq].w;
-            }
-            // packed fp32 statistics (v_pk_add_f32 / v_pk_fma_f32: the same operations per entry, two entries per instruction)
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                typedef float cf2 __attribute__((ext_vector_type(2)));
-                const cf2 vv = cf2{v[2 * i], v[2 * i + 1]};
-                cf2 s2 = cf2{st_s[2 * i], st_s[2 * i + 1]}, q2 = cf2{st_q[2 * i], st_q[2 * i + 1]};
-                s2 = s2 + vv;
-                q2 = __builtin_elementwise_fma(vv, vv, q2);
-                st_s[2 * i] = s2.x; st_s[2 * i + 1] = s2.y;
-                st_q[2 * i] = q2.x; st_q[2 * i + 1] = q2.y;
-            }
-            if constexpr (X3) {
-                // fp32 octet planes [N][4][voxel][8]: entries 4 gq .. + 3 = couts 8 gq + 4 kh .. + 3 of voxel l31
-                float* dst32 = p.out32 + ((size_t)n * 32 * ovox + (((size_t)(tx * MF0 + x) * p.P1 + ty * MF1 + y) * p.P2 + tz * MF2 + l31) * 8) + 4 * kh;
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq) *(float4*)(dst32 + (size_t)gq * 8 * ovox) = make_float4(v[4 * gq], v[4 * gq + 1], v[4 * gq + 2], v[4 * gq + 3]);
-                continue;
-            }
-            unsigned w8[8];
-#pragma unroll
-            for (int pr = 0; pr < 2; ++pr) {
-                float lo4[4], hi4[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[pr * 4 + e]), __float_as_uint(v[(pr + 2) * 4 + e]), false, false);
-                    lo4[e] = __uint_as_float(sw[0]);
-                    hi4[e] = __uint_as_float(sw[1]);
-                }
-                // one v_cvt_pk_f16_f32 (RTNE, same rounding as __float2half_rn) per output word
-                typedef float cvf2 __attribute__((ext_vector_type(2)));
-                typedef _Float16 cvh2 __attribute__((ext_vector_type(2)));
-                auto pk = [](float a, float b) {
-                    union {
-                        cvh2 v;
-                        unsigned u;
-                    } c;
-                    c.v = __builtin_convertvector(cvf2{a, b}, cvh2);
-                    return c.u;
-                };
-                w8[pr * 4 + 0] = pk(lo4[0], lo4[1]);
-                w8[pr * 4 + 1] = pk(lo4[2], lo4[3]);
-                w8[pr * 4 + 2] = pk(hi4[0], hi4[1]);
-                w8[pr * 4 + 3] = pk(hi4[2], hi4[3]);
-            }
-            // chunk-planar [N][2][voxel][16]: lane pair (2m, 2m + 1) of plane kh writes voxel m's record, then voxel 16 + m's
-            unsigned wa[4], wb[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const unsigned n0 = (unsigned)__builtin_amdgcn_mov_dpp((int)w8[i], 0xB1, 0xF, 0xF, true);       // neighbour's piece 0
-                const unsigned n1 = (unsigned)__builtin_amdgcn_mov_dpp((int)w8[4 + i], 0xB1, 0xF, 0xF, true);   // neighbour's piece 1
-                wa[i] = odd ? n1 : w8[i];
-                wb[i] = odd ? w8[4 + i] : n0;
-            }
-            __half* dst = p.out + ((size_t)(n * 2 + kh) * ovox + ((size_t)(tx * MF0 + x) * p.P1 + ty * MF1 + y) * p.P2 + tz * MF2 + (l31 >> 1)) * 16 + (odd ? 8 : 0);
-            // (streaming `nt` stores were measured: 0 ... -10 %)
-            *(uint4*)dst = make_uint4(wa[0], wa[1], wa[2], wa[3]);
-            *(uint4*)(dst + 16 * 16) = make_uint4(wb[0], wb[1], wb[2], wb[3]);
-        }
-        if (more) commit(buf ^ 1);
-        __syncthreads();
-        cur = nxt;
-    }
-    flush(slot);
-}
-
-bool first_mfma_ok(int Cin, const int P[3], const int k[3], int Cout) {
-    return Cin == 1 && Cout == 32 && k[0] == 3 && k[1] == 3 && k[2] == 3 && P[0] % MF0 == 0 && P[1] % MF1 == 0 && P[2] % MF2 == 0;
-}
-
-int conv_first_nblk(const int P[3], int cu_count) {
-    return std::max(ceil_div(P[0], FT0) * ceil_div(P[1], FT1) * ceil_div(P[2], FT2), cu_count * 4);
-}
-
-// dims of the zero-padded gather buffer for a patch P and kernel k
-void conv_first_padded_dims(const int P[3], const int k[3], int out[3]) {
-    const int ft[3] = {FT0, FT1, FT2};
-    for (int a = 0; a < 3; ++a) out[a] = ceil_div(P[a], ft[a]) * ft[a] + (k[a] - 1);
-}
-
-int launch_conv_first(boa_ctx* ctx, const float* volume, const int V[3], const int vol_off[3], const int* dev_origins,
-                      int N, int Cin, const int P[3], const int k[3], int Cout, const float* w, const float* bias,
-                      float* padded_scratch, __half* out, float* partials, int* nblk_out, int flip_mask, float* out32) {
-    BOA_REQUIRE(Cout % 32 == 0, "first conv: Cout=%d must be a multiple of 32", Cout);
-    BOA_REQUIRE(Cin >= 1 && Cin <= 4, "first conv: Cin=%d unsupported (1..4)", Cin);
-    const bool k333 = k[0] == 3 && k[1] == 3 && k[2] == 3, k133 = k[0] == 1 && k[1] == 3 && k[2] == 3;
-    BOA_REQUIRE(k333 || k133, "first conv: kernel %dx%dx%d not instantiated", k[0], k[1], k[2]);
-    int PD[3];
-    conv_first_padded_dims(P, k, PD);
-    const size_t pvol = (size_t)PD[0] * PD[1] * PD[2];
-    const double vox = (double)N * P[0] * P[1] * P[2];
-    KernelTimer tm(ctx, BOA_K_CONV_FIRST, 2.0 * vox * k[0] * k[1] * k[2] * Cin * Cout, vox * (4.0 * Cin + 2.0 * Cout));
-    const int nblk_tab = conv_first_nblk(P, ctx->cu_count);
-    if (nblk_out) *nblk_out = nblk_tab;
-    if (first_mfma_ok(Cin, P, k, Cout)) {
-        FirstMfmaArgs m;
-        m.out32 = out32;
-        m.wscale = X3_HEAD_WSCALE;   // (first-conv weights are O(0.1 .. 1) like the head's: one fixed power of two)
-        m.winv = 1.0f / X3_HEAD_WSCALE;
-        m.padded = padded_scratch; m.PX = PD[0]; m.PY = PD[1]; m.PZ = PD[2];
-        m.vol = volume; m.origins = dev_origins; m.flip = flip_mask;
-        m.V0 = V[0]; m.V1 = V[1]; m.V2 = V[2];
-        m.o0 = vol_off ? vol_off[0] : 0; m.o1 = vol_off ? vol_off[1] : 0; m.o2 = vol_off ? vol_off[2] : 0;
-        m.N = N; m.P0 = P[0]; m.P1 = P[1]; m.P2 = P[2];
-        m.w = w; m.bias = bias; m.out = out; m.partials = partials; m.nslots = nblk_tab;
-        m.t0 = P[0] / MF0; m.t1 = P[1] / MF1; m.t2 = P[2] / MF2;
-        m.vw = std::min(m.t0 * m.t1 * m.t2, ctx->cu_count);
-        // (physical workgroup b runs the virtual workgroups b, b + G, ...: any G gives the same results; more than one workgroup
-        //  per CU hides the halo gather's and the stores' latency -- the kernel is a 3.4 GB write per 25 tiles)
-        const dim3 fgrid((unsigned)std::min<long long>((long long)m.vw * N, (long long)ctx->cu_count * 4));
-        if (out32) {
-            hipLaunchKernelGGL(k_conv_first_mfma<true>, fgrid, dim3(256), 0, ctx->stream, m);
-            ctx->counters[BOA_CNT_X3]++;
-        } else {
-            hipLaunchKernelGGL(k_conv_first_mfma<false>, fgrid, dim3(256), 0, ctx->stream, m);
-            ctx->counters[BOA_CNT_FIRST_MFMA]++;
-        }
-        tm.stop();
-        BOA_HIP_TRY(hipGetLastError());
-        return BOA_OK;
-    }
-    // (the MFMA kernel gathers its halo from the volume itself; the VALU kernel reads a zero-padded copy)
-    hipLaunchKernelGGL(k_gather_patches, dim3((unsigned)((pvol + 255) / 256), Cin, N), dim3(256), 0, ctx->stream, volume,
-                       dev_origins, V[0], V[1], V[2], vol_off ? vol_off[0] : 0, vol_off ? vol_off[1] : 0,
-                       vol_off ? vol_off[2] : 0, Cin, P[0], P[1], P[2], (k[0] - 1) / 2, (k[1] - 1) / 2, (k[2] - 1) / 2, PD[0],
-                       PD[1], PD[2], flip_mask, padded_scratch);
-    FirstArgs a;
-    a.nblk = nblk_tab;
-    a.padded = padded_scratch; a.PX = PD[0]; a.PY = PD[1]; a.PZ = PD[2];
-    a.N = N; a.Cin = Cin; a.P0 = P[0]; a.P1 = P[1]; a.P2 = P[2]; a.Cout = Cout;
-    a.w = w; a.bias = bias; a.out = out; a.partials = partials; a.out32 = out32;
-    a.t0 = ceil_div(P[0], FT0); a.t1 = ceil_div(P[1], FT1); a.t2 = ceil_div(P[2], FT2);
-    const int nblk = a.t0 * a.t1 * a.t2;
-    const int HV = (FT0 + k[0] - 1) * (FT1 + k[1] - 1) * (FT2 + k[2] - 1);
-    const size_t lds = ((size_t)Cin * k[0] * k[1] * k[2] * 32 + (((size_t)Cin * HV + 3) & ~(size_t)3)) * 4 + 1024;
-    if (out32) {
-        if (k333)
-            hipLaunchKernelGGL((k_conv_first<3, 3, 3, true>), dim3(nblk, Cout / 32, N), dim3(256), lds, ctx->stream, a);
-        else
-            hipLaunchKernelGGL((k_conv_first<1, 3, 3, true>), dim3(nblk, Cout / 32, N), dim3(256), lds, ctx->stream, a);
-        ctx->counters[BOA_CNT_X3]++;
-    } else {
-        if (k333)
-            hipLaunchKernelGGL((k_conv_first<3, 3, 3, false>), dim3(nblk, Cout / 32, N), dim3(256), lds, ctx->stream, a);
-        else
-            hipLaunchKernelGGL((k_conv_first<1, 3, 3, false>), dim3(nblk, Cout / 32, N), dim3(256), lds, ctx->stream, a);
-        ctx->counters[BOA_CNT_FIRST_VALU]++;
-    }
-    tm.stop();
-    BOA_HIP_TRY(hipGetLastError());
-    return BOA_OK;
 }
 
 // ======================================================================================================
@@ -1231,905 +591,6 @@ int launch_norm_finalize(boa_ctx* ctx, float* partials, int nblk, int N, int C, 
     else
         hipLaunchKernelGGL(k_norm_finalize<256>, dim3(C, N), dim3(256), 0, ctx->stream, partials, nblk, C, count, clear, gamma,
                            beta, eps, ss_out, (unsigned short*)ss16_out);
-    tm.stop();
-    BOA_HIP_TRY(hipGetLastError());
-    return BOA_OK;
-}
-
-// ======================================================================================================
-// transposed conv, kernel == stride: out[o] = sum_ci y[o / s][ci] * W[ci][co][o % s] + b
-// ---- the transposed convs' per-wave LDS slab (D fragments -> 16-byte pieces of the output voxels' records) -------------------------
-// Logical layout [plane][output voxel ov = l31 * TZ + t][16 couts]: lane (l31, kh) writes the 8-byte piece q = 2 (gq & 1) + kh of its
-// voxel's 32-byte record, the wave then reads 16-byte pieces `lane + 64 k` and stores 1 KiB runs.  With TZ = 2 the writing lanes sit
-// 64 bytes apart: every 16-lane group of the ds_write_b64 fell on two banks' worth of one 128-byte row -- 8-way conflicts, 72 - 76 % of
-// the kernels' LDS cycles (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE, profiles/r05_pmc_lds.txt).  Physical layout for TZ = 2: record
-// (t, l31) at t * 32 + (l31 ^ 4 t) (lanes 32 bytes apart; the xor keeps the two taps of a voxel pair off the same bank row for the
-// reads), piece q at q ^ ((l31 >> 2) & 3) (the four lanes of a group that share a 32-byte window take its four pieces): writes and
-// reads are conflict-free; a reader whose record has an odd swizzle finds the two 8-byte pieces of its half swapped and swaps them back.
-template <int TZ>
-__device__ __forceinline__ int convt_slab_waddr(int gq, int l31, int t, int kh) {
-    if constexpr (TZ == 2) {
-        const int rec = t * 32 + (l31 ^ (4 * t));
-        const int q = ((gq & 1) * 2 + kh) ^ ((l31 >> 2) & 3);
-        return ((gq >> 1) * 64 + rec) * 32 + q * 8;
-    } else {
-        return ((gq >> 1) * 32 * TZ + l31 * TZ + t) * 32 + (8 * (gq & 1) + 4 * kh) * 2;
-    }
-}
-template <int TZ>
-__device__ __forceinline__ uint4 convt_slab_read(const unsigned char* slab, int pl, int piece) {
-    if constexpr (TZ == 2) {
-        const int ov = piece >> 1, h = piece & 1;
-        const int j = ov >> 1, tz = ov & 1;
-        const int sw = (j >> 2) & 3;
-        const uint4 d = *(const uint4*)(slab + (pl * 64 + tz * 32 + (j ^ (4 * tz))) * 32 + (h ^ (sw >> 1)) * 16);
-        return (sw & 1) ? make_uint4(d.z, d.w, d.x, d.y) : d;
-    } else {
-        return *(const uint4*)(slab + pl * 32 * TZ * 32 + piece * 16);
-    }
-}
-
-struct ConvTArgs {
-    const __half* src;
-    const float* ss;
-    const unsigned* ss16;  // packed fp16 (scale, shift) pairs of the input's deferred norm (preferred), or NULL
-    int Cin, Cout, N, Di, Hi, Wi, s0, s1, s2;
-    const __half* wpk;  // [tap][Cin/16][2][Cout][8]
-    const float* bias;
-    __half* out;
-    float slope;
-};
-
-// One wave = 32 consecutive (flattened) input voxels.  Per (tx, ty, cout chunk) it computes BOTH z taps (TZ = s2
-// accumulators): in the chunk-planar output the voxels 2 iz and 2 iz + 1 of a row are neighbours, so the wave's result for
-// one 16-cout plane is one run of 2 KiB (TZ = 2) of consecutive bytes.  The D fragments go through a per-wave LDS slab
-// [2 planes][32 TZ voxels][16 couts] and leave as 16-byte pieces, lane L taking pieces L, L + 64, ...: every store
-// instruction writes 1 KiB of consecutive bytes (the one-tap-per-pass form wrote 32-byte pieces 64 bytes apart).
-typedef _Float16 ct_h2 __attribute__((ext_vector_type(2)));
-
-// deferred InstanceNorm + LeakyReLU on 8 channels in packed fp16 (the same one-rounding evaluation as k_conv_ws's producers):
-// w = 4 x {packed scales, packed shifts} of the four channel pairs
-__device__ __forceinline__ uint4 convt_norm_act8_pk(uint4 raw, const uint4& w0, const uint4& w1, unsigned slope2) {
-    union {
-        uint4 u;
-        ct_h2 v[4];
-    } x;
-    union {
-        unsigned u;
-        ct_h2 v;
-    } s, t, sl;
-    const unsigned w[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
-    x.u = raw;
-    sl.u = slope2;
-    ct_h2 y[4], z[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        s.u = w[2 * i];
-        t.u = w[2 * i + 1];
-        y[i] = __builtin_elementwise_fma(x.v[i], s.v, t.v);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) z[i] = y[i] * sl.v;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) x.v[i] = __builtin_elementwise_max(y[i], z[i]);
-    return x.u;
-}
-
-template <int TZ>
-__global__ __launch_bounds__(256) void k_convt_mfma(ConvTArgs p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int l31 = lane & 31;
-    const int kh = lane >> 5;
-    const int ncc = p.Cin / 16;
-    // (32-bit index arithmetic: N * in_vox < 2^31, checked on the host -- the 64-bit divisions of the first version were
-    //  ~40 % of the kernel's instructions; the kernel is instruction-bound: with every memory access switched off it still
-    //  took half of its time)
-    const unsigned in_vox = (unsigned)(p.Di * p.Hi * p.Wi);
-    const unsigned total = (unsigned)p.N * in_vox;
-    constexpr int SLAB = 2 * 32 * TZ * 32;  // bytes: [2 planes][32 * TZ output voxels][16 halves]
-    unsigned char* lds = smem + (size_t)wave * (ncc * 1024 + SLAB);  // [cc][khalf][32 voxels][8 halves] + slab
-    unsigned char* slab = lds + ncc * 1024;
-    const unsigned g0 = ((unsigned)blockIdx.x * 4 + wave) * 32;  // first flattened (n, voxel) of this wave
-    const unsigned g = g0 + l31;
-    const bool valid = g < total;
-    const unsigned n = valid ? g / in_vox : 0;
-    const unsigned vi = valid ? g - n * in_vox : 0;
-    // stage this wave's 32 voxels: lane (l31, kh) moves octet kh of every 16-channel chunk; loads batched by 4
-    {
-        union {
-            unsigned u;
-            ct_h2 v;
-        } sl2;
-        sl2.v = ct_h2{(_Float16)p.slope, (_Float16)p.slope};
-        const __half* src_l = p.src + ((size_t)n * ncc * in_vox + vi) * 16 + kh * 8;   // + cc * in_vox * 16 per chunk
-        const unsigned* ss16_l = p.ss16 ? p.ss16 + ((size_t)n * p.Cin + kh * 8) : nullptr;  // + cc * 16 words per chunk
-        for (int c0 = 0; c0 < ncc; c0 += 4) {
-            uint4 val[4], w0[4], w1[4];
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const int cc = min(c0 + b, ncc - 1);
-                val[b] = *(const uint4*)(src_l + (size_t)cc * in_vox * 16);  // chunk-planar
-                if (ss16_l) {
-                    w0[b] = *(const uint4*)(ss16_l + cc * 16);
-                    w1[b] = *(const uint4*)(ss16_l + cc * 16 + 4);
-                }
-            }
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const int cc = min(c0 + b, ncc - 1);
-                uint4 o = val[b];
-                if (ss16_l) {
-                    o = convt_norm_act8_pk(o, w0[b], w1[b], sl2.u);
-                } else if (p.ss) {  // (callers without the packed table: fp32 evaluation)
-                    float sc[8], sh[8];
-                    const float* ss = p.ss + ((size_t)n * p.Cin + cc * 16 + kh * 8) * 2;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        sc[j] = ss[2 * j];
-                        sh[j] = ss[2 * j + 1];
-                    }
-                    o = norm_act8(o, sc, sh, p.slope);
-                }
-                if (!valid) o = make_uint4(0, 0, 0, 0);
-                *(uint4*)(lds + ((cc * 2 + kh) * 32 + l31) * 16) = o;
-            }
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    const int Ho = p.Hi * p.s1, Wo = p.Wi * p.s2;
-    const size_t ovox = (size_t)(p.Di * p.s0) * Ho * Wo;
-    const int nco = p.Cout / 32;
-    const int npairs = p.s0 * p.s1 * nco;  // (tx, ty, cout chunk); every pair covers the TZ z taps
-    // store side: the slab of one plane holds 32 * TZ output voxels = 64 * TZ pieces of 16 bytes; this lane takes pieces
-    // lane + 64 k (k < TZ) of each plane: output voxel ov = piece / 2 -> input voxel j = ov / TZ, z tap ov % TZ.
-    // optr[k]: this lane's piece in plane 0 of the sample at tap (0, 0); a pass adds ((co * 2 + pl) * ovox + toff) * 32 bytes
-    unsigned char* optr[TZ];
-    bool ovalid[TZ];
-#pragma unroll
-    for (int k = 0; k < TZ; ++k) {
-        const int ov = (lane + 64 * k) >> 1;
-        const int j = ov / TZ, tz = ov % TZ;
-        const unsigned gg = g0 + j;
-        ovalid[k] = gg < total;
-        const unsigned nn = ovalid[k] ? gg / in_vox : 0;
-        const unsigned v2 = ovalid[k] ? gg - nn * in_vox : 0;
-        const unsigned r2 = v2 / (unsigned)p.Wi;
-        const int iz = (int)(v2 - r2 * (unsigned)p.Wi);
-        const int ix = (int)(r2 / (unsigned)p.Hi), iy = (int)(r2 - (unsigned)ix * (unsigned)p.Hi);
-        const size_t ospat = ((size_t)(ix * p.s0) * Ho + (size_t)(iy * p.s1)) * Wo + (size_t)(iz * p.s2 + tz);
-        optr[k] = (unsigned char*)p.out + ((size_t)nn * (p.Cout / 16) * ovox + ospat) * 32 + 16 * (lane & 1);
-    }
-    // weights: wave-uniform part of the address per (tap, chunk, cout chunk) + this lane's (kh, cout) offset
-    const unsigned char* wbase = (const unsigned char*)p.wpk;
-    const unsigned wlane = ((unsigned)kh * (unsigned)p.Cout + (unsigned)l31) * 16u;
-    const unsigned wstep_cc = 2u * (unsigned)p.Cout * 16u;  // bytes per (tap, chunk)
-    const unsigned char* bfrag = lds + (kh * 32 + l31) * 16;  // + cc * 1024
-    int bias_co = -1;
-    f32x16 biasv;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) biasv[i] = 0.f;
-    for (int pr = blockIdx.y; pr < npairs; pr += gridDim.y) {
-        const int txy = pr / nco, co = pr - txy * nco;
-        const int ty = txy % p.s1, tx = txy / p.s1;
-        if (co != bias_co) {  // this lane's 16 biases of the cout chunk (entry 4 gq + e <-> cout 8 gq + 4 kh + e)
-            bias_co = co;
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const float4 bq = *(const float4*)(p.bias + co * 32 + 8 * gq + 4 * kh);
-                biasv[gq * 4 + 0] = bq.x; biasv[gq * 4 + 1] = bq.y; biasv[gq * 4 + 2] = bq.z; biasv[gq * 4 + 3] = bq.w;
-            }
-        }
-        f32x16 acc[TZ];
-        const int tap0 = (tx * p.s1 + ty) * p.s2;
-        const unsigned char* wpass = wbase + ((size_t)tap0 * ncc * wstep_cc + (size_t)co * 32 * 16);  // uniform
-        // groups of 4 chunks: the group's TZ x 4 weight fragments are loaded as one batch (the thin deep layers wait on L2 for
-        // them: 8 loads in flight per wave), then 4 x TZ MFMAs.  The very first MFMA takes an inline-zero C operand instead
-        // of zeroed accumulators.
-        const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        auto group = [&](int c0, bool first) {
-            f16x8 a[TZ][4];
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-#pragma unroll
-                for (int t = 0; t < TZ; ++t)
-                    a[t][b] = *(const f16x8*)(wpass + (size_t)(t * ncc + min(c0 + b, ncc - 1)) * wstep_cc + wlane);
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                if (b == 0 || c0 + b < ncc) {  // (wave-uniform)
-                    const f16x8 bf = *(const f16x8*)(bfrag + (c0 + b) * 1024);
-#pragma unroll
-                    for (int t = 0; t < TZ; ++t)
-                        acc[t] = (first && b == 0) ? __builtin_amdgcn_mfma_f32_32x32x16_f16(a[t][b], bf, zero, 0, 0, 0)
-                                                   : __builtin_amdgcn_mfma_f32_32x32x16_f16(a[t][b], bf, acc[t], 0, 0, 0);
-                }
-            }
-        };
-        group(0, true);
-        for (int c0 = 4; c0 < ncc; c0 += 4) group(c0, false);
-        // fp16, into the slab: lane (voxel l31, kh) holds couts 8 gq + 4 kh + e -> plane gq / 2, offset 8 (gq % 2) + 4 kh
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-#pragma unroll
-            for (int t = 0; t < TZ; ++t) {
-                union {
-                    uint2 u;
-                    __half h[4];
-                } pk;
-                pk.h[0] = __float2half_rn(acc[t][gq * 4 + 0] + biasv[gq * 4 + 0]);
-                pk.h[1] = __float2half_rn(acc[t][gq * 4 + 1] + biasv[gq * 4 + 1]);
-                pk.h[2] = __float2half_rn(acc[t][gq * 4 + 2] + biasv[gq * 4 + 2]);
-                pk.h[3] = __float2half_rn(acc[t][gq * 4 + 3] + biasv[gq * 4 + 3]);
-                *(uint2*)(slab + convt_slab_waddr<TZ>(gq, l31, t, kh)) = pk.u;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-        const size_t poff = ((size_t)(co * 2) * ovox + ((size_t)tx * Ho + ty) * Wo) * 32;  // uniform; plane pl adds ovox * 32
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-            for (int k = 0; k < TZ; ++k) {
-                const int piece = lane + 64 * k;
-                const uint4 d = convt_slab_read<TZ>(slab, pl, piece);
-                if (ovalid[k]) *(uint4*)(optr[k] + poff + (size_t)pl * ovox * 32) = d;
-            }
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-
-// Register-weights variant for Cin = 16 NCC <= 128 (the 32^3 -> 64^3 and 64^3 -> 128^3 transposed convs, 75 % of the class's
-// time): a wave covers G groups of 32 input voxels, staged once into its LDS slice, and per (x tap, y tap, cout chunk) pass loads
-// the pass's TZ x NCC weight fragments ONCE into registers for all G groups.  k_convt_mfma re-reads them from L2 for every 32
-// voxels: 1 KiB of weights per input voxel of the 64 -> 32 layer against 640 bytes of activations moved -- the kernel was bound
-// by L2 -> CU weight traffic, not by HBM.  Same arithmetic, same output order.
-template <int TZ, int NCC, int G>
-__global__ __launch_bounds__(256) void k_convt_mfma_rw(ConvTArgs p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int l31 = lane & 31;
-    const int kh = lane >> 5;
-    const unsigned in_vox = (unsigned)(p.Di * p.Hi * p.Wi);
-    const unsigned total = (unsigned)p.N * in_vox;
-    constexpr int SLAB = 2 * 32 * TZ * 32;  // bytes: [2 planes][32 * TZ output voxels][16 halves]
-    unsigned char* lds = smem + (size_t)wave * (G * NCC * 1024 + SLAB);  // [g][cc][khalf][32 voxels][8 halves] + slab
-    unsigned char* slab = lds + G * NCC * 1024;
-    const unsigned g0 = ((unsigned)blockIdx.x * 4 + wave) * (32 * G);  // first flattened (n, voxel) of this wave
-    union {
-        unsigned u;
-        ct_h2 v;
-    } sl2;
-    sl2.v = ct_h2{(_Float16)p.slope, (_Float16)p.slope};
-    // stage the wave's G x 32 voxels with the deferred norm applied
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        const unsigned gv = g0 + 32 * g + l31;
-        const bool valid = gv < total;
-        const unsigned n = valid ? gv / in_vox : 0;
-        const unsigned vi = valid ? gv - n * in_vox : 0;
-        const __half* src_l = p.src + ((size_t)n * NCC * in_vox + vi) * 16 + kh * 8;
-        const unsigned* ss16_l = p.ss16 ? p.ss16 + ((size_t)n * p.Cin + kh * 8) : nullptr;
-        uint4 val[NCC];
-#pragma unroll
-        for (int cc = 0; cc < NCC; ++cc) val[cc] = *(const uint4*)(src_l + (size_t)cc * in_vox * 16);
-#pragma unroll
-        for (int cc = 0; cc < NCC; ++cc) {
-            uint4 o = val[cc];
-            if (ss16_l) {
-                const uint4 w0 = *(const uint4*)(ss16_l + cc * 16), w1 = *(const uint4*)(ss16_l + cc * 16 + 4);
-                o = convt_norm_act8_pk(o, w0, w1, sl2.u);
-            }
-            if (!valid) o = make_uint4(0, 0, 0, 0);
-            *(uint4*)(lds + (((g * NCC + cc) * 2 + kh) * 32 + l31) * 16) = o;
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    const int Ho = p.Hi * p.s1, Wo = p.Wi * p.s2;
-    const size_t ovox = (size_t)(p.Di * p.s0) * Ho * Wo;
-    const int nco = p.Cout / 32;
-    const int npairs = p.s0 * p.s1 * nco;
-    // store side (per group): this lane's pieces lane + 64 k of each plane of the slab (see k_convt_mfma)
-    unsigned char* optr[G][TZ];
-    unsigned ovalid = 0;
-#pragma unroll
-    for (int g = 0; g < G; ++g)
-#pragma unroll
-        for (int k = 0; k < TZ; ++k) {
-            const int ov = (lane + 64 * k) >> 1;
-            const int j = ov / TZ, tz = ov % TZ;
-            const unsigned gg = g0 + 32 * g + j;
-            const bool ok = gg < total;
-            ovalid |= ok ? (1u << (g * TZ + k)) : 0u;
-            const unsigned nn = ok ? gg / in_vox : 0;
-            const unsigned v2 = ok ? gg - nn * in_vox : 0;
-            const unsigned r2 = v2 / (unsigned)p.Wi;
-            const int iz = (int)(v2 - r2 * (unsigned)p.Wi);
-            const int ix = (int)(r2 / (unsigned)p.Hi), iy = (int)(r2 - (unsigned)ix * (unsigned)p.Hi);
-            const size_t ospat = ((size_t)(ix * p.s0) * Ho + (size_t)(iy * p.s1)) * Wo + (size_t)(iz * p.s2 + tz);
-            optr[g][k] = (unsigned char*)p.out + ((size_t)nn * (p.Cout / 16) * ovox + ospat) * 32 + 16 * (lane & 1);
-        }
-    const unsigned char* wbase = (const unsigned char*)p.wpk;
-    const unsigned wlane = ((unsigned)kh * (unsigned)p.Cout + (unsigned)l31) * 16u;
-    const unsigned wstep_cc = 2u * (unsigned)p.Cout * 16u;  // bytes per (tap, chunk)
-    const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int pr = blockIdx.y; pr < npairs; pr += gridDim.y) {
-        const int txy = pr / nco, co = pr - txy * nco;
-        const int ty = txy % p.s1, tx = txy / p.s1;
-        float4 bq[4];
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) bq[gq] = *(const float4*)(p.bias + co * 32 + 8 * gq + 4 * kh);
-        const int tap0 = (tx * p.s1 + ty) * p.s2;
-        const unsigned char* wpass = wbase + ((size_t)tap0 * NCC * wstep_cc + (size_t)co * 32 * 16);  // uniform
-        f16x8 a[TZ][NCC];   // the pass's weights, once for all G groups
-#pragma unroll
-        for (int t = 0; t < TZ; ++t)
-#pragma unroll
-            for (int cc = 0; cc < NCC; ++cc) a[t][cc] = *(const f16x8*)(wpass + (size_t)(t * NCC + cc) * wstep_cc + wlane);
-        const size_t poff = ((size_t)(co * 2) * ovox + ((size_t)tx * Ho + ty) * Wo) * 32;  // uniform; plane pl adds ovox * 32
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            f32x16 acc[TZ];
-            const unsigned char* bfrag = lds + ((g * NCC * 2 + kh) * 32 + l31) * 16;  // + cc * 1024
-#pragma unroll
-            for (int cc = 0; cc < NCC; ++cc) {
-                const f16x8 bf = *(const f16x8*)(bfrag + cc * 1024);
-#pragma unroll
-                for (int t = 0; t < TZ; ++t)
-                    acc[t] = cc == 0 ? __builtin_amdgcn_mfma_f32_32x32x16_f16(a[t][cc], bf, zero, 0, 0, 0)
-                                     : __builtin_amdgcn_mfma_f32_32x32x16_f16(a[t][cc], bf, acc[t], 0, 0, 0);
-            }
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-#pragma unroll
-                for (int t = 0; t < TZ; ++t) {
-                    union {
-                        uint2 u;
-                        __half h[4];
-                    } pk;
-                    pk.h[0] = __float2half_rn(acc[t][gq * 4 + 0] + bq[gq].x);
-                    pk.h[1] = __float2half_rn(acc[t][gq * 4 + 1] + bq[gq].y);
-                    pk.h[2] = __float2half_rn(acc[t][gq * 4 + 2] + bq[gq].z);
-                    pk.h[3] = __float2half_rn(acc[t][gq * 4 + 3] + bq[gq].w);
-                    *(uint2*)(slab + convt_slab_waddr<TZ>(gq, l31, t, kh)) = pk.u;
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-                for (int k = 0; k < TZ; ++k) {
-                    const int piece = lane + 64 * k;
-                    const uint4 d = convt_slab_read<TZ>(slab, pl, piece);
-                    if ((ovalid >> (g * TZ + k)) & 1u) *(uint4*)(optr[g][k] + poff + (size_t)pl * ovox * 32) = d;
-                }
-            __builtin_amdgcn_wave_barrier();
-        }
-    }
-}
-
-// Deep transposed convs (Cin = 16 NCC >= 256: 4^3 ... 16^3 inputs, round 4).  These layers are not HBM-bound at all -- a pass's
-// weights (2 NCC KiB per (x tap, y tap, cout chunk)) outweigh the activations, and k_convt_mfma streams them from L2 once per WAVE:
-// 230 / 138 / 41 us per 25 tiles for 84 / 19 / 3 MB of tensor traffic.  Here the block shares them: a wave keeps the B fragments of
-// its MT x 32 input voxels (deferred norm applied) in REGISTERS for the whole kernel (one wave per SIMD: 512 VGPRs), the pass's
-// weight fragments are moved L2 -> LDS once per BLOCK by LDS-DMA (double-buffered: the next pass's weights arrive under this
-// pass's MFMAs) and every wave reads its A fragments from LDS: 0.5 KiB of LDS reads per MFMA, no weight traffic per wave.
-// Same arithmetic as k_convt_mfma (chunk order, fp32 accumulation, bias add, RTNE to fp16), same slab interleave for the stores.
-template <int NCC>
-__global__ __launch_bounds__(256) void k_convt_deep(ConvTArgs p) {
-    constexpr int TZ = 2, MT = 2;
-    constexpr int WB = TZ * NCC * 1024;          // bytes of one pass's weights in LDS
-    constexpr int SLAB = 2 * 32 * TZ * 32;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // [weights 0][weights 1][4 slabs]
-    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, kh = lane >> 5;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned in_vox = (unsigned)(p.Di * p.Hi * p.Wi);
-    const unsigned total = (unsigned)p.N * in_vox;
-    unsigned char* slab = smem + 2 * WB + wave * SLAB;
-    float* lbias = (float*)(smem + 2 * WB + 4 * SLAB);   // the bias vector in LDS: a global load inside the pass loop would make hipcc wait
-    for (int i = tid; i < p.Cout; i += 256) lbias[i] = p.bias[i];   // with vmcnt(0) -- i.e. also for the next pass's weight DMA
-    const unsigned lds_w = __builtin_amdgcn_readfirstlane((unsigned)(size_t)smem);
-    const int Ho = p.Hi * p.s1, Wo = p.Wi * p.s2;
-    const size_t ovox = (size_t)(p.Di * p.s0) * Ho * Wo;
-    const int nco = p.Cout / 32;
-    const int npairs = p.s0 * p.s1 * nco;
-    // weights of pass `pr` -> LDS buffer `buf`: fragment f = tz * NCC + cc is one wave-wide LDS-DMA (64 lanes x 16 B: k-half
-    // lane / 32, cout lane % 32); the four waves take f = wave, wave + 4, ...
-    const unsigned wvoff = ((unsigned)kh * (unsigned)p.Cout + (unsigned)l31) * 16u;
-    auto dma_pass = [&](int pr, int buf) {
-        const int txy = pr / nco, co = pr - txy * nco;
-        const int ty = txy % p.s1, tx = txy / p.s1;
-        const int tap0 = (tx * p.s1 + ty) * p.s2;
-        for (int f = wave; f < TZ * NCC; f += 4) {
-            const int t = f / NCC, cc = f - t * NCC;
-            const size_t woff = ((size_t)((tap0 + t) * NCC + cc) * 2 * p.Cout + (size_t)co * 32) * 16;
-            // (wave-uniform by construction; readfirstlane makes it so for the compiler: the SGPR operands of the DMA)
-            const unsigned wlo = __builtin_amdgcn_readfirstlane((unsigned)woff), whi = __builtin_amdgcn_readfirstlane((unsigned)(woff >> 32));
-            const unsigned char* src = (const unsigned char*)p.wpk + (((size_t)whi << 32) | wlo);
-            const unsigned m0v = __builtin_amdgcn_readfirstlane(lds_w + (unsigned)(buf * WB + f * 1024));
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(wvoff), "s"(src), "s"(m0v) : "memory");
-        }
-    };
-    int pr = blockIdx.y;
-    if (pr < npairs) dma_pass(pr, 0);
-    // this wave's B fragments (registers) and store pointers
-    union {
-        unsigned u;
-        ct_h2 v;
-    } sl2;
-    sl2.v = ct_h2{(_Float16)p.slope, (_Float16)p.slope};
-    const unsigned g0 = ((unsigned)blockIdx.x * 4 + wave) * (32 * MT);
-    f16x8 b[MT][NCC];
-    unsigned char* optr[MT][TZ];
-    unsigned ovalid = 0;
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-        const unsigned gv = g0 + 32 * m + l31;
-        const bool valid = gv < total;
-        const unsigned n = valid ? gv / in_vox : 0;
-        const unsigned vi = valid ? gv - n * in_vox : 0;
-        const __half* src_l = p.src + ((size_t)n * NCC * in_vox + vi) * 16 + kh * 8;
-        const unsigned* ss16_l = p.ss16 + ((size_t)n * p.Cin + kh * 8);
-#pragma unroll
-        for (int cc = 0; cc < NCC; ++cc) {
-            uint4 o = *(const uint4*)(src_l + (size_t)cc * in_vox * 16);
-            const uint4 w0 = *(const uint4*)(ss16_l + cc * 16), w1 = *(const uint4*)(ss16_l + cc * 16 + 4);
-            o = convt_norm_act8_pk(o, w0, w1, sl2.u);
-            if (!valid) o = make_uint4(0, 0, 0, 0);
-            union {
-                uint4 u;
-                f16x8 f;
-            } cv;
-            cv.u = o;
-            b[m][cc] = cv.f;
-        }
-#pragma unroll
-        for (int k = 0; k < TZ; ++k) {
-            const int ov = (lane + 64 * k) >> 1;
-            const int j = ov / TZ, tz = ov % TZ;
-            const unsigned gg = g0 + 32 * m + j;
-            const bool ok = gg < total;
-            ovalid |= ok ? (1u << (m * TZ + k)) : 0u;
-            const unsigned nn = ok ? gg / in_vox : 0;
-            const unsigned v2 = ok ? gg - nn * in_vox : 0;
-            const unsigned r2 = v2 / (unsigned)p.Wi;
-            const int iz = (int)(v2 - r2 * (unsigned)p.Wi);
-            const int ix = (int)(r2 / (unsigned)p.Hi), iy = (int)(r2 - (unsigned)ix * (unsigned)p.Hi);
-            const size_t ospat = ((size_t)(ix * p.s0) * Ho + (size_t)(iy * p.s1)) * Wo + (size_t)(iz * p.s2 + tz);
-            optr[m][k] = (unsigned char*)p.out + ((size_t)nn * (p.Cout / 16) * ovox + ospat) * 32 + 16 * (lane & 1);
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int it = 0; pr < npairs; pr += gridDim.y, ++it) {
-        const int buf = it & 1;
-        if (pr + (int)gridDim.y < npairs) dma_pass(pr + (int)gridDim.y, buf ^ 1);
-        const int txy = pr / nco, co = pr - txy * nco;
-        const int ty = txy % p.s1, tx = txy / p.s1;
-        float4 bq[4];
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) bq[gq] = *(const float4*)(lbias + co * 32 + 8 * gq + 4 * kh);
-        const unsigned char* wl = smem + buf * WB + (kh * 32 + l31) * 16;
-        f32x16 acc[TZ][MT];
-#pragma unroll
-        for (int cc = 0; cc < NCC; ++cc)
-#pragma unroll
-            for (int t = 0; t < TZ; ++t) {
-                const f16x8 a = *(const f16x8*)(wl + (t * NCC + cc) * 1024);
-#pragma unroll
-                for (int m = 0; m < MT; ++m)
-                    acc[t][m] = cc == 0 ? __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b[m][cc], zero, 0, 0, 0)
-                                        : __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b[m][cc], acc[t][m], 0, 0, 0);
-            }
-        const size_t poff = ((size_t)(co * 2) * ovox + ((size_t)tx * Ho + ty) * Wo) * 32;
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq)
-#pragma unroll
-                for (int t = 0; t < TZ; ++t) {
-                    union {
-                        uint2 u;
-                        __half h[4];
-                    } pk;
-                    pk.h[0] = __float2half_rn(acc[t][m][gq * 4 + 0] + bq[gq].x);
-                    pk.h[1] = __float2half_rn(acc[t][m][gq * 4 + 1] + bq[gq].y);
-                    pk.h[2] = __float2half_rn(acc[t][m][gq * 4 + 2] + bq[gq].z);
-                    pk.h[3] = __float2half_rn(acc[t][m][gq * 4 + 3] + bq[gq].w);
-                    *(uint2*)(slab + convt_slab_waddr<TZ>(gq, l31, t, kh)) = pk.u;
-                }
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-                for (int k = 0; k < TZ; ++k) {
-                    const int piece = lane + 64 * k;
-                    const uint4 d = convt_slab_read<TZ>(slab, pl, piece);
-                    if ((ovalid >> (m * TZ + k)) & 1u) *(uint4*)(optr[m][k] + poff + (size_t)pl * ovox * 32) = d;
-                }
-            __builtin_amdgcn_wave_barrier();
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the next pass's weights have landed (and this pass's stores are out)
-        __syncthreads();
-    }
-}
-
-int convt_mfma_form(int Cin, const int s[3], bool norm_src) {
-    if (s[0] == 2 && s[1] == 2 && s[2] == 2 && norm_src && (Cin == 256 || Cin == 320)) return 2;
-    if (s[2] == 2 && norm_src && (Cin == 64 || Cin == 128)) return 1;
-    return 0;
-}
-
-int launch_convt_mfma(boa_ctx* ctx, const ActSrc& src, int N, const int din[3], const int s[3], int Cout,
-                      const __half* wpk, const float* bias, float slope, __half* out) {
-    BOA_REQUIRE(src.C % 16 == 0 && Cout % 32 == 0, "convT: channels %d -> %d unsupported", src.C, Cout);
-    ConvTArgs a;
-    a.src = src.data; a.ss = src.ss; a.ss16 = src.ss16; a.Cin = src.C; a.Cout = Cout; a.N = N;
-    a.Di = din[0]; a.Hi = din[1]; a.Wi = din[2]; a.s0 = s[0]; a.s1 = s[1]; a.s2 = s[2];
-    a.wpk = wpk; a.bias = bias; a.out = out; a.slope = slope;
-    const int gy_mult = 2;  // (8 and 32 measured slower: every y-slice re-stages the block's input voxels)
-    size_t total = (size_t)N * din[0] * din[1] * din[2];
-    int gx = (int)((total + 127) / 128);
-    // split the (tap, cout-chunk) pairs over gridDim.y only as far as needed to fill the chip: every y-slice
-    // re-stages the block's input voxels
-    BOA_REQUIRE(s[2] == 1 || s[2] == 2, "convT: stride %d along the contiguous axis is not instantiated (1 or 2)", s[2]);
-    BOA_REQUIRE((double)total < 2147483648.0 - 256.0, "convT: %zu input voxels exceed the 32-bit index range", total);
-    const int npairs = s[0] * s[1] * (Cout / 32);   // (tx, ty, cout chunk); a pair covers the s2 z taps
-    int gy = std::min(npairs, std::max(1, ceil_div(gy_mult * ctx->cu_count, gx)));
-    size_t lds = (size_t)4 * ((src.C / 16) * 1024 + 2 * 32 * s[2] * 32);
-    BOA_REQUIRE(lds <= 160 * 1024, "convT: Cin=%d needs %zu bytes of LDS", src.C, lds);
-    static bool once = (hipFuncSetAttribute((const void*)k_convt_mfma<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-                        hipFuncSetAttribute((const void*)k_convt_mfma<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), true);
-    (void)once;
-    const double taps = (double)s[0] * s[1] * s[2];
-    KernelTimer tm(ctx, BOA_K_CONVT, 2.0 * total * taps * src.C * Cout, 2.0 * total * (src.C + taps * Cout));
-    const int form = convt_mfma_form(src.C, s, src.ss16 != nullptr);
-    const bool rw = form == 1, deep = form == 2;
-    if (deep) {
-        const int ncc = src.C / 16;
-        const int gxd = (int)((total + 255) / 256);    // 4 waves x 2 M-tiles x 32 voxels per block
-        // the (x tap, y tap, cout chunk) passes are spread over gridDim.y until there is about one block per CU (one fits: 64-80 KiB of
-        // weight buffers), at least two passes per block so that the weight DMA overlaps (measured at 25 tiles: 16^3 124 / 140 / 151 /
-        // 189 us at 1 / 2 / 4 / 8 slices, 8^3 139 / 81 / 48 / 58, 4^3 166 / 94 / 52 / 34 and 22 at 20)
-        const int gyd = std::max(1, std::min(npairs / 2, ctx->cu_count / std::max(gxd, 1)));
-        const size_t ldsd = (size_t)2 * 2 * ncc * 1024 + 4 * (2 * 32 * 2 * 32) + (size_t)Cout * sizeof(float);
-        static bool od = (hipFuncSetAttribute((const void*)k_convt_deep<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-                          hipFuncSetAttribute((const void*)k_convt_deep<20>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), true);
-        (void)od;
-        if (ncc == 16)
-            hipLaunchKernelGGL(k_convt_deep<16>, dim3(gxd, gyd), dim3(256), ldsd, ctx->stream, a);
-        else
-            hipLaunchKernelGGL(k_convt_deep<20>, dim3(gxd, gyd), dim3(256), ldsd, ctx->stream, a);
-    } else if (rw) {
-        // register-weights variant: G groups of 32 voxels per wave (G x 128 voxels per block)
-        const int G = 2;   // (32^3 -> 64^3: 125 -> 105 us per 8 tiles: two workgroups per CU)
-        const int gxr = (int)((total + 128 * G - 1) / (128 * G));
-        const int gyr = std::min(npairs, std::max(1, ceil_div(gy_mult * ctx->cu_count, gxr)));
-        const size_t ldsr = (size_t)4 * ((size_t)G * (src.C / 16) * 1024 + 2 * 32 * 2 * 32);
-        static bool o1 = (hipFuncSetAttribute((const void*)k_convt_mfma_rw<2, 4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-                          hipFuncSetAttribute((const void*)k_convt_mfma_rw<2, 8, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), true);
-        (void)o1;
-        if (src.C == 64)
-            hipLaunchKernelGGL((k_convt_mfma_rw<2, 4, 2>), dim3(gxr, gyr), dim3(256), ldsr, ctx->stream, a);
-        else
-            hipLaunchKernelGGL((k_convt_mfma_rw<2, 8, 2>), dim3(gxr, gyr), dim3(256), ldsr, ctx->stream, a);
-    } else if (s[2] == 2)
-        hipLaunchKernelGGL(k_convt_mfma<2>, dim3(gx, gy), dim3(256), lds, ctx->stream, a);
-    else
-        hipLaunchKernelGGL(k_convt_mfma<1>, dim3(gx, gy), dim3(256), lds, ctx->stream, a);
-    tm.stop();
-    BOA_HIP_TRY(hipGetLastError());
-    return BOA_OK;
-}
-
-// ======================================================================================================
-// 1x1x1 head (+ Gaussian weighting + fp16 accumulate)
-struct HeadArgs {
-    const __half* act;
-    const float* ss;
-    int F0, P0, P1, P2, C;
-    const float* w;  // [C][F0]
-    const float* bias;
-    float slope;
-    float* logits;
-    const unsigned short* gauss;
-    unsigned short* acc;
-    unsigned short* nacc;
-    int V0, V1, V2, s0, s1, s2;
-    size_t plane_stride;  // voxels between the 16-channel planes of `act` (the tile's voxel count; a stash: its own)
-};
-
-template <int F0, int VPT>
-__global__ __launch_bounds__(256) void k_head(HeadArgs p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float* lw = (float*)smem;        // [C][F0]
-    float* lb = lw + p.C * F0;       // [C]
-    float* lss = lb + p.C;           // [F0][2]
-    for (int i = threadIdx.x; i < p.C * F0; i += 256) lw[i] = p.w[i];
-    for (int i = threadIdx.x; i < p.C; i += 256) lb[i] = p.bias[i];
-    for (int i = threadIdx.x; i < 2 * F0; i += 256) lss[i] = p.ss[i];
-    __syncthreads();
-    const size_t pv = (size_t)p.P0 * p.P1 * p.P2;
-    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * VPT;  // first of VPT consecutive voxels along z
-    if (i >= pv) return;
-    float y[VPT][F0];
-#pragma unroll
-    for (int u = 0; u < VPT; ++u) {
-#pragma unroll
-        for (int v = 0; v < F0 / 8; ++v) {
-            union {
-                uint4 u4;
-                __half h[8];
-            } x;
-            x.u4 = *(const uint4*)(p.act + ((size_t)(v >> 1) * p.plane_stride + (i + u)) * 16 + 8 * (v & 1));  // chunk-planar
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                int c = v * 8 + j;
-                float f = __builtin_fmaf(__half2float(x.h[j]), lss[2 * c], lss[2 * c + 1]);
-                y[u][c] = f > 0.f ? f : f * p.slope;
-            }
-        }
-    }
-    if (p.logits) {
-        for (int c = 0; c < p.C; ++c) {
-#pragma unroll
-            for (int u = 0; u < VPT; ++u) {
-                float sum = lb[c];
-#pragma unroll
-                for (int k = 0; k < F0; ++k) sum = __builtin_fmaf(lw[c * F0 + k], y[u][k], sum);
-                p.logits[(size_t)c * pv + i + u] = sum;
-            }
-        }
-        return;
-    }
-    const int p2 = (int)(i % p.P2);
-    const int p1 = (int)((i / p.P2) % p.P1);
-    const int p0 = (int)(i / ((size_t)p.P2 * p.P1));
-    const size_t vv = (size_t)p.V0 * p.V1 * p.V2;
-    const size_t vi = ((size_t)(p.s0 + p0) * p.V1 + (p.s1 + p1)) * p.V2 + (p.s2 + p2);
-    float g[VPT];
-#pragma unroll
-    for (int u = 0; u < VPT; ++u) g[u] = p.gauss ? us2f(p.gauss[i + u]) : 1.0f;
-    for (int c = 0; c < p.C; ++c) {
-        float sum[VPT];
-#pragma unroll
-        for (int u = 0; u < VPT; ++u) sum[u] = lb[c];
-#pragma unroll
-        for (int k = 0; k < F0; ++k) {
-            const float wk = lw[c * F0 + k];
-#pragma unroll
-            for (int u = 0; u < VPT; ++u) sum[u] = __builtin_fmaf(wk, y[u][k], sum[u]);
-        }
-        unsigned short* ap = p.acc + (size_t)c * vv + vi;
-        if (VPT == 2) {
-            union {
-                unsigned u32;
-                unsigned short h[2];
-            } a;
-            a.u32 = *(const unsigned*)ap;
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                float pr = p.gauss ? sum[u] * g[u] : sum[u];  // prediction *= gaussian (fp32)
-                a.h[u] = f2us(us2f(a.h[u]) + pr);             // fp16 += fp32 (fp32 add, RTNE to fp16)
-            }
-            *(unsigned*)ap = a.u32;
-        } else {
-            float pr = p.gauss ? sum[0] * g[0] : sum[0];
-            *ap = f2us(us2f(*ap) + pr);
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < VPT; ++u) p.nacc[vi + u] = f2us(us2f(p.nacc[vi + u]) + g[u]);
-}
-
-// Head on the matrix cores (F0 == 32, C <= 32, accumulate mode): per 32 consecutive z voxels two
-// v_mfma_f32_32x32x16_f16 (K = 32 channels) replace 32 x C fp32 FMAs per voxel.  B fragments are the voxels' channel
-// records straight from global memory (16 B per lane and step) with the deferred InstanceNorm + LeakyReLU applied in
-// packed fp16, A = the head weights in registers.  D[class][voxel] -> + bias, x Gaussian (fp32), fp16 `+=` into the
-// accumulators exactly as k_head does it (fp32 add, one RTNE rounding): lanes 0-31 / 32-63 update two classes of the
-// same 32 voxels per instruction (64 contiguous bytes each).
-typedef _Float16 hh2_t __attribute__((ext_vector_type(2)));
-
-// LOGITS = true: the same MFMA / bias / transpose path, but the fp32 logits [C][P0][P1][P2] are written out instead of
-// being accumulated (boa_net_forward, and the seam that proves the accumulate arithmetic of THIS kernel bit-exact: the
-// logits it writes are the values its accumulate mode multiplies by the Gaussian and adds).
-template <bool LOGITS>
-__global__ __launch_bounds__(256, 5) void k_head_mfma(HeadArgs p) {
-    const int lane = threadIdx.x & 63, l31 = lane & 31, kh = lane >> 5;
-    f16x8 a0, a1;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        a0[i] = l31 < p.C ? (_Float16)p.w[l31 * 32 + 8 * kh + i] : (_Float16)0.f;
-        a1[i] = l31 < p.C ? (_Float16)p.w[l31 * 32 + 16 + 8 * kh + i] : (_Float16)0.f;
-    }
-    // The per-lane constants -- packed (scale, shift) of this lane's 16 input channels and the 16 biases of its D rows --
-    // depend on the k-half only; they live in LDS (2 x 32 words) and are re-read per M-tile instead of occupying 32 VGPRs:
-    // the kernel waits on HBM round trips, and 114 -> ~80 VGPRs doubles the waves in flight (3 -> 6 per SIMD).
-    __shared__ __attribute__((aligned(16))) unsigned s_ss[2][16];   // [kh][step 0: sc x4, sh x4 | step 1: sc x4, sh x4]
-    __shared__ __attribute__((aligned(16))) float s_bz[2][16];
-    if (threadIdx.x < 2) {
-        const int k = threadIdx.x;
-        union {
-            unsigned u;
-            hh2_t v;
-        } cv;
-        for (int i = 0; i < 4; ++i) {
-            const int c0 = 8 * k + 2 * i, c1 = 16 + 8 * k + 2 * i;
-            cv.v = hh2_t{(_Float16)p.ss[2 * c0], (_Float16)p.ss[2 * c0 + 2]};
-            s_ss[k][i] = cv.u;
-            cv.v = hh2_t{(_Float16)p.ss[2 * c0 + 1], (_Float16)p.ss[2 * c0 + 3]};
-            s_ss[k][4 + i] = cv.u;
-            cv.v = hh2_t{(_Float16)p.ss[2 * c1], (_Float16)p.ss[2 * c1 + 2]};
-            s_ss[k][8 + i] = cv.u;
-            cv.v = hh2_t{(_Float16)p.ss[2 * c1 + 1], (_Float16)p.ss[2 * c1 + 3]};
-            s_ss[k][12 + i] = cv.u;
-        }
-        for (int i = 0; i < 16; ++i) {
-            const int c = 8 * (i >> 2) + 4 * k + (i & 3);
-            s_bz[k][i] = c < p.C ? p.bias[c] : 0.f;
-        }
-    }
-    __syncthreads();
-    const hh2_t sl = hh2_t{(_Float16)p.slope, (_Float16)p.slope};
-    auto xform = [&](uint4 raw, int step) {
-        union {
-            uint4 u;
-            hh2_t v[4];
-            f16x8 f;
-        } x, sc, sh;
-        x.u = raw;
-        sc.u = *(const uint4*)&s_ss[kh][8 * step];
-        sh.u = *(const uint4*)&s_ss[kh][8 * step + 4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const hh2_t y = __builtin_elementwise_fma(x.v[i], sc.v[i], sh.v[i]);
-            x.v[i] = __builtin_elementwise_max(y, y * sl);
-        }
-        return x.f;
-    };
-    // per-wave LDS slab for the [class][voxel] transpose: 33 rows (32 classes + pad) x 36 floats (16-byte aligned rows)
-    __shared__ __attribute__((aligned(16))) float slab_all[4][32 * 36];
-    float* slab = slab_all[threadIdx.x >> 6];
-    const int mpr = p.P2 / 32;                     // M-tiles per (x, y) row
-    const int n_mt = p.P0 * p.P1 * mpr;
-    const size_t vv = (size_t)p.V0 * p.V1 * p.V2;
-    const size_t pv = (size_t)p.P0 * p.P1 * p.P2;
-    const int gw = (int)((blockIdx.x * 256 + threadIdx.x) >> 6), nw = (int)(gridDim.x * 4);
-    const int n_items = LOGITS ? p.C * 4 : (p.C + 1) * 4;  // (class, group of 8 voxels); class index C = the n_predictions row
-    for (int mt = gw; mt < n_mt; mt += nw) {
-        const int zb = (mt % mpr) * 32, row = mt / mpr, p1 = row % p.P1, p0 = row / p.P1;
-        const size_t t0 = ((size_t)p0 * p.P1 + p1) * p.P2 + zb;       // first voxel of the M-tile within the tile
-        const size_t v0 = ((size_t)(p.s0 + p0) * p.V1 + (p.s1 + p1)) * p.V2 + (p.s2 + zb);  // ... within the volume
-        // chunk-planar: plane 0 = channels 0-15 (MFMA step 0 takes its octet kh), plane 1 = channels 16-31 (step 1); a wave
-        // reads 1 KiB of consecutive bytes per plane
-        const uint4 r0 = *(const uint4*)(p.act + (t0 + l31) * 16 + kh * 8);
-        const uint4 r1 = *(const uint4*)(p.act + (p.plane_stride + t0 + l31) * 16 + kh * 8);
-        // the RMW operands of this lane's items: issued before the MFMAs so that their latency overlaps
-        uint4 gq8[2], old8[2];
-        if (!LOGITS) {
-#pragma unroll
-            for (int it = 0; it < 2; ++it) {
-                const int item = lane + 64 * it;
-                const int c = item >> 2, grp = item & 3;
-                gq8[it] = make_uint4(0x3c003c00u, 0x3c003c00u, 0x3c003c00u, 0x3c003c00u);  // 1.0 (no Gaussian)
-                old8[it] = make_uint4(0, 0, 0, 0);
-                if (item < n_items) {
-                    if (p.gauss) gq8[it] = *(const uint4*)(p.gauss + t0 + 8 * grp);
-                    const unsigned short* src = (c < p.C ? p.acc + (size_t)c * vv : p.nacc) + v0 + 8 * grp;
-                    old8[it] = *(const uint4*)src;
-                }
-            }
-        }
-        const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        f32x16 d = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, xform(r0, 0), zero, 0, 0, 0);
-        d = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, xform(r1, 1), d, 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) slab[(8 * (i >> 2) + 4 * kh + (i & 3)) * 36 + l31] = d[i] + s_bz[kh][i];
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const int item = lane + 64 * it;
-            const int c = item >> 2, grp = item & 3;
-            if (item < n_items) {
-                float4 lo = make_float4(1.f, 1.f, 1.f, 1.f), hi = lo;  // the n_predictions row adds the Gaussian itself
-                if (c < p.C) {
-                    lo = *(const float4*)(slab + c * 36 + 8 * grp);
-                    hi = *(const float4*)(slab + c * 36 + 8 * grp + 4);
-                }
-                if (LOGITS) {
-                    float* dst = p.logits + (size_t)c * pv + t0 + 8 * grp;
-                    *(float4*)dst = lo;
-                    *(float4*)(dst + 4) = hi;
-                } else {
-                    union {
-                        uint4 u;
-                        unsigned short h[8];
-                    } g, o;
-                    g.u = gq8[it];
-                    o.u = old8[it];
-                    const float sum[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const float gg = us2f(g.h[e]);
-                        const float pr = (p.gauss || c >= p.C) ? sum[e] * gg : sum[e];  // prediction *= gaussian (fp32); n += g
-                        o.h[e] = f2us(us2f(o.h[e]) + pr);                               // fp16 += fp32 (fp32 add, RTNE)
-                    }
-                    unsigned short* dst = (c < p.C ? p.acc + (size_t)c * vv : p.nacc) + v0 + 8 * grp;
-                    *(uint4*)dst = o.u;
-                }
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-
-int launch_head(boa_ctx* ctx, const __half* act, const float* ss, int F0, const int P[3], int C, const float* w,
-                const float* bias, float slope, float* logits_out, const uint16_t* gauss, uint16_t* acc,
-                uint16_t* nacc, const int PV[3], const int start[3], size_t plane_stride) {
-    BOA_REQUIRE(F0 == 32 || F0 == 64, "head: features[0]=%d unsupported (32 or 64)", F0);
-    HeadArgs a;
-    a.act = act; a.ss = ss; a.F0 = F0; a.P0 = P[0]; a.P1 = P[1]; a.P2 = P[2]; a.C = C; a.w = w; a.bias = bias;
-    a.slope = slope; a.logits = logits_out; a.gauss = gauss; a.acc = acc; a.nacc = nacc;
-    a.plane_stride = plane_stride ? plane_stride : (size_t)P[0] * P[1] * P[2];
-    bool pair = (P[2] % 2 == 0) && F0 == 32;
-    if (!logits_out) {
-        for (int d = 0; d < 3; ++d)
-            BOA_REQUIRE(start[d] >= 0 && start[d] + P[d] <= PV[d], "head: tile [%d,%d) outside accumulator dim %d (%d)",
-                        start[d], start[d] + P[d], d, PV[d]);
-        a.V0 = PV[0]; a.V1 = PV[1]; a.V2 = PV[2]; a.s0 = start[0]; a.s1 = start[1]; a.s2 = start[2];
-        pair = pair && (PV[2] % 2 == 0) && (start[2] % 2 == 0) && (((uintptr_t)acc) % 4 == 0);
-    } else {
-        a.V0 = a.V1 = a.V2 = a.s0 = a.s1 = a.s2 = 0;
-    }
-    size_t pv = (size_t)P[0] * P[1] * P[2];
-    size_t lds = ((size_t)C * F0 + C + 2 * F0) * 4;
-    double bytes = (double)pv * (2.0 * F0 + (logits_out ? 4.0 * C : (4.0 * (C + 1) + 2.0)));
-    KernelTimer tm(ctx, BOA_K_HEAD_ACCUM, 2.0 * pv * F0 * C, bytes);
-    const bool mfma_shape = F0 == 32 && C <= 31 && P[2] % 32 == 0 && ((uintptr_t)act) % 16 == 0;
-    const unsigned mfma_grid = (unsigned)std::min<size_t>(std::max<size_t>(pv / 32 / 4, 1), (size_t)ctx->cu_count * 8);
-    // 16-byte accumulator accesses: the tile's z origin, the volume's z extent and the buffers must be 8-voxel aligned
-    if (!logits_out && mfma_shape && start[2] % 8 == 0 && PV[2] % 8 == 0 && ((uintptr_t)acc) % 16 == 0 &&
-        ((uintptr_t)nacc) % 16 == 0 && (!gauss || ((uintptr_t)gauss) % 16 == 0)) {
-        hipLaunchKernelGGL(k_head_mfma<false>, dim3(mfma_grid), dim3(256), 0, ctx->stream, a);
-        ctx->counters[BOA_CNT_HEAD_MFMA]++;
-    } else if (logits_out && mfma_shape && ((uintptr_t)logits_out) % 16 == 0) {
-        hipLaunchKernelGGL(k_head_mfma<true>, dim3(mfma_grid), dim3(256), 0, ctx->stream, a);
-        ctx->counters[BOA_CNT_HEAD_MFMA]++;
-    } else if (!logits_out && mfma_shape) {
-        // accumulators that do not allow the 16-byte read-modify-write (tile z origin / volume z extent not 8-aligned: the common
-        // case for real CT sizes): the SAME MFMA logits (logits mode) into a scratch buffer, then the reference's accumulate step on
-        // them (k_accumulate_tile: identical arithmetic, tests/test_gpu_head.py) -- so that every tile's logits come from the same
-        // kernel whatever its alignment, and the logits API agrees bit for bit with the label path (gather head).  (Round 2 fell
-        // back to an fp32 VALU head here, whose logits differ in the last bits.)
-        float* tmp = nullptr;
-        if (boa_malloc(ctx, (size_t)C * pv * sizeof(float), (void**)&tmp) != BOA_OK) {
-            tm.stop();
-            return BOA_ENOMEM;
-        }
-        HeadArgs al = a;
-        al.logits = tmp;
-        hipLaunchKernelGGL(k_head_mfma<true>, dim3(mfma_grid), dim3(256), 0, ctx->stream, al);
-        tm.stop();
-        ctx->counters[BOA_CNT_HEAD_MFMA]++;
-        const int rc = boa_accumulate_tile(ctx, tmp, gauss, acc, nacc, C, P, PV, start);
-        boa_free(ctx, tmp);
-        if (rc) return rc;
-        BOA_HIP_TRY(hipGetLastError());
-        return BOA_OK;
-    } else {
-        if (pair)
-            hipLaunchKernelGGL((k_head<32, 2>), dim3((unsigned)((pv / 2 + 255) / 256)), dim3(256), lds, ctx->stream, a);
-        else if (F0 == 32)
-            hipLaunchKernelGGL((k_head<32, 1>), dim3((unsigned)((pv + 255) / 256)), dim3(256), lds, ctx->stream, a);
-        else
-            hipLaunchKernelGGL((k_head<64, 1>), dim3((unsigned)((pv + 255) / 256)), dim3(256), lds, ctx->stream, a);
-        ctx->counters[BOA_CNT_HEAD_VALU]++;
-    }
     tm.stop();
     BOA_HIP_TRY(hipGetLastError());
     return BOA_OK;

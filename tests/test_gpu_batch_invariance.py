@@ -20,6 +20,7 @@ def ctx():
     ((32, 32, 32), (32, 64, 128), (44, 40, 48)),          # one tile run per virtual workgroup
     ((64, 64, 64), (32, 64), (80, 64, 96)),               # 512 spatial tiles per sample at full resolution: runs of 2 tiles
     ((32, 64, 128), (32, 64, 128, 256), (40, 64, 160)),   # anisotropic, 4 stages, tiles % virtual workgroups != 0
+    ((24, 40, 32), (32, 64, 128, 256), (36, 60, 48)),     # 60 / 480 voxels per sample into the transposed convs: waves straddle samples
 ])
 def test_tile_logits_independent_of_batch(ctx, patch, features, vol):
     from boa_hip import plans, sliding_window as sw

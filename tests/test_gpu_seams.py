@@ -217,6 +217,8 @@ def test_conv_block_norm_act(ctx, N, Cin, dims, Cout, k, s):
     (1, 64, (8, 8, 16), 32, (2, 2, 2)),
     (2, 320, (4, 4, 4), 320, (2, 2, 2)),
     (1, 128, (5, 6, 7), 64, (1, 2, 2)),
+    (3, 64, (3, 5, 7), 32, (2, 2, 2)),     # 105 voxels per sample: waves span samples 0/1 and 1/2; a partial and two empty waves
+    (2, 32, (3, 5, 7), 32, (2, 2, 1)),     # stride 1 along the contiguous axis (k_convt_mfma<1>), two chunks under the batch-of-4 loads
 ])
 def test_convtranspose(ctx, N, Cin, dims, Cout, s):
     import torch

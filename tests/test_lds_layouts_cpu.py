@@ -1,4 +1,4 @@
-"""LDS layouts of round 5 as index arithmetic: the formulas of csrc/conv.hip (convt_slab_waddr / convt_slab_read), csrc/conv_ns.hip
+"""LDS layouts of round 5 as index arithmetic: the formulas of csrc/convt.hip (convt_slab_waddr / convt_slab_read), csrc/conv_ns.hip
 (NS_SW_ROW: the stride-2 halo de-interleaved by parity) and choose_conv_tile's padded x-plane stride, restated in Python and checked
 for (a) being permutations that round-trip the data and (b) being free of bank conflicts under the lane groups the hardware guide
 lists (ds_read_b128: four fixed 16-lane groups on 64 banks; ds_write_b64: contiguous 16-lane groups on 32 banks).  The kernels
