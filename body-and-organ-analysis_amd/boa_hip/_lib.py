@@ -86,6 +86,9 @@ _PROTOS = {
     "boa_tissue_projections": (i32, [vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, vp, vp]),
     "boa_label_hu_histogram": (i32, [vp, vp, vp, vp, u64, i32, i32, vp]),
     "boa_label_hu_mask": (i32, [vp, vp, vp, vp, i32, i32, i32, u64, vp]),
+    "boa_group_stats_f64": (i32, [vp, vp, vp, u64, vp, i32, vp, vp]),
+    "boa_label_hu_mask_f64": (i32, [vp, vp, vp, vp, i32, C.c_double, C.c_double, u64, vp]),
+    "boa_tissue_aggregate_f64": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
     "boa_binary_erode": (i32, [vp, vp, vp, vp, i32, i32, i32, i32]),
     "boa_ccl26": (i32, [vp, vp, i32, i32, i32, vp, vp, ip]),
     "boa_ccl_filter_largest": (i32, [vp, vp, vp, u64, vp, i32]),
@@ -99,6 +102,7 @@ _PROTOS = {
     "boa_mask_assign": (i32, [vp, vp, u64, i32, i32, vp]),
     "boa_label_overlay": (i32, [vp, vp, u64, vp]),
     "boa_median3_inplane": (i32, [vp, vp, i32, i32, i32, i32, vp]),
+    "boa_median3_inplane_f64": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "boa_bits_words": (u64, [i32, i32, i32]),
     "boa_bits_erode_u8": (i32, [vp, vp, vp, i32, i32, i32, i32, i32]),
     "boa_bits_select": (i32, [vp, vp, i32, i32, i32, vp, i32, vp]),

@@ -59,27 +59,31 @@ def slice_axis_from_orientation(orientation) -> int:
     raise ValueError(f"The orientation {orientation} does not contain neither I nor S.")
 
 
-def median_filter_inplane(ctx: Context, ct: DeviceBuffer, shape, flat_axis: int = 0) -> DeviceBuffer:
-    """scipy.ndimage.median_filter(image, size=[3,3,3] with 1 on `flat_axis`) on the device (int16)."""
+def median_filter_inplane(ctx: Context, ct: DeviceBuffer, shape, flat_axis: int = 0, ct_f64: bool = False) -> DeviceBuffer:
+    """scipy.ndimage.median_filter(image, size=[3,3,3] with 1 on `flat_axis`) on the device (int16, or float64 with `ct_f64`)."""
     Z, Y, X = (int(s) for s in shape)
-    out = ctx.alloc(Z * Y * X * 2)
-    check(ctx.lib.boa_median3_inplane(ctx.h, ct.vp, Z, Y, X, int(flat_axis), out.vp), "boa_median3_inplane")
+    out = ctx.alloc(Z * Y * X * (8 if ct_f64 else 2))
+    if ct_f64:
+        check(ctx.lib.boa_median3_inplane_f64(ctx.h, ct.vp, Z, Y, X, int(flat_axis), out.vp), "boa_median3_inplane_f64")
+    else:
+        check(ctx.lib.boa_median3_inplane(ctx.h, ct.vp, Z, Y, X, int(flat_axis), out.vp), "boa_median3_inplane")
     return out
 
 
 def tissue_aggregate(ctx: Context, ct: DeviceBuffer, regions: DeviceBuffer, parts: Optional[DeviceBuffer], shape,
-                     want_tissues: bool = True, ct_rules: Optional[DeviceBuffer] = None):
+                     want_tissues: bool = True, ct_rules: Optional[DeviceBuffer] = None, ct_f64: bool = False):
     """One pass: tissues (uint8, optional), counts uint32 [Z,2,8], hu_sums int64 [Z,2,8] ([.,0,.] all voxels,
-    [.,1,.] body_parts == TORSO).  ct_rules: the (median-filtered) CT the derivation rules look at, default ct."""
+    [.,1,.] body_parts == TORSO).  ct_rules: the (median-filtered) CT the derivation rules look at, default ct.
+    `ct_f64`: ct / ct_rules hold float64, the rules compare the float values and hu_sums comes back as float64."""
     Z, Y, X = (int(s) for s in shape)
     tis = ctx.alloc(Z * Y * X) if want_tissues else None
     cnt = ctx.alloc(Z * 16 * 4)
     sums = ctx.alloc(Z * 16 * 8)
-    check(ctx.lib.boa_tissue_aggregate(ctx.h, ct.vp, ct_rules.vp if ct_rules else None, regions.vp,
-                                       parts.vp if parts else None, tis.vp if tis else None, Z, Y, X, cnt.vp, sums.vp),
-          "boa_tissue_aggregate")
+    fn, what = (ctx.lib.boa_tissue_aggregate_f64, "boa_tissue_aggregate_f64") if ct_f64 else (ctx.lib.boa_tissue_aggregate, "boa_tissue_aggregate")
+    check(fn(ctx.h, ct.vp, ct_rules.vp if ct_rules else None, regions.vp,
+             parts.vp if parts else None, tis.vp if tis else None, Z, Y, X, cnt.vp, sums.vp), what)
     counts = cnt.download((Z, 2, 8), np.uint32)
-    hu_sums = sums.download((Z, 2, 8), np.int64)
+    hu_sums = sums.download((Z, 2, 8), np.float64 if ct_f64 else np.int64)
     cnt.free()
     sums.free()
     return tis, counts, hu_sums
@@ -202,7 +206,7 @@ def _descriptive(x_all: np.ndarray, cols, counts_a, sums_a, lo, hi) -> dict:
     s = sums_a[lo:hi].sum(axis=0)
     mean_hu = {_tname(nme): ((float(s[v]) / float(c[v])) if c[v] else None) for nme, v in TISSUES}
     adip = [5, 3, 4, 6, 7]
-    ca, sa = int(c[adip].sum()), int(s[adip].sum())
+    ca, sa = int(c[adip].sum()), s[adip].sum()      # (int64 sums of an int16 CT, fp64 sums of a float CT)
     mean_hu["TAT"] = (float(sa) / float(ca)) if ca else None
     keys = [_ROW[r] for r in _STAT_ROWS[:-1]]
     res = {}
@@ -242,17 +246,20 @@ def bca_measurements_from_tables(counts, hu_sums, present, spacing_xyz, vertebra
 def bca_measurements(ctx: Context, ct: np.ndarray, regions: np.ndarray, parts: np.ndarray, spacing_xyz,
                      vertebrae=None, return_tissues: bool = False, median_filtering: bool = False, orientation="LPS",
                      body_parts_override=None):
-    """CT (z,y,x) int16 + body_regions + body_parts -> bca-measurements dict (+ tissues array).
+    """CT (z,y,x) + body_regions + body_parts -> bca-measurements dict (+ tissues array).  An int16-exact CT runs as int16, any
+    other as float64 (measurements.ct_for_stats).
     median_filtering: subclassify on the 3x3 in-plane median of the CT (run_pipeline(median_filtering=True))."""
     if ct.shape != regions.shape or ct.shape != parts.shape:
         raise ValueError("image, body_regions and body_parts must have the same shape")
     shape = ct.shape
-    d_ct = ctx.from_numpy(np.ascontiguousarray(ct, dtype=np.int16))
+    from .measurements import ct_for_stats
+    ct, ct_f64 = ct_for_stats(ct, "bca: CT")
+    d_ct = ctx.from_numpy(np.ascontiguousarray(ct))
     d_rg = ctx.from_numpy(np.ascontiguousarray(regions, dtype=np.uint8))
     d_pt = ctx.from_numpy(np.ascontiguousarray(parts, dtype=np.uint8))
     try:
         out, tis = bca_measurements_device(ctx, d_ct, d_rg, d_pt, shape, spacing_xyz, vertebrae, return_tissues,
-                                           median_filtering, orientation, body_parts_override)
+                                           median_filtering, orientation, body_parts_override, ct_f64=ct_f64)
         if return_tissues:
             t = tis.download(shape, np.uint8)
             tis.free()
@@ -265,13 +272,15 @@ def bca_measurements(ctx: Context, ct: np.ndarray, regions: np.ndarray, parts: n
 
 def bca_measurements_device(ctx: Context, d_ct: DeviceBuffer, d_rg: DeviceBuffer, d_pt: DeviceBuffer, shape, spacing_xyz,
                             vertebrae=None, return_tissues: bool = False, median_filtering: bool = False,
-                            orientation="LPS", body_parts_override=None):
-    """`bca_measurements` on resident (z,y,x) buffers (int16 CT, uint8 regions / parts) -> (dict, tissues buffer | None)."""
+                            orientation="LPS", body_parts_override=None, ct_f64: bool = False):
+    """`bca_measurements` on resident (z,y,x) buffers (int16 CT, or float64 with `ct_f64`; uint8 regions / parts)
+    -> (dict, tissues buffer | None)."""
     d_med = None
     try:
         if median_filtering:
-            d_med = median_filter_inplane(ctx, d_ct, shape, slice_axis_from_orientation(orientation))
-        tis, counts, hu_sums = tissue_aggregate(ctx, d_ct, d_rg, d_pt, shape, want_tissues=return_tissues, ct_rules=d_med)
+            d_med = median_filter_inplane(ctx, d_ct, shape, slice_axis_from_orientation(orientation), ct_f64=ct_f64)
+        tis, counts, hu_sums = tissue_aggregate(ctx, d_ct, d_rg, d_pt, shape, want_tissues=return_tissues, ct_rules=d_med,
+                                                ct_f64=ct_f64)
         present = slice_label_presence(ctx, d_rg, shape)
         out = bca_measurements_from_tables(counts, hu_sums, present, spacing_xyz, vertebrae, body_parts_override)
         return out, tis

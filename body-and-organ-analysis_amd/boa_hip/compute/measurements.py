@@ -39,11 +39,14 @@ def compute_measurements(ct_path: pathlib.Path, segmentation_folder: pathlib.Pat
     pending = {m: pool.submit(nifti.load, path_of(m)) for m in ordered if path_of(m).exists()}
     pool.shutdown(wait=False)
     data, _, hdr = nifti.load(ct_path)
-    # SimpleITK view (z,y,x) of the file, int16 HU, made on the device (a 512^3 host transpose costs ~0.5 s)
-    from .util import require_int16_exact
-    d_file = DevArray.from_numpy(ctx, data if (data.dtype == np.int16 and not nifti.is_scaled(hdr))
-                                 else require_int16_exact(nifti.fdata(data, hdr), str(ct_path)))
-    d_ct = d_file.transpose((2, 1, 0)).contiguous(np.int16, force_copy=True)
+    # SimpleITK view (z,y,x) of the file, made on the device (a 512^3 host transpose costs ~0.5 s): int16 HU when the values
+    # are int16-exact, otherwise get_fdata()'s float64 for the float statistics path (M.ct_for_stats decides)
+    if data.dtype == np.int16 and not nifti.is_scaled(hdr) and not M.force_float_stats():
+        values, ct_f64 = data, False
+    else:
+        values, ct_f64 = M.ct_for_stats(nifti.fdata(data, hdr), str(ct_path))
+    d_file = DevArray.from_numpy(ctx, values)
+    d_ct = d_file.transpose((2, 1, 0)).contiguous(np.float64 if ct_f64 else np.int16, force_copy=True)
     d_file.free()
     spacing = tuple(float(v) for v in hdr.get_zooms())
     am = asd = None
@@ -64,7 +67,8 @@ def compute_measurements(ct_path: pathlib.Path, segmentation_folder: pathlib.Pat
                 raise ValueError("The spacing of the image and of the segmentation should be the same")
             if model_name == "total":
                 meas, d_mask = M.total_measurements(ctx, None, None, label_map, spacing, cnr_adjustment=cnr_adjustment,
-                                                    d_ct=d_ct.buf, d_lab=d_seg.buf, shape=d_ct.shape, mask_on_device=True)
+                                                    d_ct=d_ct.buf, d_lab=d_seg.buf, shape=d_ct.shape, mask_on_device=True,
+                                                    ct_f64=ct_f64)
                 measurements["segmentations"].update(meas["segmentations"])
                 if "cnr_adjusted" in meas:
                     measurements["cnr_adjusted"] = meas["cnr_adjusted"]
@@ -75,15 +79,20 @@ def compute_measurements(ct_path: pathlib.Path, segmentation_folder: pathlib.Pat
                 finally:
                     fat.free()
             else:
-                hist = M.label_hu_histogram(ctx, d_ct.buf, d_seg.buf, d_ct.size)
-                measurements["segmentations"][model_name] = M._metrics_from_hist(hist, label_map, am, asd, spacing)
+                if ct_f64:
+                    measurements["segmentations"][model_name], hist = M._metrics_from_groups(ctx, d_ct.buf, d_seg.buf, d_ct.size,
+                                                                                             label_map, am, asd, spacing)
+                else:
+                    hist = M.label_hu_histogram(ctx, d_ct.buf, d_seg.buf, d_ct.size)
+                    measurements["segmentations"][model_name] = M._metrics_from_hist(hist, label_map, am, asd, spacing)
                 if cnr_adjustment and model_name in label_maps.cnr_adjusted_regions():
                     if am is None or asd is None:   # (:307-313)
                         logger.warning("Skipping CNR-adjusted measurements for %s: autochthon reference is unavailable (the "
                                        "'total' model did not run or did not produce a usable autochthon mask).", model_name)
                     else:
                         adj = M.cnr_adjusted_region_metrics(ctx, d_ct.buf, d_seg.buf, d_ct.shape, label_map,
-                                                            label_maps.cnr_adjusted_regions()[model_name], hist, am, asd, spacing)
+                                                            label_maps.cnr_adjusted_regions()[model_name], hist, am, asd, spacing,
+                                                            ct_f64=ct_f64)
                         measurements.setdefault("cnr_adjusted", {}).update(adj)
         finally:
             d_seg.free()

@@ -13,10 +13,16 @@ histogram).
 Exactness: counts, min, max, median, percentiles (numpy 'linear' interpolation restated operation for operation),
 mean (exact integer sum / n) are bit-identical to numpy on the same integer data; std differs by summation order
 only (<= 1e-12 relative).
+
+CTs that are not int16-exact (float-valued, scaled, out of range: `require_int16_exact` refuses them) take the float64 path: the
+values `get_fdata()` returns stay float64 on the device, boa_group_stats_f64 returns count / sum / centred sum of squares / min /
+max and the six order statistics behind median and quartiles per label group (radix select: exact), and `stats_from_order`
+forms the reference's statistics from them.  BOA_STATS_FLOAT=1 sends int16-exact CTs down that path as well (cross-check).
 """
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Any, Dict, Iterable, Optional, Tuple
 
 import numpy as np
@@ -102,6 +108,163 @@ def _metrics(st: Optional[dict], ml_per_voxel: float, auto_mean, auto_std, cnr_n
     return out
 
 
+# ---- statistics of float64 voxels (CTs that are not int16-exact) -----------------------------------------
+STATS_F64_COLS = 10   # boa_group_stats_f64: min, max, sum, m2, order statistics of q = 1/4, 1/2, 3/4 (floor rank, ceil rank)
+
+
+def force_float_stats() -> bool:
+    """BOA_STATS_FLOAT=1: int16-exact CTs take the float64 statistics path too (to compare the two paths on the same data)."""
+    return os.environ.get("BOA_STATS_FLOAT", "") not in ("", "0")
+
+
+def ct_for_stats(values: np.ndarray, what: str = "CT") -> Tuple[np.ndarray, bool]:
+    """-> (array to upload, is_float): the int16 array when `require_int16_exact` accepts the values (today's histogram path),
+    otherwise the values as float64 for the float path.  NaN / +-inf are refused: `what` names the file."""
+    from .compute.util import require_int16_exact
+    values = np.asarray(values)
+    if not force_float_stats():
+        try:
+            with np.errstate(invalid="ignore"):       # (NaN / inf -> int16 in the check; they are refused below)
+                return require_int16_exact(values, what), False
+        except ValueError:
+            pass
+    f = np.ascontiguousarray(values, dtype=np.float64)
+    if not np.isfinite(f).all():
+        raise ValueError(f"{what}: the CT holds {int((~np.isfinite(f)).sum())} non-finite voxel values (NaN or inf); HU statistics "
+                         "are undefined on them")
+    return f, True
+
+
+def stats_from_order(count: int, total: float, m2: float, vmin: float, vmax: float, order) -> Optional[Dict[str, float]]:
+    """The reference's eight statistics of one voxel group from what the device returns: `count` voxels, their sum `total`, the
+    centred sum of squares `m2` about total / count, min, max and `order` = the sorted group's elements at the 0-based ranks
+    floor / ceil of (count-1)*q for q = 0.25, 0.5, 0.75.  np.percentile's linear rule (`_lerp`, as in `stats_from_hist`); the
+    median is np.median's mean of the two middle elements, which can differ from the lerp form in the last bit.  None for an
+    empty group."""
+    n = int(count)
+    if n == 0:
+        return None
+    o = [float(v) for v in order]
+
+    def percentile(p: float, lo: float, hi: float) -> float:
+        virt = (n - 1) * (p / 100.0)
+        return float(_lerp(lo, hi, virt - int(np.floor(virt))))
+
+    mean = float(np.float64(total) / np.float64(n))
+    return {"n": n, "mean": mean, "std": float(np.sqrt(np.float64(m2) / np.float64(n))), "min": float(vmin), "max": float(vmax),
+            "median": o[2] if n % 2 else (o[2] + o[3]) / 2.0, "p25": percentile(25, o[0], o[1]), "p75": percentile(75, o[4], o[5])}
+
+
+def group_stats_f64(ctx: Context, d_ct: DeviceBuffer, d_labels: DeviceBuffer, n: int, lut: np.ndarray, n_groups: int):
+    """boa_group_stats_f64 -> [stats dict | None per group].  lut: uint8[256], label value -> group, 0xFF = not measured."""
+    lut = np.ascontiguousarray(lut, dtype=np.uint8)
+    counts = np.zeros(n_groups, dtype=np.uint64)
+    st = np.zeros((n_groups, STATS_F64_COLS), dtype=np.float64)
+    check(ctx.lib.boa_group_stats_f64(ctx.h, d_ct.vp, d_labels.vp, int(n), lut.ctypes.data_as(C.c_void_p), int(n_groups),
+                                      counts.ctypes.data_as(C.c_void_p), st.ctypes.data_as(C.c_void_p)), "boa_group_stats_f64")
+    return [stats_from_order(int(counts[g]), st[g, 2], st[g, 3], st[g, 0], st[g, 1], st[g, 4:10]) for g in range(n_groups)]
+
+
+def _group_lut(groups) -> np.ndarray:
+    """groups: [iterable of label values per group] (disjoint) -> lut."""
+    lut = np.full(256, 0xFF, dtype=np.uint8)
+    for g, labels in enumerate(groups):
+        for l in labels:
+            lut[int(l)] = g
+    return lut
+
+
+def _masked_stats_f64(ctx, d_ct, d_mask, n):
+    """stats of ct[mask != 0] for a 0/1 mask: the mask is the label volume, lut[1] = group 0."""
+    return group_stats_f64(ctx, d_ct, d_mask, n, _group_lut([[1]]), 1)[0]
+
+
+def label_hu_mask_f64(ctx: Context, d_ct, d_labels, labels, mode: int, n: int, out: DeviceBuffer, window=ADIPOSE_TISSUE):
+    """`label_hu_mask` on float64 HU: the window is compared on the float value (numpy's `ct >= lo`, `ct < lo`)."""
+    lut = _lut(labels)
+    check(ctx.lib.boa_label_hu_mask_f64(ctx.h, d_ct.vp, d_labels.vp, lut.ctypes.data_as(C.c_void_p), mode, float(window[0]),
+                                        float(window[1]), n, out.vp), "boa_label_hu_mask_f64")
+
+
+def _label_stats_f64(ctx, d_ct, d_lab, n, label_map) -> Dict[int, Optional[dict]]:
+    """{label value: stats} of every label of `label_map` from one boa_group_stats_f64 call."""
+    labels = sorted({int(l) for l in label_map.values() if 0 < int(l) < 256})
+    if not labels:
+        return {}
+    return dict(zip(labels, group_stats_f64(ctx, d_ct, d_lab, n, _group_lut([[l] for l in labels]), len(labels))))
+
+
+def _metrics_from_groups(ctx, d_ct, d_lab, n, label_map, am, asd, spacing, by_label=None):
+    """`_metrics_from_hist` for the float path -> (metrics, {label: stats})."""
+    ml = np.prod(spacing) / 1000.0
+    by_label = _label_stats_f64(ctx, d_ct, d_lab, n, label_map) if by_label is None else by_label
+    res = {region: _metrics(by_label.get(int(label)), ml, am, asd) for region, label in label_map.items()}
+    if "autochthon_left" in label_map and "autochthon_right" in label_map:
+        both = group_stats_f64(ctx, d_ct, d_lab, n, _group_lut([[label_map["autochthon_left"], label_map["autochthon_right"]]]), 1)[0]
+        res["autochthon"] = _metrics(both, ml, am, asd)
+    return res, by_label
+
+
+def _total_measurements_f64(ctx, d_ct, d_lab, shape, label_map, spacing, cnr_adjustment, model_name, mask_on_device, defer_host):
+    """`total_measurements` on a resident float64 CT: the same masks and erosions, group statistics instead of histograms."""
+    n = int(np.prod(shape))
+    ml = np.prod(spacing) / 1000.0
+    info: Dict[str, Any] = {}
+    adj: Optional[Dict[str, Any]] = None
+    d_m, d_e, d_t = ctx.alloc(max(n, 1)), ctx.alloc(max(n, 1)), ctx.alloc(max(n, 1))
+    keep_mask = None
+    try:
+        by_label = _label_stats_f64(ctx, d_ct, d_lab, n, label_map)
+        # autochthon reference: (left | right) minus fat, eroded (:42-58)
+        auto_labels = [label_map["autochthon_left"], label_map["autochthon_right"]]
+        label_hu_mask_f64(ctx, d_ct, d_lab, auto_labels, 2, n, d_m)
+        binary_erode(ctx, d_m, d_e, d_t, shape)
+        st_auto = _masked_stats_f64(ctx, d_ct, d_e, n)
+        am, asd = (st_auto["mean"], st_auto["std"]) if st_auto else (None, None)
+        seg, _ = _metrics_from_groups(ctx, d_ct, d_lab, n, label_map, am, asd, spacing, by_label)
+        # pulmonary fat (ct_pfav, :151-200): the lung labels inside the fat window, as a label volume (d_e: lobe label or 0)
+        lungs = [label_map[nm] for nm in LUNG_MASKS]
+        label_hu_mask_f64(ctx, d_ct, d_lab, lungs, 1, n, d_m)
+        check(ctx.lib.boa_copy3(ctx.h, d_lab.vp, 0, 0, (C.c_longlong * 3)(0, 0, 1), (C.c_int * 3)(1, 1, n), d_e.vp, 0, 0,
+                                (C.c_longlong * 3)(0, 0, 1)), "boa_copy3")
+        check(ctx.lib.boa_mask_assign(ctx.h, d_m.vp, n, 1, 0, d_e.vp), "boa_mask_assign")      # d_e[mask == 0] = 0
+        sides = [[label_map[nm] for nm in LUNG_MASKS if nm.endswith(side)] for side in ("left", "right")]
+        lobe = group_stats_f64(ctx, d_ct, d_e, n, _group_lut([[l] for l in lungs]), len(lungs))
+        side = group_stats_f64(ctx, d_ct, d_e, n, _group_lut(sides), 2)
+        whole = group_stats_f64(ctx, d_ct, d_e, n, _group_lut([lungs]), 1)
+        pf = {"ct_pfav_" + nm: _metrics(st, ml, am, asd) for nm, st in zip(LUNG_MASKS, lobe)}
+        pf["ct_pfav_lobe_left"], pf["ct_pfav_lobe_right"] = (_metrics(st, ml, am, asd) for st in side)
+        pf["ct_pfav_lungs"] = _metrics(whole[0], ml, am, asd)
+        if mask_on_device:
+            keep_mask = ctx.alloc(n)
+            check(ctx.lib.boa_copy3(ctx.h, d_m.vp, 0, 0, (C.c_longlong * 3)(0, 0, 1), (C.c_int * 3)(1, 1, n), keep_mask.vp, 0, 0,
+                                    (C.c_longlong * 3)(0, 0, 1)), "boa_copy3")
+            fat_mask = keep_mask
+        else:
+            fat_mask = d_m.download(shape, np.uint8)
+        if cnr_adjustment and model_name in CNR_ADJUSTED_REGIONS and am is not None and asd is not None:
+            adj = {}
+            regions = [r for r in label_map if r in CNR_ADJUSTED_REGIONS[model_name]]
+            for region in regions:
+                is_auto = "autochthon" in region
+                label_hu_mask_f64(ctx, d_ct, d_lab, [label_map[region]], 2 if is_auto else 0, n, d_m)
+                binary_erode(ctx, d_m, d_e, d_t, shape)
+                st = _masked_stats_f64(ctx, d_ct, d_e, n) if by_label.get(int(label_map[region])) else None
+                adj[region] = _metrics(st, ml, am, asd, cnr_none=region.partition("_")[0] == "autochthon")
+            if {"autochthon_left", "autochthon_right"} <= set(regions):
+                present = any(by_label.get(int(l)) for l in auto_labels)      # union, minus fat, eroded == the reference mask above
+                adj["autochthon"] = _metrics(st_auto if present else None, ml, am, asd, cnr_none=True)
+        info["autochthon_mean"], info["autochthon_std"] = am, asd
+        keep_mask = None
+        out = {"segmentations": {model_name: {**seg, **pf}}, "info": info}      # key order of the reference's dict
+        if adj is not None:
+            out["cnr_adjusted"] = adj
+        return ((lambda: out) if defer_host else out), fat_mask
+    finally:
+        for b in (d_m, d_e, d_t) + ((keep_mask,) if keep_mask is not None else ()):
+            b.free()
+
+
 # ---- device passes --------------------------------------------------------------------------------------
 def _label_hu_histogram_local(ctx: Context, d_ct: DeviceBuffer, d_labels: DeviceBuffer, n: int,
                               d_mask: Optional[DeviceBuffer] = None) -> np.ndarray:
@@ -165,11 +328,15 @@ _masked_stats = _masked_stats_local
 
 def metrics_for_each_region(ctx: Context, ct: np.ndarray, region_data: np.ndarray, label_map: Dict[str, int],
                             autochthon_mean, autochthon_std, img_spacing) -> Dict[str, Any]:
-    """metrics_for_each_region (:203-241), cnr_adjustment=False, from one histogram pass."""
+    """metrics_for_each_region (:203-241), cnr_adjustment=False, from one histogram pass (int16-exact CT) or one group
+    statistics call (any other CT, as float64)."""
     n = ct.size
-    d_ct = ctx.from_numpy(np.ascontiguousarray(ct, dtype=np.int16))
+    ct, is_float = ct_for_stats(ct)
+    d_ct = ctx.from_numpy(np.ascontiguousarray(ct))
     d_lab = ctx.from_numpy(np.ascontiguousarray(region_data, dtype=np.uint8))
     try:
+        if is_float:
+            return _metrics_from_groups(ctx, d_ct, d_lab, n, label_map, autochthon_mean, autochthon_std, img_spacing)[0]
         hist = label_hu_histogram(ctx, d_ct, d_lab, n)
     finally:
         d_ct.free()
@@ -191,11 +358,13 @@ def _metrics_from_hist(hist, label_map, am, asd, spacing):
 
 
 def cnr_adjusted_region_metrics(ctx: Context, d_ct: DeviceBuffer, d_lab: DeviceBuffer, shape, label_map: Dict[str, int],
-                                regions: Iterable[str], hist: np.ndarray, am, asd, spacing) -> Dict[str, Any]:
+                                regions: Iterable[str], hist, am, asd, spacing, ct_f64: bool = False) -> Dict[str, Any]:
     """`metrics_for_each_region(..., cnr_adjustment=True)` for the `regions` of a model other than `total`
     (BOA/compute/measurements.py:318-341; e.g. heartchambers_highres / pulmonary_artery): the region's mask (autochthon names:
     minus fat) is eroded with the 6^3 kernel before the statistics (metrics_for_region, :85-93).  `hist`: the model's
-    per-label histogram (tells which labels are present)."""
+    per-label histogram (tells which labels are present).  `ct_f64`: `d_ct` holds float64 and `hist` is the {label: stats}
+    table of `_metrics_from_groups`."""
+    mask_of, stats_of = (label_hu_mask_f64, _masked_stats_f64) if ct_f64 else (label_hu_mask, _masked_stats_local)
     shape = tuple(int(v) for v in shape)
     n = int(np.prod(shape))
     ml = np.prod(spacing) / 1000.0
@@ -204,9 +373,10 @@ def cnr_adjusted_region_metrics(ctx: Context, d_ct: DeviceBuffer, d_lab: DeviceB
     try:
         for region in [r for r in label_map if r in set(regions)]:
             is_auto = "autochthon" in region
-            label_hu_mask(ctx, d_ct, d_lab, [label_map[region]], 2 if is_auto else 0, n, d_m)
+            mask_of(ctx, d_ct, d_lab, [label_map[region]], 2 if is_auto else 0, n, d_m)
             binary_erode(ctx, d_m, d_e, d_t, shape)
-            st = _masked_stats_local(ctx, d_ct, d_e, n) if hist[label_map[region]].any() else None
+            present = bool(hist.get(int(label_map[region]))) if ct_f64 else hist[label_map[region]].any()
+            st = stats_of(ctx, d_ct, d_e, n) if present else None
             out[region] = _metrics(st, ml, am, asd, cnr_none=region.partition("_")[0] == "autochthon")
     finally:
         for b in (d_m, d_e, d_t):
@@ -217,7 +387,7 @@ def cnr_adjusted_region_metrics(ctx: Context, d_ct: DeviceBuffer, d_lab: DeviceB
 def total_measurements(ctx: Context, ct: Optional[np.ndarray], total_seg: Optional[np.ndarray], label_map: Dict[str, int],
                        spacing, cnr_adjustment: bool = True, model_name: str = "total", d_ct: Optional[DeviceBuffer] = None,
                        d_lab: Optional[DeviceBuffer] = None, shape=None, mask_on_device: bool = False, shard=None,
-                       defer_host: bool = False):
+                       defer_host: bool = False, ct_f64: bool = False):
     """compute_measurements (:244-343) for models == ["total"] on (z,y,x) arrays.  Returns (measurements dict, ct_pfav
     mask).  `defer_host=True`: the device passes run now, the ~120 per-label order statistics (pure numpy on the downloaded
     histogram) are returned as a function `finish() -> measurements dict` in place of the dict, so that a caller can run them
@@ -228,15 +398,29 @@ def total_measurements(ctx: Context, ct: Optional[np.ndarray], total_seg: Option
     agg_shard.ERODE_REACH planes towards its neighbours, and planes [a, b) of them are the ones the rank owns.  Masks and
     erosions run on the whole slab (the halo supplies the neighbours' voxels; its own planes are discarded), histograms only
     over the owned planes and are summed over the ranks -- every rank returns the volume's measurements; the returned
-    ct_pfav mask covers the slab."""
+    ct_pfav mask covers the slab.
+
+    A host `ct` that is not int16-exact (or any, with BOA_STATS_FLOAT=1) is uploaded as float64 and measured by the float path;
+    `ct_f64=True` says that a resident `d_ct` holds float64."""
     own = d_ct is None
     if own:
         if ct.shape != total_seg.shape:
             raise ValueError("The spacing of the image and of the segmentation should be the same")  # shape contract
         shape = ct.shape
-        d_ct = ctx.from_numpy(np.ascontiguousarray(ct, dtype=np.int16))
+        ct, ct_f64 = ct_for_stats(ct)
+        d_ct = ctx.from_numpy(np.ascontiguousarray(ct))
         d_lab = ctx.from_numpy(np.ascontiguousarray(total_seg, dtype=np.uint8))
     shape = tuple(int(v) for v in shape)
+    if ct_f64:
+        try:
+            if shard is not None:
+                raise NotImplementedError("total_measurements: z-slab sharding (agg_shard) of a float64 CT is not implemented")
+            return _total_measurements_f64(ctx, d_ct, d_lab, shape, label_map, spacing, cnr_adjustment, model_name, mask_on_device,
+                                           defer_host)
+        finally:
+            if own:
+                d_ct.free()
+                d_lab.free()
     n = int(np.prod(shape))
     ml = np.prod(spacing) / 1000.0
     meas: Dict[str, Any] = {"segmentations": {}, "info": {}}

@@ -223,15 +223,20 @@ class BcaPipelineHip:
         "vertebrae" (dict)}.  `total_seg`: the `total` label volume on the same grid (vertebra groups), optional.
         The CT is uploaded once; every stage (nets, post-processing, LPS reload, tissues, tables) works on resident
         buffers (`run_resident`), the three label volumes are downloaded at the end."""
-        if np.asarray(ct).dtype != np.int16:
-            from .compute.util import require_int16_exact
-            require_int16_exact(ct, "bca: CT")    # tissue rules / HU sums run on int16 HU: never truncate or wrap silently
+        # tissue rules / HU sums run on int16 HU when the values are int16-exact, otherwise on the float64 values (never truncated
+        # or wrapped silently); the nets see the array as it came either way
+        from .measurements import ct_for_stats, force_float_stats
+        ct_f64 = False
+        if np.asarray(ct).dtype != np.int16 or force_float_stats():
+            ct_f64 = ct_for_stats(ct, "bca: CT")[1]
+            if ct_f64 and np.asarray(ct).dtype not in (np.int16, np.float64):
+                ct = np.asarray(ct, dtype=np.float64)      # what get_fdata() hands to the reference
         d_ct = DevArray.from_numpy(self.ctx, SegmentationTask._supported(ct))
         d_tot = None if total_seg is None else DevArray.from_numpy(self.ctx, np.ascontiguousarray(total_seg, dtype=np.uint8))
         res = None
         try:
             res = self.run_resident(d_ct, affine, d_tot, median_filtering, examined_body_region, crop_body, force_split, raw_parts,
-                                    raw_regions, done_parts, done_regions)
+                                    raw_regions, done_parts, done_regions, ct_f64=ct_f64)
             return {"body_parts": res["body_parts"].download(), "body_regions": res["body_regions"].download(),
                     "tissues": res["tissues"].download(), "bca_measurements": res["bca_measurements"],
                     "vertebrae": res["vertebrae"], "examined_body_part": res["examined_body_part"]}
@@ -243,11 +248,12 @@ class BcaPipelineHip:
     def run_resident(self, d_ct: DevArray, affine: np.ndarray, d_total: Optional[DevArray] = None,
                      median_filtering: bool = False, examined_body_region: Optional[str] = None, crop_body: bool = False,
                      force_split: bool = False, raw_parts: Optional[np.ndarray] = None, raw_regions: Optional[np.ndarray] = None,
-                     done_parts: Optional[np.ndarray] = None, done_regions: Optional[np.ndarray] = None) -> dict:
+                     done_parts: Optional[np.ndarray] = None, done_regions: Optional[np.ndarray] = None, ct_f64: bool = False) -> dict:
         """`run` on device-resident inputs (CT and `total` labels in the file's axis order; neither is freed here): the three
         label volumes come back as contiguous DevArrays in file axis order (the caller frees them), the tables as dicts.
         `d_total` may be a callable returning the DevArray: it is called when the vertebra table needs the `total` labels,
-        i.e. after both nets and their post-processing (boa_hip/lanes.py runs `total` on a second stream meanwhile)."""
+        i.e. after both nets and their post-processing (boa_hip/lanes.py runs `total` on a second stream meanwhile).
+        `ct_f64`: the tissue stage reads the CT as float64 (a CT that is not int16-exact) instead of int16."""
         ctx = self.ctx
         affine = np.asarray(affine, dtype=np.float64)
         live = []
@@ -272,7 +278,7 @@ class BcaPipelineHip:
                 _, laff = orientation.with_axcodes(np.empty(d_ct.shape, dtype=np.uint8), affine, "LPS")
                 sp = np.sqrt(np.sum(np.asarray(laff, dtype=np.float64)[:3, :3] ** 2, axis=0))
                 spacing = (float(sp[0]), float(sp[1]), float(sp[2]))
-                ct_l = self._lps_zyx(d_ct, affine, np.int16)
+                ct_l = self._lps_zyx(d_ct, affine, np.float64 if ct_f64 else np.int16)
                 rg_l = self._lps_zyx(d_regions, affine)
                 pt_l = self._lps_zyx(d_parts, affine)
                 live += [ct_l, rg_l, pt_l]
@@ -295,11 +301,14 @@ class BcaPipelineHip:
                     vertebrae = bca.create_vertebrae_info(ctx, None, label_maps.CLASS_MAP_TOTAL, flags, d_total=tot_l.buf,
                                                           shape=tot_l.shape)
                 if self.agg is not None and self.agg[0].world > 1 and not median_filtering:
+                    if ct_f64:
+                        raise NotImplementedError("bca: z-slab sharding (agg_shard) of a float64 CT is not implemented")
                     js, d_tis = bca.bca_measurements_device_sharded(ctx, self.agg, ct_l.buf, rg_l.buf, pt_l.buf, ct_l.shape, spacing,
                                                                     vertebrae or None, "LPS", flags if examined_body_region else None)
                 else:
                     js, d_tis = bca.bca_measurements_device(ctx, ct_l.buf, rg_l.buf, pt_l.buf, ct_l.shape, spacing, vertebrae or None,
-                                                            True, median_filtering, "LPS", flags if examined_body_region else None)
+                                                            True, median_filtering, "LPS", flags if examined_body_region else None,
+                                                            ct_f64=ct_f64)
                 tis_l = DevArray(ctx, d_tis, ct_l.shape, np.uint8)
                 live.append(tis_l)
                 # back to the file's axis order: (z,y,x) LPS -> (x,y,z) LPS -> file orientation

@@ -489,15 +489,18 @@ struct Lut256 {
     unsigned char v[256];
 };
 
-__global__ __launch_bounds__(256) void k_label_hu_mask(const short* __restrict__ ct, const unsigned char* __restrict__ labels,
-                                                       Lut256 lut, int mode, int lo, int hi, size_t n,
+// T: the CT's value type, B: the type the window is compared in (int16 HU as int; float64 HU as double, i.e. numpy's `ct >= lo` /
+// `ct < lo` on the float value itself, no rounding to integer HU)
+template <typename T, typename B>
+__global__ __launch_bounds__(256) void k_label_hu_mask(const T* __restrict__ ct, const unsigned char* __restrict__ labels,
+                                                       Lut256 lut, int mode, B lo, B hi, size_t n,
                                                        unsigned char* __restrict__ out) {
     size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     const size_t stride = (size_t)gridDim.x * 256;
     for (; i < n; i += stride) {
         bool m = lut.v[labels[i]] != 0;
         if (mode != 0) {
-            const int hu = ct[i];
+            const B hu = ct[i];
             const bool inside = hu >= lo && hu <= hi;
             m = m && (mode == 1 ? inside : !inside);
         }
@@ -505,20 +508,31 @@ __global__ __launch_bounds__(256) void k_label_hu_mask(const short* __restrict__
     }
 }
 
-extern "C" int boa_label_hu_mask(boa_ctx* c, const int16_t* dev_ct, const uint8_t* dev_labels, const uint8_t* host_lut,
-                                 int mode, int hu_lo, int hu_hi, size_t n, uint8_t* dev_mask_out) {
-    BOA_REQUIRE(c && dev_labels && host_lut && dev_mask_out && (mode == 0 || dev_ct), "boa_label_hu_mask: bad argument");
-    BOA_REQUIRE(mode >= 0 && mode <= 2, "boa_label_hu_mask: mode %d", mode);
+template <typename T, typename B>
+static int label_hu_mask(boa_ctx* c, const char* what, const T* dev_ct, const uint8_t* dev_labels, const uint8_t* host_lut, int mode, B hu_lo,
+                         B hu_hi, size_t n, uint8_t* dev_mask_out) {
+    BOA_REQUIRE(c && dev_labels && host_lut && dev_mask_out && (mode == 0 || dev_ct), "%s: bad argument", what);
+    BOA_REQUIRE(mode >= 0 && mode <= 2, "%s: mode %d", what, mode);
     if (n == 0) return BOA_OK;
     Lut256 lut;
     memcpy(lut.v, host_lut, 256);
     int grid = (int)std::min<size_t>((n + 255) / 256, (size_t)c->cu_count * 32);
-    KernelTimer t(c, BOA_K_AGG, 0, (double)n * 4.0);
-    hipLaunchKernelGGL(k_label_hu_mask, dim3(grid), dim3(256), 0, c->stream, dev_ct, dev_labels, lut, mode, hu_lo, hu_hi,
+    KernelTimer t(c, BOA_K_AGG, 0, (double)n * (2.0 + sizeof(T)));
+    hipLaunchKernelGGL((k_label_hu_mask<T, B>), dim3(grid), dim3(256), 0, c->stream, dev_ct, dev_labels, lut, mode, hu_lo, hu_hi,
                        n, dev_mask_out);
     t.stop();
     BOA_HIP_TRY(hipGetLastError());
     return BOA_OK;
+}
+
+extern "C" int boa_label_hu_mask(boa_ctx* c, const int16_t* dev_ct, const uint8_t* dev_labels, const uint8_t* host_lut,
+                                 int mode, int hu_lo, int hu_hi, size_t n, uint8_t* dev_mask_out) {
+    return label_hu_mask<short, int>(c, "boa_label_hu_mask", dev_ct, dev_labels, host_lut, mode, hu_lo, hu_hi, n, dev_mask_out);
+}
+
+extern "C" int boa_label_hu_mask_f64(boa_ctx* c, const double* dev_ct, const uint8_t* dev_labels, const uint8_t* host_lut,
+                                     int mode, double hu_lo, double hu_hi, size_t n, uint8_t* dev_mask_out) {
+    return label_hu_mask<double, double>(c, "boa_label_hu_mask_f64", dev_ct, dev_labels, host_lut, mode, hu_lo, hu_hi, n, dev_mask_out);
 }
 
 __global__ __launch_bounds__(256) void k_label_select(const unsigned char* __restrict__ labels, size_t n, int mode,

@@ -219,15 +219,18 @@ extern "C" int boa_fill_holes_2d(boa_ctx* c, const uint8_t* dev_mask, int Z, int
 }
 
 // ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void cswap(short& a, short& b) {
-    const short lo = a < b ? a : b, hi = a < b ? b : a;
+template <typename T>
+__device__ __forceinline__ void cswap(T& a, T& b) {
+    const T lo = a < b ? a : b, hi = a < b ? b : a;
     a = lo;
     b = hi;
 }
 
-// flat_axis: the axis (0 = z, 1 = y, 2 = x of the [Z][Y][X] array) with kernel size 1
-__global__ __launch_bounds__(256) void k_median3_inplane(const short* __restrict__ in, int Z, int Y, int X, int flat_axis,
-                                                         short* __restrict__ out) {
+// flat_axis: the axis (0 = z, 1 = y, 2 = x of the [Z][Y][X] array) with kernel size 1.  T = short (int16 HU) or double: the
+// network only moves values, so the float median is one of the nine inputs, equal to numpy's under `==`.
+template <typename T>
+__global__ __launch_bounds__(256) void k_median3_inplane(const T* __restrict__ in, int Z, int Y, int X, int flat_axis,
+                                                         T* __restrict__ out) {
     const size_t n = (size_t)Z * Y * X;
     size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -238,7 +241,7 @@ __global__ __launch_bounds__(256) void k_median3_inplane(const short* __restrict
     const int pos[3] = {z, y, x};
     const int a0 = flat_axis == 0 ? 1 : 0, a1 = flat_axis == 2 ? 1 : 2;
     const size_t strides[3] = {(size_t)Y * X, (size_t)X, 1};
-    short v[9];
+    T v[9];
 #pragma unroll
     for (int d0 = -1; d0 <= 1; ++d0)
 #pragma unroll
@@ -260,16 +263,25 @@ __global__ __launch_bounds__(256) void k_median3_inplane(const short* __restrict
     out[i] = v[4];
 }
 
-extern "C" int boa_median3_inplane(boa_ctx* c, const int16_t* dev_in, int Z, int Y, int X, int flat_axis, int16_t* dev_out) {
-    BOA_REQUIRE(c && dev_in && dev_out && dev_in != dev_out && Z > 0 && Y > 0 && X > 0, "boa_median3_inplane: bad argument");
-    BOA_REQUIRE(flat_axis >= 0 && flat_axis <= 2, "boa_median3_inplane: flat_axis %d", flat_axis);
+template <typename T>
+static int median3_inplane(boa_ctx* c, const char* what, const T* dev_in, int Z, int Y, int X, int flat_axis, T* dev_out) {
+    BOA_REQUIRE(c && dev_in && dev_out && dev_in != dev_out && Z > 0 && Y > 0 && X > 0, "%s: bad argument", what);
+    BOA_REQUIRE(flat_axis >= 0 && flat_axis <= 2, "%s: flat_axis %d", what, flat_axis);
     const size_t n = (size_t)Z * Y * X;
-    KernelTimer t(c, BOA_K_MORPH, 0, (double)n * 4.0);
-    hipLaunchKernelGGL(k_median3_inplane, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, dev_in, Z, Y, X, flat_axis,
+    KernelTimer t(c, BOA_K_MORPH, 0, (double)n * 2.0 * sizeof(T));
+    hipLaunchKernelGGL(k_median3_inplane<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, dev_in, Z, Y, X, flat_axis,
                        dev_out);
     t.stop();
     BOA_HIP_TRY(hipGetLastError());
     return BOA_OK;
+}
+
+extern "C" int boa_median3_inplane(boa_ctx* c, const int16_t* dev_in, int Z, int Y, int X, int flat_axis, int16_t* dev_out) {
+    return median3_inplane<int16_t>(c, "boa_median3_inplane", dev_in, Z, Y, X, flat_axis, dev_out);
+}
+
+extern "C" int boa_median3_inplane_f64(boa_ctx* c, const double* dev_in, int Z, int Y, int X, int flat_axis, double* dev_out) {
+    return median3_inplane<double>(c, "boa_median3_inplane_f64", dev_in, Z, Y, X, flat_axis, dev_out);
 }
 
 __global__ __launch_bounds__(256) void k_mask_assign(const unsigned char* __restrict__ mask, size_t n, int invert, int value,

@@ -355,6 +355,31 @@ int boa_label_hu_histogram(boa_ctx* ctx, const int16_t* dev_ct, const uint8_t* d
 int boa_label_hu_mask(boa_ctx* ctx, const int16_t* dev_ct, const uint8_t* dev_labels, const uint8_t* host_lut,
                       int mode, int hu_lo, int hu_hi, size_t n_voxels, uint8_t* dev_mask_out);
 
+/* ---- the same measurements on CT values held as float64 (`get_fdata()` of a float-valued, scaled or out-of-int16-range CT;
+ * the reference computes on whatever array its reader hands over: BOA/compute/measurements.py:257-258, BCA/report/builder.py).
+ *
+ * boa_group_stats_f64: what `np.mean / std / min / max / median / percentile(hu_region, 25 | 75)` of metrics_for_region
+ * (BOA/compute/measurements.py:95-112) need, for up to 255 voxel groups at once.  host_lut[256] maps a label value to its group
+ * (0xFF: not measured); label unions are LUT entries with the same group, a 0/1 mask with lut[1] = 0 is the masked form.
+ *   host_count[n_groups]                               voxels per group (exact)
+ *   host_stats[n_groups][BOA_GROUP_STATS_F64_COLS]     min, max, sum, m2, then the order statistics (0-based ranks in the sorted
+ *       group) floor((count-1)/4), ceil((count-1)/4), floor((count-1)/2), ceil((count-1)/2), floor(3(count-1)/4), ceil(3(count-1)/4)
+ *   m2 = sum((x - sum / count)^2), taken in a second pass about the fp64 mean as np.std does.
+ * min, max and the order statistics are exact (radix select on the 64 bits of the values, eight passes of 9 B per voxel; no
+ * sort, no download of the volume); sum and m2 are fp64 sums whose last bits depend on the order of the atomic adds.  Values
+ * must be finite (the host checks before it uploads).  Rows of empty groups are zero.  Synchronous. */
+#define BOA_GROUP_STATS_F64_COLS 10
+int boa_group_stats_f64(boa_ctx* ctx, const double* dev_ct, const uint8_t* dev_labels, size_t n_voxels, const uint8_t* host_lut,
+                        int n_groups, uint64_t* host_count, double* host_stats);
+/* boa_label_hu_mask on float64 HU: the window is compared on the float value itself (`ct >= lo`, `ct < lo`: no rounding). */
+int boa_label_hu_mask_f64(boa_ctx* ctx, const double* dev_ct, const uint8_t* dev_labels, const uint8_t* host_lut,
+                          int mode, double hu_lo, double hu_hi, size_t n_voxels, uint8_t* dev_mask_out);
+/* boa_tissue_aggregate on float64 HU: the derivation rules compare the float value (-29.5 is neither muscle nor adipose tissue),
+ * counts and the tissue map are exact, hu_sums is dev double [Z][2][8]. */
+int boa_tissue_aggregate_f64(boa_ctx* ctx, const double* dev_ct, const double* dev_ct_rules, const uint8_t* dev_regions,
+                             const uint8_t* dev_parts, uint8_t* dev_tissues_out, int Z, int Y, int X, uint32_t* dev_counts,
+                             double* dev_hu_sums);
+
 /* erode_region (BOA/compute/measurements.py:61-71): binary erosion with a k^3 ones footprint whose anchor is
  * the centre of the end-padded (k+1)^3 footprint for even k; voxels outside the volume count as set.
  * Separable min filter, three passes. tmp: dev uint8 scratch of the same size. */
@@ -441,6 +466,8 @@ int boa_label_overlay(boa_ctx* ctx, const uint8_t* dev_part, size_t n, uint8_t* 
 /* subclassify_tissues(median_filtering=True) (BCA/tissue/subclassification.py:21-36): scipy.ndimage.median_filter
  * with size 3 on two axes and 1 on `flat_axis` (0 = z, 1 = y, 2 = x of the [Z][Y][X] array), mode="reflect". */
 int boa_median3_inplane(boa_ctx* ctx, const int16_t* dev_in, int Z, int Y, int X, int flat_axis, int16_t* dev_out);
+/* the same selection on float64 values (exact: the result is one of the nine inputs) */
+int boa_median3_inplane_f64(boa_ctx* ctx, const double* dev_in, int Z, int Y, int X, int flat_axis, double* dev_out);
 
 /* ------------------------------------------------------------------ index remaps around a task ------- */
 /* Strided 3-D gather copy with dtype conversion: the device form of as_closest_canonical / undo_canonical

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Wall time of the aggregation scan stages on the structured phantoms at 512^3 (median of 5 synchronised calls): tissue aggregate,
-label HU histogram, 6^3 erosion.  Development aid for the HBM fractions that bench.py reports as `phantom_stages`."""
+label HU histogram, 6^3 erosion; then the float leg: the same phantom as float64 (int16 + a fixed fraction) through the float64
+forms of the tissue pass and of the per-label statistics (boa_group_stats_f64: eight passes of 9 B per voxel, so the GB/s column
+is the rate of every pass).  Development aid for the HBM fractions that bench.py reports as `phantom_stages`."""
 import os
 import sys
 import time
@@ -47,4 +49,12 @@ d_m, d_o, d_t = ctx.alloc(n), ctx.alloc(n), ctx.alloc(n)
 M.label_hu_mask(ctx, d_ct, d["total"], range(1, 30), 0, n, d_m)
 timed("binary_erode_6", lambda: M.binary_erode(ctx, d_m, d_o, d_t, shape, 6), 2.0 * n)
 timed("slice_label_presence", lambda: bca.slice_label_presence(ctx, d["regions"], shape) is None, 1.0 * n)
+for b in (d_m, d_o, d_t, d_ct):
+    b.free()
+# float leg
+d_ctf = ctx.from_numpy(ct.astype(np.float64) + 0.375)
+labels = list(range(1, 118))
+lut = M._group_lut([[l] for l in labels])
+timed("tissue_aggregate f64", lambda: bca.tissue_aggregate(ctx, d_ctf, d["regions"], d["parts"], shape, ct_f64=True)[0], 11.0 * n)
+timed("group_stats_f64 x8 passes", lambda: M.group_stats_f64(ctx, d_ctf, d["total"], n, lut, len(labels)) is None, 8 * 9.0 * n)
 ctx.close()
