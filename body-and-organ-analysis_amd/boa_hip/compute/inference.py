@@ -141,7 +141,7 @@ def _segment_one(ctx, name, ct, affine, hdr, folder, fast, recompute):
                                rough_resample=model_store.TASKS[rough]["resample"], remove_outside=info.get("remove_outside"),
                                remove_outside_dilation=info.get("remove_outside_dilation"))
         names = label_maps.class_map(name)
-    nifti.save(target, seg, affine, like=hdr, extensions=[(0, nifti.label_xml(names))])
+    nifti.save_volume(target, seg, affine, ctx=ctx, like=hdr, extensions=[(0, nifti.label_xml(names))])
 
 
 def _write_total_measurements(ctx, ct_path, folder, models, cnr_adjustment, recompute):
@@ -173,7 +173,7 @@ def _run_bca_model(ctx, name, ct, affine, hdr, folder, fast_bca, bca_params, spl
     pipe = BcaPipelineHip(ctx, models.get("body_parts"), models.get("body_regions"), fast_bca=fast_bca)
     try:
         if name != "bca":
-            nifti.save(folder / f"{name}.nii.gz", pipe.inference(name, ct, affine, force_split=split), affine, like=hdr)
+            nifti.save_volume(folder / f"{name}.nii.gz", pipe.inference(name, ct, affine, force_split=split), affine, ctx=ctx, like=hdr)
             return
         total_file = folder / "total.nii.gz"
         out = pipe.run(ct, affine, total_seg=nifti.load(total_file)[0] if total_file.is_file() else None, force_split=split,
@@ -183,7 +183,7 @@ def _run_bca_model(ctx, name, ct, affine, hdr, folder, fast_bca, bca_params, spl
         for volume in ("body_parts", "body_regions", "tissues"):
             if volume in done:
                 continue
-            nifti.save(folder / f"{volume}.nii.gz", out[volume], affine, like=hdr)
+            nifti.save_volume(folder / f"{volume}.nii.gz", out[volume], affine, ctx=ctx, like=hdr)
         if out["vertebrae"]:
             with (folder / "vertebrae.json").open("w") as fh:
                 json.dump(out["vertebrae"], fh, indent=2)

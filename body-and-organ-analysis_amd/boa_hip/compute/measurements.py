@@ -75,7 +75,7 @@ def compute_measurements(ct_path: pathlib.Path, segmentation_folder: pathlib.Pat
                 am, asd = meas["info"].get("autochthon_mean"), meas["info"].get("autochthon_std")
                 fat = DevArray(ctx, d_mask, d_ct.shape, np.uint8)
                 try:
-                    nifti.save(segmentation_folder / "ct_pfav.nii.gz", fat.transpose((2, 1, 0)).download(), saff, like=shdr)
+                    nifti.save_volume(segmentation_folder / "ct_pfav.nii.gz", fat.transpose((2, 1, 0)), saff, ctx=ctx, like=shdr)
                 finally:
                     fat.free()
             else:

@@ -234,6 +234,75 @@ SAVE_THREADS = int(os.environ.get("BOA_SAVE_THREADS", "0")) or min(8, os.cpu_cou
 _GZ_BLOCK = 4 << 20
 
 
+def gzip_member(body, crc32: int, size: int) -> bytes:
+    """One gzip member (RFC 1952) around a raw deflate stream `body` of `size` payload bytes with CRC-32 `crc32`: the container
+    of write_gzip_members, whichever encoder made the body (zlib there, the device encoder in device_deflate)."""
+    total = 20 + len(body) + 8
+    head = b"\x1f\x8b\x08\x04" + b"\x00\x00\x00\x00" + b"\x00\xff" + b"\x08\x00" + b"BO\x04\x00" + struct.pack("<I", total)
+    return head + bytes(body) + struct.pack("<II", crc32 & 0xFFFFFFFF, size & 0xFFFFFFFF)
+
+
+def write_wrapped_members(f, members):
+    """Write (body, crc32, size) triples as consecutive gzip members."""
+    for body, crc, size in members:
+        f.write(gzip_member(body, crc, size))
+
+
+def device_deflate(ctx, src, n: int, row_bytes: int = 0, member_bytes: int = 0):
+    """Deflate `n` payload bytes that are on the device (`src`: a c_void_p / address, bytes in file order) with
+    `boa_deflate_members` (csrc/deflate.hip): -> [(body, crc32, size)] per member of `member_bytes` (default: the 4 MiB of
+    write_gzip_members).  Only the compressed bytes and the offset / CRC tables are downloaded."""
+    import ctypes as C
+    from . import _lib
+    member_bytes = int(member_bytes) or _GZ_BLOCK
+    n = int(n)
+    cap = int(ctx.lib.boa_deflate_bound(n, member_bytes))
+    if cap == 0:
+        raise ValueError(f"device_deflate: {n} bytes in members of {member_bytes}")
+    n_mem = max(1, -(-n // member_bytes))
+    offs, crcs = (C.c_size_t * (n_mem + 1))(), (C.c_uint32 * n_mem)()
+    out = ctx.alloc(cap)
+    try:
+        src = src if isinstance(src, C.c_void_p) else C.c_void_p(src)
+        _lib.check(ctx.lib.boa_deflate_members(ctx.h, src, n, member_bytes, int(row_bytes), out.vp, cap, offs, crcs),
+                   "boa_deflate_members")
+        comp = memoryview(out.download((int(offs[n_mem]),), np.uint8)) if offs[n_mem] else memoryview(b"")
+    finally:
+        out.free()
+    return [(comp[offs[m]:offs[m + 1]], int(crcs[m]), min(member_bytes, n - m * member_bytes)) for m in range(n_mem)]
+
+
+def _device_body(ctx, data):
+    """(buffer to free or None, address, bytes, row bytes) of `data` in file order on the device: a DevArray whose view is already
+    in file order (x fastest) is used in place, any other one is reordered there; a numpy array is uploaded."""
+    from .devarray import DevArray
+    if isinstance(data, DevArray):
+        x, y, _ = data.shape
+        if data.strides == (1, x, x * y):
+            return None, data.buf.ptr + data.offset * data.dtype.itemsize, data.size * data.dtype.itemsize, x * data.dtype.itemsize
+        v = data.transpose((2, 1, 0)).contiguous(force_copy=True)
+        return v.buf, v.buf.ptr, v.size * v.dtype.itemsize, x * data.dtype.itemsize
+    body = np.asfortranarray(data).reshape(-1, order="F")
+    row = (data.shape[0] if data.ndim else 1) * data.dtype.itemsize
+    if body.nbytes == 0:
+        return None, None, 0, row
+    buf = ctx.from_numpy(body)
+    return buf, buf.ptr, body.nbytes, row
+
+
+SAVE_DEVICE_ENV = "BOA_SAVE_DEVICE"
+
+
+def save_volume(path, data, affine, ctx=None, **kw):
+    """`save` for the file-level callers (compute_all_models, the ct_pfav writer): uint8 volumes of a `.gz` path go through the
+    device encoder when $BOA_SAVE_DEVICE is 1 (default off: DESIGN 4.9); everything else, and everything without the switch,
+    takes the CPU path (a DevArray is downloaded first)."""
+    from .devarray import DevArray
+    if ctx is not None and os.environ.get(SAVE_DEVICE_ENV) == "1" and np.dtype(data.dtype) == np.uint8 and str(path).endswith(".gz"):
+        return save(path, data, affine, ctx=ctx, **kw)
+    return save(path, data.download() if isinstance(data, DevArray) else data, affine, **kw)
+
+
 def write_gzip_members(f, payload, compresslevel: int = 1, threads: int = 1, block: int = _GZ_BLOCK):
     """`payload` (bytes-like) as a gzip stream of independently compressed members (RFC 1952 section 2.2: a gzip file is a
     series of members; gzip.open, zlib's gzread -- SimpleITK, nibabel -- and `gunzip` read them as one stream; each member
@@ -251,10 +320,7 @@ def write_gzip_members(f, payload, compresslevel: int = 1, threads: int = 1, blo
         # (read_bytes); every other gzip reader skips it
         piece = mv[lo:lo + block]
         c = zlib.compressobj(compresslevel, zlib.DEFLATED, -15)
-        body = c.compress(piece) + c.flush()
-        total = 20 + len(body) + 8
-        head = b"\x1f\x8b\x08\x04" + b"\x00\x00\x00\x00" + b"\x00\xff" + b"\x08\x00" + b"BO\x04\x00" + struct.pack("<I", total)
-        return head + body + struct.pack("<II", zlib.crc32(piece) & 0xFFFFFFFF, len(piece) & 0xFFFFFFFF)
+        return gzip_member(c.compress(piece) + c.flush(), zlib.crc32(piece), len(piece))
 
     starts = list(range(0, len(mv), block)) or [0]
     if threads <= 1 or len(starts) == 1:
@@ -299,17 +365,25 @@ def quatern_from_affine(affine: np.ndarray) -> Tuple[Tuple[float, float, float],
 
 def save(path, data: np.ndarray, affine: np.ndarray, like: Optional[NiftiHeader] = None,
          extensions: Optional[List[Tuple[int, bytes]]] = None, compresslevel: int = 1, threads: Optional[int] = None,
-         form_codes: Optional[Tuple[int, int]] = None):
-    """Write `data` (file axis order); `.gz` paths are deflated on `threads` cores (default SAVE_THREADS).  `like`: header to copy (pixdim units, descrip, q/s-form codes ... as
+         form_codes: Optional[Tuple[int, int]] = None, ctx=None):
+    """Write `data` (file axis order); `.gz` paths are deflated on `threads` cores (default SAVE_THREADS).  With `ctx` (a device
+    Context) the data body of a `.gz` path is deflated on the device instead (device_deflate; same member container, so read_bytes
+    inflates it in parallel as well), from a numpy array after an upload or from a 3-D DevArray without a download; the header and
+    the extensions stay on the CPU path.  `like`: header to copy (pixdim units, descrip, q/s-form codes ... as
     `img_in_orig.header.copy()` keeps them); datatype/bitpix/dim/vox_offset and the affine fields are set from the
     arguments; scl_slope/inter are reset (label volumes are stored unscaled).  `form_codes`: also store the affine as a qform."""
-    data = np.asarray(data)
+    on_device = ctx is not None and str(path).endswith(".gz")
+    if on_device:
+        from .devarray import DevArray
+    if not (on_device and isinstance(data, DevArray)):   # (a DevArray is taken as it is)
+        data = np.asarray(data)
+    ndim = len(data.shape)
     if data.dtype not in _DT_INV:
         raise TypeError(f"unsupported dtype {data.dtype}")
     affine = np.asarray(affine, dtype=np.float64)
     v = list(struct.unpack(_HDR, like.raw)) if like is not None else list(struct.unpack(_HDR, b"\0" * 348))
     v[0] = 348
-    dim = [data.ndim] + list(data.shape) + [1] * (7 - data.ndim)
+    dim = [ndim] + list(data.shape) + [1] * (7 - ndim)
     v[7:15] = dim
     v[19] = _DT_INV[data.dtype]
     v[20] = data.dtype.itemsize * 8
@@ -338,6 +412,17 @@ def save(path, data: np.ndarray, affine: np.ndarray, like: Optional[NiftiHeader]
     v[-1] = b"n+1\0"
     hdr = struct.pack(_HDR, *v)
     head = hdr + bytes([1 if exts else 0, 0, 0, 0]) + ext_blob
+    if on_device:
+        buf, addr, nbytes, row = _device_body(ctx, data)
+        try:
+            members = device_deflate(ctx, addr, nbytes, row)
+        finally:
+            if buf is not None:
+                buf.free()
+        with open(path, "wb") as f:
+            write_gzip_members(f, head, compresslevel, 1)
+            write_wrapped_members(f, members)
+        return
     body = np.asfortranarray(data).reshape(-1, order="F")          # (a view when `data` is already F-ordered)
     with open(path, "wb") as f:
         if str(path).endswith(".gz"):

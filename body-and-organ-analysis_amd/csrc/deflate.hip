@@ -1,0 +1,450 @@
+// Deflate encoder for label volumes (boa_deflate_members): the payload of a .nii.gz is cut into gzip members, every member into
+// deflate blocks of DFL_BLK input bytes, one workgroup per block.  RFC 1951 (the stream), RFC 1952 (CRC-32 of each member).
+//   k_deflate_block    match lengths against distance 1 and distance row_bytes, greedy parse by pointer jumping, fixed-Huffman
+//                      bit assembly in LDS (or a stored block where that is not smaller), the block's CRC-32; one slot per block
+//   k_deflate_scan     block sizes -> byte offsets; CRCs of the blocks -> CRC of each member
+//   k_deflate_compact  slots -> one contiguous body per member
+// Every block ends on a byte boundary (an empty stored block after a non-final fixed block, as pigz does), so bodies concatenate
+// by byte copy.  A match never reaches before its member's first byte nor past its block's last, so a member inflates alone.
+#include <algorithm>
+
+#include "common.h"
+#include "deflate_codes.h"
+
+namespace {
+
+constexpr int DFL_BLK = 16384;                 // input bytes per deflate block
+constexpr int DFL_NT = 1024;                   // threads per block workgroup
+constexpr int DFL_PIECE = DFL_BLK / DFL_NT;    // positions per thread (16: one uint4 of payload, one half mark word)
+constexpr int DFL_SLOT = DFL_BLK + 16;         // bytes of a block's slot in the workspace (a stored block is 5 + DFL_BLK)
+constexpr int DFL_MAXLEN = 258;
+constexpr int DFL_MAXROW = 32768;
+constexpr int DFL_LOOK = (DFL_MAXLEN + DFL_PIECE - 1) / DFL_PIECE;   // pieces a run is followed into
+static_assert(DFL_PIECE == 16, "the match scan reads one uint4 per thread");
+
+// LDS carve (bytes).  s_next is reused for the assembled bits once the parse is known.
+constexpr int OFF_NEXT = 0;                                    // uint16 [DFL_BLK + 8]
+constexpr int OFF_TOK = OFF_NEXT + (DFL_BLK + 8) * 2;          // uint16 [DFL_BLK]: match length (0 = literal) | 0x8000 if the row distance
+constexpr int OFF_MARK = OFF_TOK + DFL_BLK * 2;                // uint32 [DFL_BLK / 32 + 4]: bit i = position i starts a token
+constexpr int OFF_TAB = OFF_MARK + (DFL_BLK / 32 + 4) * 4;     // uint32 [256]: byte-wise CRC table
+constexpr int OFF_LEAD = OFF_TAB + 1024;                       // uint8 [2][DFL_NT]: leading equal positions of each piece
+constexpr int OFF_MISC = OFF_LEAD + 2 * DFL_NT;                // uint32 [32]
+constexpr int OFF_DATA = OFF_MISC + 128;                       // uint8 [hist + DFL_BLK + 16]: history, then the block
+static_assert(OFF_DATA % 16 == 0 && OFF_TOK % 16 == 0 && OFF_MARK % 16 == 0, "LDS carve alignment");
+static_assert(OFF_DATA >= DFL_MAXROW + 16, "a row candidate of an early piece reads below s_d, inside the carve");
+
+// bit k = (block byte p0 + k equals the byte `d` before it); 16 positions.  Reads LDS words only; the caller masks what is invalid.
+__device__ __forceinline__ unsigned eq_mask16(const unsigned char* s_d, int a, const uint4 own) {
+    const unsigned* w = (const unsigned*)(s_d + (a & ~3));
+    const int sh = (a & 3) * 8;
+    unsigned v[5];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) v[j] = w[j];
+    const unsigned o[4] = {own.x, own.y, own.z, own.w};
+    unsigned mask = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const unsigned b = sh ? (v[j] >> sh) | (v[j + 1] << (32 - sh)) : v[j];
+        const unsigned x = b ^ o[j];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (((x >> (8 * q)) & 0xffu) == 0) mask |= 1u << (4 * j + q);
+    }
+    return mask;
+}
+
+__device__ __forceinline__ void or_bits(unsigned* words, unsigned bit_off, uint64_t bits) {
+    const uint64_t v = bits << (bit_off & 31);
+    const unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
+    if (lo) atomicOr(&words[bit_off >> 5], lo);
+    if (hi) atomicOr(&words[(bit_off >> 5) + 1], hi);
+}
+
+// grid = blocks of all members in file order; dynamic LDS = OFF_DATA + hist + DFL_BLK + 16
+__global__ __launch_bounds__(DFL_NT) void k_deflate_block(const unsigned char* __restrict__ src, size_t n, unsigned member_bytes,
+                                                          unsigned bpm, int row, int hist, const unsigned* __restrict__ pw, unsigned* __restrict__ ws,
+                                                          unsigned* __restrict__ blk_size, unsigned* __restrict__ blk_crc) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned short* s_next = (unsigned short*)(smem + OFF_NEXT);
+    unsigned* s_out = (unsigned*)(smem + OFF_NEXT);
+    unsigned short* s_tok = (unsigned short*)(smem + OFF_TOK);
+    unsigned* s_mark = (unsigned*)(smem + OFF_MARK);
+    unsigned* s_tab = (unsigned*)(smem + OFF_TAB);
+    unsigned char* s_lead = smem + OFF_LEAD;
+    unsigned* s_misc = (unsigned*)(smem + OFF_MISC);
+    unsigned char* s_d = smem + OFF_DATA;
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const size_t g = blockIdx.x;
+    const size_t moff = (g / bpm) * (size_t)member_bytes;
+    const unsigned boff = (unsigned)(g % bpm) * DFL_BLK;                              // block start inside its member
+    const size_t mlen = n - moff < member_bytes ? n - moff : member_bytes;            // 0 only for the empty payload
+    const int blen = (int)(mlen - boff < (size_t)DFL_BLK ? mlen - boff : DFL_BLK);
+    const bool bfinal = boff + (size_t)blen == mlen;
+    const int avail = boff < (unsigned)hist ? (int)boff : hist;                       // history bytes of the same member (multiple of 16)
+    const int H = hist;
+
+    // ---- payload -> LDS, CRC table, marks ----
+    {
+        const unsigned char* gsrc = src + moff + boff - avail;
+        unsigned char* ldst = s_d + H - avail;
+        const int total = avail + blen;
+        const int n16 = ((uintptr_t)gsrc & 15) == 0 ? total >> 4 : 0;
+        for (int i = t; i < n16; i += DFL_NT) ((uint4*)ldst)[i] = ((const uint4*)gsrc)[i];
+        for (int i = n16 * 16 + t; i < total; i += DFL_NT) ldst[i] = gsrc[i];
+    }
+    if (t < 256) {
+        unsigned c = t;
+        for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1) ? DFL_CRC_POLY : 0u);
+        s_tab[t] = c;
+    }
+    for (int i = t; i < DFL_BLK / 32 + 4; i += DFL_NT) s_mark[i] = (i == 0 && blen > 0) ? 1u : 0u;
+    __syncthreads();
+
+    // ---- CRC-32: pieces of 16 bytes aligned to the block's END (the first may be short or empty: crc32("") = 0), combined in
+    // a tree inside each wave, then across the 16 waves ----
+    {
+        const int hi = blen - DFL_PIECE * (DFL_NT - 1 - t);
+        unsigned c = 0xffffffffu;
+        for (int i = hi - DFL_PIECE > 0 ? hi - DFL_PIECE : 0; i < hi; ++i) c = s_tab[(c ^ s_d[H + i]) & 0xffu] ^ (c >> 8);
+        c ^= 0xffffffffu;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {        // after step k the lanes that are multiples of 2^(k+1) hold 2^(k+1) pieces
+            const unsigned right = __shfl_down(c, 1 << k, 64);
+            c = dfl_gf2_mul(pw[4 + k], c) ^ right;
+        }
+        if (lane == 0) s_misc[wave] = c;     // 1 KiB each
+        __syncthreads();
+        if (wave == 0) {
+            unsigned v = 0;
+            if (lane < DFL_NT / 64) v = dfl_gf2_mul(dfl_crc_xpow(pw, 1024ull * (DFL_NT / 64 - 1 - lane)), s_misc[lane]);
+#pragma unroll
+            for (int k = 1; k < 64; k <<= 1) v ^= __shfl_xor(v, k, 64);
+            if (lane == 0) blk_crc[g] = v;
+        }
+        __syncthreads();
+    }
+
+    // ---- match lengths.  Thread t owns positions [16 t, 16 t + 16). ----
+    const int p0 = t * DFL_PIECE;
+    unsigned eq1 = 0, eqr = 0;
+    {
+        const uint4 own = *(const uint4*)(s_d + H + p0);
+        const int inside = blen - p0;                                             // positions of this piece inside the block
+        const unsigned in_mask = inside >= DFL_PIECE ? 0xffffu : inside > 0 ? (1u << inside) - 1 : 0u;
+        if (in_mask) {
+            const int first1 = 1 - avail - p0;                                    // first k whose source byte is in the member
+            const unsigned m1 = in_mask & (first1 <= 0 ? 0xffffu : first1 >= DFL_PIECE ? 0u : 0xffffu << first1);
+            if (m1) eq1 = eq_mask16(s_d, H + p0 - 1, own) & m1;
+            if (row > 0) {
+                const int firstr = row - avail - p0;
+                const unsigned mr = in_mask & (firstr <= 0 ? 0xffffu : firstr >= DFL_PIECE ? 0u : 0xffffu << firstr);
+                if (mr) eqr = eq_mask16(s_d, H + p0 - row, own) & mr;
+            }
+        }
+        s_lead[t] = (unsigned char)__builtin_ctz(~eq1 & 0x1ffffu);
+        s_lead[DFL_NT + t] = (unsigned char)__builtin_ctz(~eqr & 0x1ffffu);
+    }
+    __syncthreads();
+    {
+        // the runs that leave this piece: full pieces behind it, then the lead of the first that is not
+        int run1 = 0, runr = 0;
+        for (int k = 1; k <= DFL_LOOK && t + k < DFL_NT; ++k) {
+            const int l = s_lead[t + k];
+            run1 += l;
+            if (l < DFL_PIECE) break;
+        }
+        for (int k = 1; k <= DFL_LOOK && t + k < DFL_NT; ++k) {
+            const int l = s_lead[DFL_NT + t + k];
+            runr += l;
+            if (l < DFL_PIECE) break;
+        }
+        unsigned tok[8], nxt[8];
+#pragma unroll
+        for (int k = DFL_PIECE - 1; k >= 0; --k) {
+            run1 = (eq1 >> k) & 1 ? run1 + 1 : 0;
+            runr = (eqr >> k) & 1 ? runr + 1 : 0;
+            const int l1 = run1 < DFL_MAXLEN ? run1 : DFL_MAXLEN, lr = runr < DFL_MAXLEN ? runr : DFL_MAXLEN;
+            int L = l1 >= lr ? l1 : lr;                    // a tie goes to distance 1: no extra distance bits
+            const unsigned far = l1 >= lr ? 0u : 0x8000u;
+            if (L < 3) L = 0;
+            const int i = p0 + k;
+            const unsigned tv = (unsigned)L | (L ? far : 0u);
+            const unsigned nv = i < blen ? (unsigned)(i + (L ? L : 1)) : (unsigned)blen;
+            if (k & 1) {
+                tok[k >> 1] = tv << 16;
+                nxt[k >> 1] = nv << 16;
+            } else {
+                tok[k >> 1] |= tv;
+                nxt[k >> 1] |= nv;
+            }
+        }
+        uint4* pt = (uint4*)(s_tok + p0);
+        uint4* pn = (uint4*)(s_next + p0);
+        pt[0] = make_uint4(tok[0], tok[1], tok[2], tok[3]);
+        pt[1] = make_uint4(tok[4], tok[5], tok[6], tok[7]);
+        pn[0] = make_uint4(nxt[0], nxt[1], nxt[2], nxt[3]);
+        pn[1] = make_uint4(nxt[4], nxt[5], nxt[6], nxt[7]);
+        if (t == 0) s_next[DFL_BLK] = (unsigned short)blen;
+    }
+    __syncthreads();
+
+    // ---- greedy parse: the token starts are the orbit of 0 under next[].  After round r, next[] jumps 2^r tokens and the first
+    // 2^r tokens are marked; every marked position then marks its image.  Position blen is the fixed point. ----
+    {
+        int rounds = 0;
+        while ((1 << rounds) < blen) ++rounds;               // at most log2(DFL_BLK)
+        for (int r = 0; r < rounds; ++r) {
+            unsigned pair[DFL_PIECE];
+            unsigned marked = 0;
+#pragma unroll
+            for (int j = 0; j < DFL_PIECE; ++j) {
+                const int i = t + DFL_NT * j;
+                const unsigned nx = s_next[i];
+                pair[j] = nx | ((unsigned)s_next[nx] << 16);
+                marked |= ((s_mark[i >> 5] >> (i & 31)) & 1u) << j;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < DFL_PIECE; ++j) {
+                const int i = t + DFL_NT * j;
+                const unsigned nx = pair[j] & 0xffffu;
+                if ((marked >> j) & 1) atomicOr(&s_mark[nx >> 5], 1u << (nx & 31));
+                s_next[i] = (unsigned short)(pair[j] >> 16);
+            }
+            __syncthreads();
+        }
+    }
+
+    // ---- token bit lengths -> bit offsets ----
+    const int inside = blen - p0;
+    const unsigned starts = (s_mark[p0 >> 5] >> (p0 & 31)) & (inside >= DFL_PIECE ? 0xffffu : inside > 0 ? (1u << inside) - 1 : 0u);
+    const int far_dist = row;
+    unsigned my_bits = 0;
+    for (unsigned m = starts; m; m &= m - 1) {
+        const int i = p0 + __builtin_ctz(m);
+        const unsigned tv = s_tok[i];
+        int nb;
+        if (tv & 0x7fffu)
+            dfl_match(tv & 0x7fffu, (tv & 0x8000u) ? far_dist : 1, &nb);
+        else
+            dfl_literal(s_d[H + i], &nb);
+        my_bits += nb;
+    }
+    unsigned incl = my_bits;
+#pragma unroll
+    for (int k = 1; k < 64; k <<= 1) {
+        const unsigned up = __shfl_up(incl, k, 64);
+        if (lane >= k) incl += up;
+    }
+    if (lane == 63) s_misc[wave] = incl;
+    __syncthreads();                                            // (also: s_next is dead from here on, s_out may be written)
+    unsigned before = 0, tok_bits = 0;
+    for (int w = 0; w < DFL_NT / 64; ++w) {
+        const unsigned v = s_misc[w];
+        if (w < wave) before += v;
+        tok_bits += v;
+    }
+    // 3 header bits, the tokens, 7 bits of end-of-block; a non-final block then gets 3 header bits of an empty stored block,
+    // padding to a byte and 00 00 FF FF; the final block is only padded
+    const unsigned end_bit = 3 + tok_bits + 7;
+    const unsigned sync_byte = (end_bit + 3 + 7) >> 3;
+    const unsigned fixed_bytes = bfinal ? (end_bit + 7) >> 3 : sync_byte + 4;
+    const unsigned stored_bytes = 5 + blen;
+    const bool fixed = fixed_bytes < stored_bytes;
+    const unsigned out_bytes = fixed ? fixed_bytes : stored_bytes;
+    const unsigned out_words = (out_bytes + 3) >> 2;            // <= DFL_SLOT / 4
+    unsigned* slot = ws + g * (size_t)(DFL_SLOT / 4);
+    if (fixed) {
+        for (unsigned w = t; w < out_words + 1; w += DFL_NT) s_out[w] = 0;
+        __syncthreads();
+        unsigned off = 3 + before + (incl - my_bits);
+        for (unsigned m = starts; m; m &= m - 1) {
+            const int i = p0 + __builtin_ctz(m);
+            const unsigned tv = s_tok[i];
+            int nb;
+            const uint64_t bits = (tv & 0x7fffu) ? dfl_match(tv & 0x7fffu, (tv & 0x8000u) ? far_dist : 1, &nb) : dfl_literal(s_d[H + i], &nb);
+            or_bits(s_out, off, bits);
+            off += nb;
+        }
+        if (t == 0) {
+            atomicOr(&s_out[0], (bfinal ? 1u : 0u) | 2u);       // BFINAL, BTYPE = 01
+            if (!bfinal) {
+                atomicOr(&s_out[(sync_byte + 2) >> 2], 0xffu << (((sync_byte + 2) & 3) * 8));
+                atomicOr(&s_out[(sync_byte + 3) >> 2], 0xffu << (((sync_byte + 3) & 3) * 8));
+            }
+        }
+        __syncthreads();
+        for (unsigned w = t; w < out_words; w += DFL_NT) slot[w] = s_out[w];
+    } else {
+        // stored block: BFINAL + BTYPE = 00 in one byte (the block starts on a byte boundary), LEN, ~LEN, the bytes
+        const unsigned head[5] = {bfinal ? 1u : 0u, (unsigned)blen & 0xffu, (unsigned)blen >> 8, ~(unsigned)blen & 0xffu, (~(unsigned)blen >> 8) & 0xffu};
+        for (unsigned w = t; w < out_words; w += DFL_NT) {
+            unsigned v = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const unsigned b = 4 * w + q;
+                const unsigned byte = b < 5 ? head[b] : b < stored_bytes ? s_d[H + b - 5] : 0u;
+                v |= byte << (8 * q);
+            }
+            slot[w] = v;
+        }
+    }
+    if (t == 0) blk_size[g] = out_bytes;
+}
+
+// one workgroup: exclusive scan of the block sizes (members are consecutive runs of blocks), then one thread per member
+__global__ __launch_bounds__(DFL_NT) void k_deflate_scan(const unsigned* __restrict__ blk_size, const unsigned* __restrict__ blk_crc,
+                                                         unsigned nblocks, unsigned bpm, unsigned nmem, size_t n, unsigned member_bytes,
+                                                         const unsigned* __restrict__ pw, unsigned long long* __restrict__ blk_off,
+                                                         unsigned long long* __restrict__ mem_off, unsigned* __restrict__ mem_crc) {
+    __shared__ unsigned long long s_wave[DFL_NT / 64];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    unsigned long long carry = 0;
+    for (unsigned base = 0; base < nblocks; base += DFL_NT) {
+        const unsigned i = base + t;
+        const unsigned long long v = i < nblocks ? blk_size[i] : 0;
+        unsigned long long incl = v;
+#pragma unroll
+        for (int k = 1; k < 64; k <<= 1) {
+            const unsigned long long up = __shfl_up(incl, k, 64);
+            if (lane >= k) incl += up;
+        }
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        unsigned long long before = 0, total = 0;
+        for (int w = 0; w < DFL_NT / 64; ++w) {
+            if (w < wave) before += s_wave[w];
+            total += s_wave[w];
+        }
+        if (i < nblocks) blk_off[i] = carry + before + incl - v;
+        carry += total;
+        __syncthreads();
+    }
+    __threadfence_block();
+    __syncthreads();
+    for (unsigned m = t; m < nmem; m += DFL_NT) {
+        const size_t moff = (size_t)m * member_bytes;
+        const size_t mlen = n - moff < member_bytes ? n - moff : member_bytes;
+        const unsigned first = m * bpm;
+        const unsigned nb = m + 1 < nmem ? bpm : nblocks - first;
+        unsigned c = 0;
+        for (unsigned k = 0; k < nb; ++k) {
+            const size_t left = mlen - (size_t)k * DFL_BLK;
+            c = dfl_crc_combine(pw, c, blk_crc[first + k], left < (size_t)DFL_BLK ? left : DFL_BLK);
+        }
+        mem_off[m] = blk_off[first];
+        mem_crc[m] = c;
+    }
+    if (t == 0) mem_off[nmem] = carry;
+}
+
+__device__ __forceinline__ unsigned slot_byte(const unsigned* w, unsigned i) { return (w[i >> 2] >> ((i & 3) * 8)) & 0xffu; }
+
+// grid = blocks; the slot of block g -> dst + blk_off[g], whole words where the destination allows
+__global__ __launch_bounds__(256) void k_deflate_compact(const unsigned* __restrict__ ws, const unsigned* __restrict__ blk_size,
+                                                         const unsigned long long* __restrict__ blk_off, unsigned char* __restrict__ dst) {
+    const size_t g = blockIdx.x;
+    const unsigned* w = ws + g * (size_t)(DFL_SLOT / 4);
+    const unsigned sz = blk_size[g];
+    unsigned char* d = dst + blk_off[g];
+    unsigned head = (unsigned)((4 - ((uintptr_t)d & 3)) & 3);
+    if (head > sz) head = sz;
+    const unsigned nw = (sz - head) >> 2;
+    const int t = threadIdx.x;
+    if ((unsigned)t < head) d[t] = (unsigned char)slot_byte(w, t);
+    unsigned* dw = (unsigned*)(d + head);
+    const unsigned sh = (head & 3) * 8;
+    for (unsigned k = t; k < nw; k += 256) {
+        const unsigned s = (head + 4 * k) >> 2;
+        dw[k] = sh ? (w[s] >> sh) | (w[s + 1] << (32 - sh)) : w[s];      // w[s + 1] holds byte head + 4 k + 3 < sz: inside the slot
+    }
+    const unsigned tail = head + 4 * nw;
+    if (tail + t < sz) d[tail + t] = (unsigned char)slot_byte(w, tail + t);
+}
+
+const DflCrcPow& crc_pow() {
+    static const DflCrcPow t = [] {
+        DflCrcPow p;
+        dfl_crc_pow_init(&p);
+        return p;
+    }();
+    return t;
+}
+
+// (members, blocks per full member, blocks in all) of n payload bytes; the empty payload is one member of one empty block
+void deflate_shape(size_t n, size_t member_bytes, size_t* nmem, size_t* bpm, size_t* nblocks) {
+    *bpm = (member_bytes + DFL_BLK - 1) / DFL_BLK;
+    if (n == 0) {
+        *nmem = *nblocks = 1;
+        return;
+    }
+    *nmem = (n + member_bytes - 1) / member_bytes;
+    const size_t last = n - (*nmem - 1) * member_bytes;
+    *nblocks = (*nmem - 1) * *bpm + (last + DFL_BLK - 1) / DFL_BLK;
+}
+
+constexpr size_t DFL_MAX_N = (size_t)1 << 40;
+constexpr size_t DFL_MAX_MEMBER = (size_t)1 << 30;
+
+}  // namespace
+
+extern "C" size_t boa_deflate_bound(size_t n, size_t member_bytes) {
+    if (member_bytes < 1 || member_bytes > DFL_MAX_MEMBER || n > DFL_MAX_N) return 0;
+    size_t nmem, bpm, nblocks;
+    deflate_shape(n, member_bytes, &nmem, &bpm, &nblocks);
+    return n + 5 * nblocks;      // every block as a stored block: 5 bytes of header each
+}
+
+extern "C" int boa_deflate_members(boa_ctx* c, const uint8_t* dev_src, size_t n, size_t member_bytes, int row_bytes, uint8_t* dev_out,
+                                   size_t out_capacity, size_t* host_offsets, uint32_t* host_crc32) {
+    BOA_REQUIRE(c && dev_out && host_offsets && host_crc32 && (dev_src || n == 0), "boa_deflate_members: NULL argument");
+    BOA_REQUIRE(member_bytes >= 1 && member_bytes <= DFL_MAX_MEMBER, "boa_deflate_members: member_bytes %zu outside [1, 2^30]", member_bytes);
+    BOA_REQUIRE(n <= DFL_MAX_N, "boa_deflate_members: %zu payload bytes (at most 2^40)", n);
+    size_t nmem, bpm, nblocks;
+    deflate_shape(n, member_bytes, &nmem, &bpm, &nblocks);
+    BOA_REQUIRE(nblocks <= 0x7fffffffu && nmem <= 0x7fffffffu, "boa_deflate_members: %zu blocks in %zu members", nblocks, nmem);
+    const size_t bound = n + 5 * nblocks;
+    BOA_REQUIRE(out_capacity >= bound, "boa_deflate_members: out_capacity %zu below boa_deflate_bound = %zu", out_capacity, bound);
+    const int row = (row_bytes >= 1 && row_bytes <= DFL_MAXROW) ? row_bytes : 0;      // anything else: no row candidate
+    const int hist = std::max(16, (row + 15) & ~15);
+    const size_t lds = (size_t)OFF_DATA + hist + DFL_BLK + 16;
+
+    // workspace: [slots][block offsets u64][member offsets u64][block sizes][block CRCs][member CRCs][x^(8 2^k) table]
+    const size_t slots_b = nblocks * (size_t)DFL_SLOT;
+    const size_t boff_b = nblocks * 8, moff_b = (nmem + 1) * 8, bsz_b = nblocks * 4, bcrc_b = nblocks * 4, mcrc_b = nmem * 4;
+    unsigned char* blk = nullptr;
+    BOA_TRY(boa_malloc(c, slots_b + boff_b + moff_b + bsz_b + bcrc_b + mcrc_b + sizeof(DflCrcPow), (void**)&blk));
+    unsigned* d_slots = (unsigned*)blk;
+    unsigned long long* d_boff = (unsigned long long*)(blk + slots_b);
+    unsigned long long* d_moff = (unsigned long long*)(blk + slots_b + boff_b);
+    unsigned* d_bsz = (unsigned*)(blk + slots_b + boff_b + moff_b);
+    unsigned* d_bcrc = (unsigned*)(blk + slots_b + boff_b + moff_b + bsz_b);
+    unsigned* d_mcrc = (unsigned*)(blk + slots_b + boff_b + moff_b + bsz_b + bcrc_b);
+    unsigned* d_pw = (unsigned*)(blk + slots_b + boff_b + moff_b + bsz_b + bcrc_b + mcrc_b);
+
+    static bool once = (hipFuncSetAttribute((const void*)k_deflate_block, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), true);
+    (void)once;
+    std::vector<unsigned long long> offs(nmem + 1);
+    hipError_t e = hipMemcpyAsync(d_pw, crc_pow().x, sizeof(DflCrcPow), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) {
+        boa_free(c, blk);
+        BOA_HIP_TRY(e);
+    }
+    c->prof_break = true;
+    KernelTimer t(c, BOA_K_OTHER, 0, (double)n * 2 + (double)nblocks * 16);
+    hipLaunchKernelGGL(k_deflate_block, dim3((unsigned)nblocks), dim3(DFL_NT), lds, c->stream, dev_src, n, (unsigned)member_bytes,
+                       (unsigned)bpm, row, hist, d_pw, d_slots, d_bsz, d_bcrc);
+    hipLaunchKernelGGL(k_deflate_scan, dim3(1), dim3(DFL_NT), 0, c->stream, d_bsz, d_bcrc, (unsigned)nblocks, (unsigned)bpm,
+                       (unsigned)nmem, n, (unsigned)member_bytes, d_pw, d_boff, d_moff, d_mcrc);
+    hipLaunchKernelGGL(k_deflate_compact, dim3((unsigned)nblocks), dim3(256), 0, c->stream, d_slots, d_bsz, d_boff, dev_out);
+    t.stop();
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(offs.data(), d_moff, moff_b, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(host_crc32, d_mcrc, mcrc_b, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    boa_free(c, blk);
+    BOA_HIP_TRY(e);
+    for (size_t m = 0; m <= nmem; ++m) host_offsets[m] = (size_t)offs[m];
+    return BOA_OK;
+}

@@ -644,6 +644,23 @@ int boa_ljpeg_decode(boa_ctx* ctx, const uint8_t* dev_data, size_t data_bytes, i
 int boa_j2k_decode(boa_ctx* ctx, const uint8_t* dev_data, size_t data_bytes, int n_frames, const int* frames, int n_blocks,
                    const int* blocks, uint16_t* dev_out, int* host_status);
 
+/* ------------------------------------------------------------------ deflate encoder for label volumes (deflate.hip) --- */
+/* The data body of a .nii.gz label volume as raw deflate streams (RFC 1951), one per gzip member (RFC 1952), encoded on the
+ * device.  dev_src: n payload bytes in file order.  The payload is cut into members of member_bytes (1 .. 2^30; the last may be
+ * shorter; n == 0 is one member whose body is the empty final fixed block, 03 00), every member into deflate blocks of 16 KiB of
+ * input.  Each block is parsed greedily against two candidates per position, distance 1 (a run) and distance row_bytes (the
+ * voxel one x-row back; row_bytes outside 1 .. 32768 = no row candidate), matches of 3 .. 258 bytes that neither reach before
+ * the member's first byte nor past the block's last, and written with the fixed Huffman codes (BTYPE = 01), or as a stored block
+ * (BTYPE = 00) where that is not larger.  Non-final blocks are byte-aligned by an empty stored block; the last block of a member
+ * has BFINAL = 1 and is padded to a byte, so every member inflates on its own.
+ * Output: the bodies packed back to back in dev_out, member m at [host_offsets[m], host_offsets[m + 1]) (n_members + 1 entries,
+ * n_members = max(1, ceil(n / member_bytes))), and host_crc32[m] = the CRC-32 (RFC 1952 section 8) of member m's payload,
+ * computed on the device.  out_capacity must be at least boa_deflate_bound(n, member_bytes) (every block stored: n + 5 bytes per
+ * block; 0 for sizes boa_deflate_members rejects), else BOA_EINVAL before anything is launched.  Deterministic.  Synchronous. */
+size_t boa_deflate_bound(size_t n, size_t member_bytes);
+int boa_deflate_members(boa_ctx* ctx, const uint8_t* dev_src, size_t n, size_t member_bytes, int row_bytes, uint8_t* dev_out,
+                        size_t out_capacity, size_t* host_offsets, uint32_t* host_crc32);
+
 #ifdef __cplusplus
 }
 #endif
