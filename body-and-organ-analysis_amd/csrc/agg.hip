@@ -1,6 +1,5 @@
-// HBM-bound voxel aggregations of the BOA body-composition / measurement path (integer arithmetic only):
-// tissue subclassification + slice-wise counts and HU sums, per-label HU histograms, label/HU masks,
-// separable binary erosion, 26-connected component labelling by atomic union-find.
+// HBM-bound voxel aggregations of the BOA body-composition / measurement path (integer arithmetic, but for the float64 HU instantiations):
+// tissue subclassification + slice-wise counts and HU sums (int16 and float64 HU), per-label HU histograms, label/HU masks.
 #include <string.h>
 
 #include <algorithm>
@@ -11,7 +10,10 @@
 // BCA/tissue/subclassification.py:38-53 with the rules of BCA/tissue/definition.py:22-30 applied in enum order
 // (later rules overwrite): MUSCLE(-29..150 in MUSCLE=2), BONE(-1000..3000 in BONE=5), SAT/VAT/IMAT/PAT/EAT
 // (-190..-30 in SUBCUTANEOUS=1 / ABDOMINAL=3 / MUSCLE=2 / MEDIASTINUM=9 / PERICARDIUM=7).
-__device__ __forceinline__ int tissue_of(int hu, int region) {
+// H: the type the bounds are compared in -- int for int16 HU; double for float64 HU, where the rules compare the float value itself
+// (`image >= lo` and `image <= hi`: -29.5 is neither muscle nor adipose tissue, -190.0 is adipose).  The bounds are exact in both.
+template <typename H>
+__device__ __forceinline__ int tissue_of(H hu, int region) {
     const bool adip = hu >= -190 && hu <= -30;
     int t = 0;
     if (region == 2 && hu >= -29 && hu <= 150) t = 1;
@@ -26,16 +28,66 @@ __device__ __forceinline__ int tissue_of(int hu, int region) {
     return t;
 }
 
-template <int VEC>
-__global__ __launch_bounds__(256) void k_tissue_aggregate(const short* __restrict__ ct,
-                                                          const short* __restrict__ ct_rules,
+// What the tissue pass needs to know about the CT's value type T (int16 HU, or float64 HU: agg_f64.hip has the other float statistics).
+// Per-slice counts are exact in both; the per-slice HU sums are int64, or fp64 (wave and block reduction, then one fp64 atomic per
+// block and counter).  The vector form reads VEC voxels per thread: 16-byte loads of the HU values, one `bytes` load per byte array.
+template <typename T>
+struct TissueTraits;
+template <>
+struct TissueTraits<short> {
+    static constexpr int VEC = 8;
+    typedef int hu_t;         // tissue_of's compared type
+    typedef int acc_t;        // per-thread sum
+    typedef long long sum_t;  // block and slice sum
+    typedef uint2 bytes;
+    // workgroups per slice: 16 (each thread reduces >= 64 voxels before the wave / block reduction and its 14 global atomics; 64
+    // workgroups per slice measured 0.43 ms per 512^3 volume, 8 ... 32: 0.35 ms)
+    static constexpr int MAX_GX = 16;
+    static __device__ __forceinline__ void load(short* dst, const short* src) { *(uint4*)dst = *(const uint4*)src; }
+    // src + o if src is there, else the registers `alt` (a select here, a branch in the double form: each is the form its kernel was
+    // measured with, and the compiler allocates registers differently for the other)
+    static __device__ __forceinline__ void load_or(short* dst, const short* src, size_t o, const short* alt) {
+        *(uint4*)dst = src ? *(const uint4*)(src + o) : *(const uint4*)alt;
+    }
+    static __device__ __forceinline__ void add(sum_t* p, sum_t v) { atomicAdd((unsigned long long*)p, (unsigned long long)v); }
+};
+template <>
+struct TissueTraits<double> {
+    static constexpr int VEC = 4;
+    typedef double hu_t;
+    typedef double acc_t;
+    typedef double sum_t;
+    typedef unsigned int bytes;
+    static constexpr int MAX_GX = 32;
+    static __device__ __forceinline__ void load(double* dst, const double* src) {
+        *(double2*)dst = *(const double2*)src;
+        *(double2*)(dst + 2) = *(const double2*)(src + 2);
+    }
+    static __device__ __forceinline__ void load_or(double* dst, const double* src, size_t o, const double* alt) {
+        if (src) {
+            load(dst, src + o);
+        } else {
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) dst[j] = alt[j];
+        }
+    }
+    static __device__ __forceinline__ void add(sum_t* p, sum_t v) { atomicAdd(p, v); }
+};
+
+// VEC: TissueTraits<T>::VEC, or 1 (slices or arrays that the vector loads cannot take)
+template <typename T, int VEC>
+__global__ __launch_bounds__(256) void k_tissue_aggregate(const T* __restrict__ ct, const T* __restrict__ ct_rules,
                                                           const unsigned char* __restrict__ regions,
                                                           const unsigned char* __restrict__ parts,
                                                           unsigned char* __restrict__ tissues, int slice_vox,
                                                           unsigned int* __restrict__ counts,
-                                                          long long* __restrict__ sums) {
+                                                          typename TissueTraits<T>::sum_t* __restrict__ sums) {
+    typedef TissueTraits<T> Tr;
+    typedef typename Tr::acc_t acc_t;
+    typedef typename Tr::sum_t sum_t;
+    typedef typename Tr::bytes bytes;
     __shared__ unsigned int s_cnt[16];
-    __shared__ long long s_sum[16];
+    __shared__ sum_t s_sum[16];
     const int z = blockIdx.y;
     if (threadIdx.x < 16) {
         s_cnt[threadIdx.x] = 0;
@@ -43,25 +95,28 @@ __global__ __launch_bounds__(256) void k_tissue_aggregate(const short* __restric
     }
     __syncthreads();
     int cnt[2][8];
-    int sum[2][8];
+    acc_t sum[2][8];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int t = 0; t < 8; ++t) cnt[a][t] = sum[a][t] = 0;
+        for (int t = 0; t < 8; ++t) {
+            cnt[a][t] = 0;
+            sum[a][t] = 0;
+        }
     const size_t base = (size_t)z * slice_vox;
     const int nvec = slice_vox / VEC;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < nvec; i += gridDim.x * 256) {
-        short hu[VEC] __attribute__((aligned(16)));
-        short hr[VEC] __attribute__((aligned(16)));
-        unsigned char rg[VEC] __attribute__((aligned(8)));
-        unsigned char pt[VEC] __attribute__((aligned(8)));
-        unsigned char ts[VEC] __attribute__((aligned(8)));
+        T hu[VEC] __attribute__((aligned(16)));
+        T hr[VEC] __attribute__((aligned(16)));
+        unsigned char rg[VEC] __attribute__((aligned(sizeof(bytes))));
+        unsigned char pt[VEC] __attribute__((aligned(sizeof(bytes))));
+        unsigned char ts[VEC] __attribute__((aligned(sizeof(bytes))));
         const size_t o = base + (size_t)i * VEC;
-        if (VEC == 8) {
-            *(uint4*)hu = *(const uint4*)(ct + o);
-            *(uint4*)hr = ct_rules ? *(const uint4*)(ct_rules + o) : *(const uint4*)hu;
-            *(uint2*)rg = *(const uint2*)(regions + o);
-            if (parts) *(uint2*)pt = *(const uint2*)(parts + o);
+        if (VEC > 1) {
+            Tr::load(hu, ct + o);
+            Tr::load_or(hr, ct_rules, o, hu);
+            *(bytes*)rg = *(const bytes*)(regions + o);
+            if (parts) *(bytes*)pt = *(const bytes*)(parts + o);
         } else {
             hu[0] = ct[o];
             hr[0] = ct_rules ? ct_rules[o] : hu[0];
@@ -70,21 +125,21 @@ __global__ __launch_bounds__(256) void k_tissue_aggregate(const short* __restric
         }
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
-            const int t = tissue_of(hr[j], rg[j]);
+            const int t = tissue_of<typename Tr::hu_t>(hr[j], rg[j]);
             ts[j] = (unsigned char)t;
             const bool torso = parts && pt[j] == 1;
 #pragma unroll
             for (int k = 1; k < 8; ++k) {
                 const bool m = (t == k);
                 cnt[0][k] += m ? 1 : 0;
-                sum[0][k] += m ? hu[j] : 0;
+                sum[0][k] += m ? (acc_t)hu[j] : (acc_t)0;
                 cnt[1][k] += (m && torso) ? 1 : 0;
-                sum[1][k] += (m && torso) ? hu[j] : 0;
+                sum[1][k] += (m && torso) ? (acc_t)hu[j] : (acc_t)0;
             }
         }
         if (tissues) {
-            if (VEC == 8)
-                *(uint2*)(tissues + o) = *(const uint2*)ts;
+            if (VEC > 1)
+                *(bytes*)(tissues + o) = *(const bytes*)ts;
             else
                 tissues[o] = ts[0];
         }
@@ -95,7 +150,7 @@ __global__ __launch_bounds__(256) void k_tissue_aggregate(const short* __restric
 #pragma unroll
         for (int k = 1; k < 8; ++k) {
             int c = cnt[a][k];
-            long long s = sum[a][k];
+            sum_t s = sum[a][k];
 #pragma unroll
             for (int m = 32; m >= 1; m >>= 1) {
                 c += __shfl_xor(c, m);
@@ -103,42 +158,59 @@ __global__ __launch_bounds__(256) void k_tissue_aggregate(const short* __restric
             }
             if ((threadIdx.x & 63) == 0 && c) {
                 atomicAdd(&s_cnt[a * 8 + k], (unsigned int)c);
-                atomicAdd((unsigned long long*)&s_sum[a * 8 + k], (unsigned long long)s);
+                Tr::add(&s_sum[a * 8 + k], s);
             }
         }
     __syncthreads();
     if (threadIdx.x < 16 && s_cnt[threadIdx.x]) {
         atomicAdd(&counts[(size_t)z * 16 + threadIdx.x], s_cnt[threadIdx.x]);
-        atomicAdd((unsigned long long*)&sums[(size_t)z * 16 + threadIdx.x], (unsigned long long)s_sum[threadIdx.x]);
+        Tr::add(&sums[(size_t)z * 16 + threadIdx.x], s_sum[threadIdx.x]);
     }
+}
+
+template <typename T>
+static int tissue_aggregate(boa_ctx* c, const char* what, const T* dev_ct, const T* dev_ct_rules, const uint8_t* dev_regions,
+                            const uint8_t* dev_parts, uint8_t* dev_tissues_out, int Z, int Y, int X, uint32_t* dev_counts,
+                            typename TissueTraits<T>::sum_t* dev_hu_sums) {
+    typedef TissueTraits<T> Tr;
+    constexpr int VEC = Tr::VEC;   // also the alignment of the vector form's byte arrays
+    static_assert(VEC == sizeof(typename Tr::bytes), "the byte arrays are loaded VEC bytes at a time: their alignment test below is % VEC");
+    BOA_REQUIRE(c && dev_ct && dev_regions && dev_counts && dev_hu_sums, "%s: NULL argument", what);
+    BOA_REQUIRE(Z > 0 && Y > 0 && X > 0 && (long long)Y * X < (1ll << 30), "%s: bad dims", what);
+    BOA_HIP_TRY(hipMemsetAsync(dev_counts, 0, (size_t)Z * 16 * sizeof(uint32_t), c->stream));
+    BOA_HIP_TRY(hipMemsetAsync(dev_hu_sums, 0, (size_t)Z * 16 * sizeof(typename Tr::sum_t), c->stream));   // (all-zero bytes are +0.0)
+    const int sv = Y * X;
+    // (NULL optional arrays pass; ct_rules is read with the same 16-byte loads as ct)
+    const bool vec = (sv % VEC == 0) && (((uintptr_t)dev_ct) % 16 == 0) && (((uintptr_t)dev_ct_rules) % 16 == 0) &&
+                     (((uintptr_t)dev_regions) % VEC == 0) && (((uintptr_t)dev_parts) % VEC == 0) && (((uintptr_t)dev_tissues_out) % VEC == 0);
+    const int nvec = vec ? sv / VEC : sv;
+    const int gx = std::min(ceil_div(nvec, 256), Tr::MAX_GX);
+    const double vox = (double)Z * sv;
+    KernelTimer t(c, BOA_K_AGG, 0,
+                  vox * (1.0 + sizeof(T) + (dev_ct_rules ? (double)sizeof(T) : 0.0) + (dev_parts ? 1 : 0) + (dev_tissues_out ? 1 : 0)));
+    if (vec)
+        hipLaunchKernelGGL((k_tissue_aggregate<T, VEC>), dim3(gx, Z), dim3(256), 0, c->stream, dev_ct, dev_ct_rules, dev_regions, dev_parts,
+                           dev_tissues_out, sv, dev_counts, dev_hu_sums);
+    else
+        hipLaunchKernelGGL((k_tissue_aggregate<T, 1>), dim3(gx, Z), dim3(256), 0, c->stream, dev_ct, dev_ct_rules, dev_regions, dev_parts,
+                           dev_tissues_out, sv, dev_counts, dev_hu_sums);
+    t.stop();
+    BOA_HIP_TRY(hipGetLastError());
+    return BOA_OK;
 }
 
 extern "C" int boa_tissue_aggregate(boa_ctx* c, const int16_t* dev_ct, const int16_t* dev_ct_rules,
                                     const uint8_t* dev_regions, const uint8_t* dev_parts, uint8_t* dev_tissues_out, int Z, int Y, int X,
                                     uint32_t* dev_counts, int64_t* dev_hu_sums) {
-    BOA_REQUIRE(c && dev_ct && dev_regions && dev_counts && dev_hu_sums, "boa_tissue_aggregate: NULL argument");
-    BOA_REQUIRE(Z > 0 && Y > 0 && X > 0 && (long long)Y * X < (1ll << 30), "boa_tissue_aggregate: bad dims");
-    BOA_HIP_TRY(hipMemsetAsync(dev_counts, 0, (size_t)Z * 16 * sizeof(uint32_t), c->stream));
-    BOA_HIP_TRY(hipMemsetAsync(dev_hu_sums, 0, (size_t)Z * 16 * sizeof(int64_t), c->stream));
-    const int sv = Y * X;
-    // (NULL optional arrays pass; ct_rules is read with the same 16-byte loads as ct)
-    const bool vec8 = (sv % 8 == 0) && (((uintptr_t)dev_ct) % 16 == 0) && (((uintptr_t)dev_ct_rules) % 16 == 0) && (((uintptr_t)dev_regions) % 8 == 0) &&
-                      (((uintptr_t)dev_parts) % 8 == 0) && (((uintptr_t)dev_tissues_out) % 8 == 0);
-    const int nvec = vec8 ? sv / 8 : sv;
-    // workgroups per slice: 16 (each thread reduces >= 64 voxels before the wave / block reduction and its 14 global atomics; 64
-    // workgroups per slice measured 0.43 ms per 512^3 volume, 8 ... 32: 0.35 ms)
-    const int gx = std::min(ceil_div(nvec, 256), 16);
-    const double vox = (double)Z * sv;
-    KernelTimer t(c, BOA_K_AGG, 0, vox * (3.0 + (dev_ct_rules ? 2 : 0) + (dev_parts ? 1 : 0) + (dev_tissues_out ? 1 : 0)));
-    if (vec8)
-        hipLaunchKernelGGL(k_tissue_aggregate<8>, dim3(gx, Z), dim3(256), 0, c->stream, dev_ct, dev_ct_rules, dev_regions,
-                           dev_parts, dev_tissues_out, sv, dev_counts, (long long*)dev_hu_sums);
-    else
-        hipLaunchKernelGGL(k_tissue_aggregate<1>, dim3(gx, Z), dim3(256), 0, c->stream, dev_ct, dev_ct_rules, dev_regions,
-                           dev_parts, dev_tissues_out, sv, dev_counts, (long long*)dev_hu_sums);
-    t.stop();
-    BOA_HIP_TRY(hipGetLastError());
-    return BOA_OK;
+    return tissue_aggregate<short>(c, "boa_tissue_aggregate", dev_ct, dev_ct_rules, dev_regions, dev_parts, dev_tissues_out, Z, Y, X, dev_counts,
+                                   (long long*)dev_hu_sums);
+}
+
+extern "C" int boa_tissue_aggregate_f64(boa_ctx* c, const double* dev_ct, const double* dev_ct_rules, const uint8_t* dev_regions,
+                                        const uint8_t* dev_parts, uint8_t* dev_tissues_out, int Z, int Y, int X, uint32_t* dev_counts,
+                                        double* dev_hu_sums) {
+    return tissue_aggregate<double>(c, "boa_tissue_aggregate_f64", dev_ct, dev_ct_rules, dev_regions, dev_parts, dev_tissues_out, Z, Y, X,
+                                    dev_counts, dev_hu_sums);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -560,579 +632,6 @@ extern "C" int boa_label_select(boa_ctx* c, const uint8_t* dev_labels, size_t n,
     int grid = (int)std::min<size_t>((n + 255) / 256, (size_t)c->cu_count * 32);
     hipLaunchKernelGGL(k_label_select, dim3(grid), dim3(256), 0, c->stream, dev_labels, n, mode, vals ? vals[0] : 0,
                        vals ? vals[1] : 0, vals ? vals[2] : 0, dev_mask_out);
-    BOA_HIP_TRY(hipGetLastError());
-    return BOA_OK;
-}
-
-// ------------------------------------------------------------------------------------------------------
-// erode_region: AND over offsets [-(k/2) .. k - 1 - k/2] for even k (footprint padded at the end), symmetric for
-// odd k; outside the volume counts as set.  One pass per axis.
-__global__ __launch_bounds__(256) void k_erode_axis(const unsigned char* __restrict__ in, unsigned char* __restrict__ out,
-                                                    int Z, int Y, int X, int axis, int lo, int hi) {
-    const size_t n = (size_t)Z * Y * X;
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    int x, y, z;
-    idx3(i, Y, X, z, y, x);
-    const int pos = axis == 0 ? z : (axis == 1 ? y : x);
-    const int len = axis == 0 ? Z : (axis == 1 ? Y : X);
-    const size_t st = axis == 0 ? (size_t)Y * X : (axis == 1 ? (size_t)X : 1);
-    unsigned char r = 1;
-    for (int d = lo; d <= hi; ++d) {
-        const int q = pos + d;
-        if (q < 0 || q >= len) continue;
-        r &= (in[i + (long long)d * (long long)st] != 0) ? 1 : 0;
-    }
-    out[i] = r;
-}
-
-extern "C" int boa_bits_erode_u8(boa_ctx* c, const uint8_t* dev_mask, uint8_t* dev_out, int Z, int Y, int X, int lo, int hi);
-
-extern "C" int boa_binary_erode(boa_ctx* c, const uint8_t* dev_mask, uint8_t* dev_out, uint8_t* dev_tmp, int Z, int Y,
-                                int X, int kernel_value) {
-    BOA_REQUIRE(c && dev_mask && dev_out && dev_tmp && kernel_value >= 1, "boa_binary_erode: bad argument");
-    BOA_REQUIRE(dev_out != dev_mask && dev_tmp != dev_mask && dev_tmp != dev_out, "boa_binary_erode: buffers must differ");
-    const int k = kernel_value;
-    const int center = (k % 2 == 0) ? (k + 1) / 2 : k / 2;  // centre of the (padded) footprint
-    const int lo = -center, hi = k - 1 - center;
-    const size_t n = (size_t)Z * Y * X;
-    // bit-mask form (csrc/ccl_bits.hip): 1 byte read + 1 byte written per voxel and three passes over 1 / 8 byte per voxel, instead of
-    // three byte passes of one thread per voxel (1.9 ms -> 0.2 ms per 512^3 mask); the byte passes take reaches of 32 and more
-    if (lo > -32 && hi < 32) return boa_bits_erode_u8(c, dev_mask, dev_out, Z, Y, X, lo, hi);
-    unsigned grid = (unsigned)((n + 255) / 256);
-    KernelTimer t(c, BOA_K_AGG, 0, (double)n * 6.0);
-    hipLaunchKernelGGL(k_erode_axis, dim3(grid), dim3(256), 0, c->stream, dev_mask, dev_out, Z, Y, X, 2, lo, hi);
-    hipLaunchKernelGGL(k_erode_axis, dim3(grid), dim3(256), 0, c->stream, dev_out, dev_tmp, Z, Y, X, 1, lo, hi);
-    hipLaunchKernelGGL(k_erode_axis, dim3(grid), dim3(256), 0, c->stream, dev_tmp, dev_out, Z, Y, X, 0, lo, hi);
-    t.stop();
-    BOA_HIP_TRY(hipGetLastError());
-    return BOA_OK;
-}
-
-// ------------------------------------------------------------------------------------------------------
-// 26-connected components by atomic union-find (roots = smallest linear index of each component)
-#define AGENT_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-
-__device__ __forceinline__ int uf_find(int* L, int i) {
-    // path halving: every node on the way is re-pointed to its grandparent (parents only ever move towards the root, so a racing
-    // walker at worst takes the longer way).  The store is an agent-scope atomic store like every other access to L in the
-    // union kernels: a plain store stays dirty in the L2 of the XCD that issued it, and when that line is written back it can
-    // take stale copies of NEIGHBOURING words with it -- words that another XCD's atomicMin has meanwhile changed at the
-    // memory side.  Measured: with plain stores 1 labelling in ~200 lost one union (a voxel keeps a root that was merged away)
-    // whenever a second stream kept the GPU busy (tools/ccl_stress.py, tests/test_gpu_lanes.py); with atomic stores 0 in 2 400.
-    int p = AGENT_LOAD(&L[i]);
-    while (p != i) {
-        const int gp = AGENT_LOAD(&L[p]);
-        if (gp != p) __hip_atomic_store(&L[i], gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        i = p;
-        p = gp;
-    }
-    return i;
-}
-
-__device__ __forceinline__ void uf_union(int* L, int a, int b) {
-    while (true) {
-        a = uf_find(L, a);
-        b = uf_find(L, b);
-        if (a == b) return;
-        if (a < b) {
-            int t = a;
-            a = b;
-            b = t;
-        }
-        int old = atomicMin(&L[a], b);  // link the larger root under the smaller
-        if (old == a) return;
-        a = old;
-    }
-}
-
-// ---- two-level labelling: tiles of CCL_TX x CCL_TY x CCL_TZ voxels are labelled in LDS first, then only the unions that
-// cross a tile face go through global memory.  A per-voxel version (uf_union on every voxel) spent its time in device-scope atomics
-// and pointer chasing through HBM (5.7 ms per 512^3 mask); inside a tile the same union-find runs on LDS words.  Forest invariant:
-// parent index <= own index, root = smallest linear index of the component.
-#define CCL_TX 32
-#define CCL_TY 16
-#define CCL_TZ 16
-#define CCL_TILE (CCL_TX * CCL_TY * CCL_TZ)
-
-__device__ __forceinline__ int lds_find(volatile int* L, int i) {
-    int p = L[i];
-    while (p != i) {
-        const int gp = L[p];
-        if (gp != p) L[i] = gp;  // path halving (a racing walker at worst takes the longer way)
-        i = p;
-        p = gp;
-    }
-    return i;
-}
-
-__device__ __forceinline__ void lds_union(int* L, int a, int b) {
-    while (true) {
-        a = lds_find(L, a);
-        b = lds_find(L, b);
-        if (a == b) return;
-        if (a < b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = atomicMin(&L[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_ccl_local(const unsigned char* __restrict__ mask, int Z, int Y, int X, int tiles_x, int tiles_y,
-                                                   int* __restrict__ L, unsigned int* __restrict__ sizes) {
-    __shared__ int lab[CCL_TILE];  // union-find parents; reused for the component sizes once every voxel knows its root
-    __shared__ unsigned int rowbits[CCL_TY * CCL_TZ];  // bit lx of word (lz, ly): voxel is foreground
-    const int tid = threadIdx.x;
-    int t = blockIdx.x;
-    const int tx = t % tiles_x;
-    t /= tiles_x;
-    const int ty = t % tiles_y, tz = t / tiles_y;
-    const int x0 = tx * CCL_TX, y0 = ty * CCL_TY, z0 = tz * CCL_TZ;
-    // one wave-wide ballot per row pair: lane (row r of the pair, lx)
-    for (int r2 = tid >> 5; r2 < CCL_TY * CCL_TZ; r2 += 8) {
-        const int lx = tid & 31, ly = r2 % CCL_TY, lz = r2 / CCL_TY;
-        const int x = x0 + lx, y = y0 + ly, z = z0 + lz;
-        const bool fg = x < X && y < Y && z < Z && mask[((size_t)z * Y + y) * X + x] != 0;
-        const unsigned long long b = __ballot(fg);
-        if (lx == 0) rowbits[r2] = (unsigned int)(b >> (32 * ((tid >> 5) & 1)));
-    }
-    __syncthreads();
-    // uniform tiles (all background, or a full tile of foreground: one component rooted at its first voxel) skip the union-find:
-    // body-sized masks and their inverses are mostly such tiles.  Same forest as the general path (root = smallest index).
-    {
-        unsigned int w_and = 0xffffffffu, w_or = 0u;
-        for (int r2 = tid; r2 < CCL_TY * CCL_TZ; r2 += 256) {
-            w_and &= rowbits[r2];
-            w_or |= rowbits[r2];
-        }
-        const int all0 = __syncthreads_and(w_or == 0u);
-        const int all1 = __syncthreads_and(w_and == 0xffffffffu);
-        if (all0 || all1) {
-            const int root = (int)(((size_t)z0 * Y + y0) * X + x0);
-#pragma unroll
-            for (int k = 0; k < CCL_TILE / 256; ++k) {
-                const int r2 = (tid >> 5) + 8 * k, lx = tid & 31, ly = r2 % CCL_TY, lz = r2 / CCL_TY;
-                const int x = x0 + lx, y = y0 + ly, z = z0 + lz;
-                if (x >= X || y >= Y || z >= Z) continue;   // (all1 implies the tile lies inside the volume)
-                const size_t gi = ((size_t)z * Y + y) * X + x;
-                L[gi] = all1 ? root : -1;
-                sizes[gi] = (all1 && r2 == 0 && lx == 0) ? (unsigned int)CCL_TILE : 0u;
-            }
-            return;
-        }
-    }
-    // parents start at the first voxel of the voxel's x-run (the runs of a row are its components: no unions along x at all)
-    for (int r2 = tid >> 5; r2 < CCL_TY * CCL_TZ; r2 += 8) {
-        const int lx = tid & 31;
-        const unsigned int me = rowbits[r2];
-        const unsigned int starts = me & ~(me << 1);                       // first voxel of every run
-        const unsigned int upto = starts & (0xffffffffu >> (31 - lx));     // run starts at or left of lx
-        lab[r2 * CCL_TX + lx] = ((me >> lx) & 1u) ? r2 * CCL_TX + (31 - __clz((int)upto)) : -1;
-    }
-    __syncthreads();
-    // unions between the runs of neighbouring rows (the four forward rows (dz, dy) = (0, 1), (1, -1), (1, 0), (1, 1)): ONE union per
-    // pair of touching runs -- at the first voxel where both rows are set, or, for runs that only touch diagonally, at the run end
-    // facing the other run.  (The first version linked every voxel to the voxel below it: ~5 LDS union-finds per voxel.)
-    for (int r2 = tid >> 5; r2 < CCL_TY * CCL_TZ; r2 += 8) {
-        const int lx = tid & 31, ly = r2 % CCL_TY, lz = r2 / CCL_TY;
-        const unsigned int me = rowbits[r2];
-        if (!((me >> lx) & 1u)) continue;
-        const int i = r2 * CCL_TX + lx;
-        const bool a_l = lx > 0 && ((me >> (lx - 1)) & 1u), a_r = lx + 1 < CCL_TX && ((me >> (lx + 1)) & 1u);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int dz = r == 0 ? 0 : 1, dy = r == 0 ? 1 : r - 2;
-            const int zz = lz + dz, yy = ly + dy;
-            if (zz >= CCL_TZ || yy < 0 || yy >= CCL_TY) continue;
-            const int rr = zz * CCL_TY + yy;
-            const unsigned int w = rowbits[rr];
-            const bool m0 = lx > 0 && ((w >> (lx - 1)) & 1u), m1 = (w >> lx) & 1u, m2 = lx + 1 < CCL_TX && ((w >> (lx + 1)) & 1u);
-            const int row = rr * CCL_TX;
-            if (m1) {
-                if (!(a_l && m0)) lds_union(lab, i, row + lx);          // first voxel of the overlap of the two runs
-            } else {
-                if (m2 && !a_r) lds_union(lab, i, row + lx + 1);        // my run ends here, the other starts diagonally
-                if (m0 && !a_l) lds_union(lab, i, row + lx - 1);        // my run starts here, the other ends diagonally
-            }
-        }
-    }
-    __syncthreads();
-    // global labels: the tile-local root's linear index in the volume; voxel counts of the local components (LDS atomics:
-    // the per-voxel global atomics of the one-level version were its second most expensive part)
-    int myroot[CCL_TILE / 256];
-#pragma unroll
-    for (int k = 0; k < CCL_TILE / 256; ++k) {
-        const int r2 = (tid >> 5) + 8 * k, lx = tid & 31;
-        myroot[k] = -1;
-        if ((rowbits[r2] >> lx) & 1u) myroot[k] = lds_find(lab, r2 * CCL_TX + lx);
-    }
-    __syncthreads();
-    unsigned int* cnt = (unsigned int*)lab;  // (a second 32 KiB array halved the occupancy: 2.1 -> 4.0 ms per 512^3 mask)
-#pragma unroll
-    for (int k = 0; k < CCL_TILE / 256; ++k) cnt[tid + 256 * k] = 0;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < CCL_TILE / 256; ++k) {
-        const int lx = tid & 31;
-        // one LDS atomic per run of equal roots in the row (a solid tile would otherwise put 8 192 atomics on one word)
-        const int prev = __shfl_up(myroot[k], 1);
-        const bool lead = lx == 0 || prev != myroot[k];
-        const unsigned int leads = (unsigned int)(__ballot(lead) >> (32 * ((tid >> 5) & 1)));  // this row's half of the wave
-        if (lead && myroot[k] >= 0) {
-            const unsigned int after = lx == 31 ? 0u : (leads >> (lx + 1));
-            const int len = after ? __ffs((int)after) : 32 - lx;
-            atomicAdd(&cnt[myroot[k]], (unsigned int)len);
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < CCL_TILE / 256; ++k) {
-        const int r2 = (tid >> 5) + 8 * k, lx = tid & 31, ly = r2 % CCL_TY, lz = r2 / CCL_TY;
-        const int x = x0 + lx, y = y0 + ly, z = z0 + lz;
-        if (x >= X || y >= Y || z >= Z) continue;
-        int out = -1;
-        if (myroot[k] >= 0) {
-            const int rt = myroot[k];
-            const int rx = rt % CCL_TX, rr = rt / CCL_TX;
-            out = (int)(((size_t)(z0 + rr / CCL_TY) * Y + (y0 + rr % CCL_TY)) * X + (x0 + rx));
-        }
-        const size_t gi = ((size_t)z * Y + y) * X + x;
-        L[gi] = out;
-        sizes[gi] = cnt[r2 * CCL_TX + lx];  // > 0 only at tile-local roots (every voxel is written: no memset of `sizes`)
-    }
-}
-
-// after the border unions: every voxel points at its global root; a tile-local root that is not the global root hands its count
-// over (one global atomic per tile-local component instead of one per voxel)
-__global__ __launch_bounds__(256) void k_ccl_resolve(size_t n, int* L, unsigned int* sizes, int* n_comp) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    int is_root = 0;
-    unsigned int pend_c = 0u;
-    int pend_root = 0;
-    if (i < n) {
-        const int p0 = L[i];
-        if (p0 >= 0) {
-            int root = p0, p = L[root];
-            while (p != root) {
-                root = p;
-                p = L[root];
-            }
-            if (root != p0) L[i] = root;
-            if (root == (int)i) {
-                is_root = 1;
-            } else {
-                const unsigned int c = sizes[i];
-                if (c) {
-                    pend_c = c;
-                    pend_root = root;
-                    // (agent-scope store, not a plain one: the same line may hold a root's count that other XCDs are adding to)
-                    __hip_atomic_store(&sizes[i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-        }
-    }
-    // hand the counts over: body-sized masks are ONE giant component, so nearly every tile-local root of the volume adds to the same
-    // word -- a device-scope atomic per tile-local component serialises at that address (resolve took 0.2 ms on a mask of scattered
-    // specks and 2 ms on a solid one).  Two rounds of wave-level aggregation on the most common root of the wave, then the rest one
-    // by one.
-    {
-        const int lane = threadIdx.x & 63;
-#pragma unroll 1
-        for (int round = 0; round < 2; ++round) {
-            const unsigned long long act = __ballot(pend_c != 0u);
-            if (!act) break;
-            const int leader = __ffsll((long long)act) - 1;
-            const int r0 = __shfl(pend_root, leader);
-            const bool mine = pend_c != 0u && pend_root == r0;
-            unsigned int sum = mine ? pend_c : 0u;
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) sum += __shfl_xor(sum, m);
-            if (lane == leader) atomicAdd(&sizes[r0], sum);
-            if (mine) pend_c = 0u;
-        }
-        if (pend_c) atomicAdd(&sizes[pend_root], pend_c);
-    }
-    const unsigned long long b = __ballot(is_root);
-    if ((threadIdx.x & 63) == 0 && b) atomicAdd(n_comp, __popcll(b));
-}
-
-// unions across tile faces only: voxels on the faces x = 0 (its x - 1 neighbours in the later rows), x = TX-1, y = 0 (the
-// (dz, dy) = (1, -1) row), y = TY-1 and z = TZ-1 of their tile have forward neighbours in another tile
-__device__ __forceinline__ void ccl_border_voxel(const unsigned char* __restrict__ mask, int Z, int Y, int X, int* L, int x, int y, int z) {
-    const size_t i = ((size_t)z * Y + y) * X + x;
-    const int lx = x % CCL_TX, ly = y % CCL_TY, lz = z % CCL_TZ;
-    if (!mask[i]) return;
-    if (lx == CCL_TX - 1 && x + 1 < X && mask[i + 1]) uf_union(L, (int)i, (int)(i + 1));
-    const bool left = x > 0 && mask[i - 1];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int dz = r == 0 ? 0 : 1, dy = r == 0 ? 1 : r - 2;
-        const int zz = z + dz, yy = y + dy;
-        if (zz >= Z || yy < 0 || yy >= Y) continue;
-        const bool row_other = (dz && lz == CCL_TZ - 1) || (dy == 1 && ly == CCL_TY - 1) || (dy == -1 && ly == 0);
-        const size_t row = ((size_t)zz * Y + yy) * X;
-        const bool m0 = x > 0 && mask[row + x - 1], m1 = mask[row + x] != 0, m2 = x + 1 < X && mask[row + x + 1];
-        // (a link inside the tile was made in LDS; x - 1 / x + 1 of the other row hang on its x voxel through that row's own links)
-        if (row_other) {
-            // the whole row lies in another tile.  A foreground left neighbour (same face, so it runs this code too -- in this tile
-            // or the one to the left) has linked itself to x - 2, x - 1, x of that row already, so only x + 1 is new; within the
-            // triple one link is enough when consecutive voxels of that row are foreground (that row's own x + 1 links join them)
-            if (!left) {
-                if (m1) {
-                    uf_union(L, (int)i, (int)(row + x));
-                } else {
-                    if (m0) uf_union(L, (int)i, (int)(row + x - 1));
-                    if (m2) uf_union(L, (int)i, (int)(row + x + 1));
-                }
-            } else if (m2 && !m1) {
-                uf_union(L, (int)i, (int)(row + x + 1));
-            }
-        } else if (!m1) {
-            if (m0 && lx == 0) uf_union(L, (int)i, (int)(row + x - 1));
-            if (m2 && lx == CCL_TX - 1) uf_union(L, (int)i, (int)(row + x + 1));
-        }
-    }
-}
-
-// The face voxels are enumerated directly (23 % of the volume; the first version launched over every voxel and returned for the
-// rest: 1.9 of the 5.5 ms of a 512^3 mask).  mode 0: whole rows of the planes lz = TZ-1 (grid: x blocks, Y, planes);
-// mode 1: the rows ly = 0 and ly = TY-1 of the other planes (grid: x blocks, 2 rows per y tile, Z);
-// mode 2: the x-face voxels lx = 0 / TX-1 of the remaining rows (thread <-> (x tile, face, y), grid: blocks, 1, Z).
-__global__ __launch_bounds__(256) void k_ccl_border(const unsigned char* __restrict__ mask, int Z, int Y, int X, int* L, int mode) {
-    if (mode == 0) {
-        const int x = (int)blockIdx.x * 256 + (int)threadIdx.x, y = (int)blockIdx.y, z = (int)blockIdx.z * CCL_TZ + CCL_TZ - 1;
-        if (x >= X || z >= Z) return;
-        ccl_border_voxel(mask, Z, Y, X, L, x, y, z);
-    } else if (mode == 1) {
-        const int x = (int)blockIdx.x * 256 + (int)threadIdx.x, z = (int)blockIdx.z;
-        const int y = ((int)blockIdx.y >> 1) * CCL_TY + (((int)blockIdx.y & 1) ? CCL_TY - 1 : 0);
-        if (x >= X || y >= Y || (z % CCL_TZ) == CCL_TZ - 1) return;
-        ccl_border_voxel(mask, Z, Y, X, L, x, y, z);
-    } else {
-        const int tiles_x = (X + CCL_TX - 1) / CCL_TX;
-        const int t = (int)blockIdx.x * 256 + (int)threadIdx.x, z = (int)blockIdx.z;
-        const int f = t % (2 * tiles_x), y = t / (2 * tiles_x);
-        const int x = (f >> 1) * CCL_TX + ((f & 1) ? CCL_TX - 1 : 0);
-        if (y >= Y || x >= X) return;
-        const int ly = y % CCL_TY;
-        if ((z % CCL_TZ) == CCL_TZ - 1 || ly == 0 || ly == CCL_TY - 1) return;   // rows of modes 0 / 1
-        ccl_border_voxel(mask, Z, Y, X, L, x, y, z);
-    }
-}
-
-extern "C" int boa_ccl26(boa_ctx* c, const uint8_t* dev_mask, int Z, int Y, int X, int32_t* dev_roots,
-                         uint32_t* dev_sizes, int* host_n_components) {
-    BOA_REQUIRE(c && dev_mask && dev_roots && dev_sizes && Z > 0 && Y > 0 && X > 0, "boa_ccl26: bad argument");
-    const size_t n = (size_t)Z * Y * X;
-    BOA_REQUIRE(n < (1ull << 31), "boa_ccl26: volume too large for int32 indices");
-    // the component counter: a pooled 4-byte block; without host_n_components nothing is copied back and the call does not
-    // synchronise (the BCA post-processing chains 16 of these per volume)
-    int* d_count = nullptr;
-    BOA_TRY(boa_malloc(c, sizeof(int), (void**)&d_count));
-    {   // (an early return must hand the pooled counter back)
-        const hipError_t e0 = hipMemsetAsync(d_count, 0, sizeof(int), c->stream);
-        if (e0 != hipSuccess) {
-            boa_free(c, d_count);
-            BOA_HIP_TRY(e0);
-        }
-    }
-    unsigned grid = (unsigned)((n + 255) / 256);
-    KernelTimer t(c, BOA_K_MORPH, 0, (double)n * 14.0);
-    const int tx = (X + CCL_TX - 1) / CCL_TX, ty = (Y + CCL_TY - 1) / CCL_TY, tz = (Z + CCL_TZ - 1) / CCL_TZ;
-    hipLaunchKernelGGL(k_ccl_local, dim3((unsigned)((size_t)tx * ty * tz)), dim3(256), 0, c->stream, dev_mask, Z, Y, X, tx, ty, dev_roots,
-                       dev_sizes);
-    hipLaunchKernelGGL(k_ccl_border, dim3((unsigned)((X + 255) / 256), (unsigned)Y, (unsigned)tz), dim3(256), 0, c->stream, dev_mask, Z, Y, X,
-                       dev_roots, 0);
-    hipLaunchKernelGGL(k_ccl_border, dim3((unsigned)((X + 255) / 256), (unsigned)(2 * ty), (unsigned)Z), dim3(256), 0, c->stream, dev_mask, Z,
-                       Y, X, dev_roots, 1);
-    hipLaunchKernelGGL(k_ccl_border, dim3((unsigned)(((size_t)2 * tx * Y + 255) / 256), 1, (unsigned)Z), dim3(256), 0, c->stream, dev_mask, Z, Y,
-                       X, dev_roots, 2);
-    hipLaunchKernelGGL(k_ccl_resolve, dim3(grid), dim3(256), 0, c->stream, n, dev_roots, dev_sizes, d_count);
-    t.stop();
-    hipError_t e = hipGetLastError();
-    if (host_n_components && e == hipSuccess) {
-        int cnt = 0;
-        e = hipMemcpyAsync(&cnt, d_count, sizeof(int), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        *host_n_components = cnt;
-    }
-    boa_free(c, d_count);  // (stream-ordered: the block is reused only by work queued after the kernels above)
-    BOA_HIP_TRY(e);
-    return BOA_OK;
-}
-
-__global__ __launch_bounds__(256) void k_ccl_best(const unsigned int* __restrict__ sizes, size_t n,
-                                                  unsigned long long* best) {
-    // grid-stride, one atomic per wave of a few thousand (one per 64 voxels was 2 M atomics on one word: 1.8 ms per 512^3 volume)
-    unsigned long long key = 0;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const unsigned int sz = sizes[i];
-        if (sz) {
-            const unsigned long long k = ((unsigned long long)sz << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)i);
-            key = k > key ? k : key;
-        }
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        unsigned long long o = __shfl_xor(key, m);
-        key = o > key ? o : key;
-    }
-    if ((threadIdx.x & 63) == 0 && key) atomicMax(best, key);
-}
-
-__global__ __launch_bounds__(256) void k_ccl_apply_largest(const int* __restrict__ roots, size_t n,
-                                                           const unsigned long long* best, unsigned char* seg, int fill) {
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const unsigned long long b = *best;
-    if (!b) return;
-    const int best_root = (int)(0xFFFFFFFFu - (unsigned)(b & 0xFFFFFFFFull));
-    const int r = roots[i];
-    if (r >= 0 && r != best_root) seg[i] = (unsigned char)fill;
-}
-
-extern "C" int boa_ccl_filter_largest(boa_ctx* c, const int32_t* dev_roots, const uint32_t* dev_sizes, size_t n,
-                                      uint8_t* dev_seg, int fill_value) {
-    BOA_REQUIRE(c && dev_roots && dev_sizes && dev_seg, "boa_ccl_filter_largest: NULL argument");
-    if (n == 0) return BOA_OK;
-    unsigned long long* d_best = nullptr;
-    BOA_TRY(boa_malloc(c, sizeof(unsigned long long), (void**)&d_best));   // (pooled: no synchronisation around the two kernels)
-    {
-        const hipError_t e0 = hipMemsetAsync(d_best, 0, sizeof(unsigned long long), c->stream);
-        if (e0 != hipSuccess) {   // (an early return must hand the pooled block back)
-            boa_free(c, d_best);
-            BOA_HIP_TRY(e0);
-        }
-    }
-    unsigned grid = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(k_ccl_best, dim3(std::min<unsigned>(grid, (unsigned)c->cu_count * 8)), dim3(256), 0, c->stream, dev_sizes, n, d_best);
-    hipLaunchKernelGGL(k_ccl_apply_largest, dim3(grid), dim3(256), 0, c->stream, dev_roots, n, d_best, dev_seg,
-                       fill_value);
-    hipError_t e = hipGetLastError();
-    boa_free(c, d_best);
-    BOA_HIP_TRY(e);
-    return BOA_OK;
-}
-
-__global__ __launch_bounds__(256) void k_ccl_remove_small(const int* __restrict__ roots, const unsigned int* __restrict__ sizes,
-                                                          size_t n, unsigned int max_size, unsigned char* mask) {
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int r = roots[i];
-    if (r >= 0 && sizes[r] <= max_size) mask[i] = 0;
-}
-
-extern "C" int boa_ccl_remove_small(boa_ctx* c, const int32_t* dev_roots, const uint32_t* dev_sizes, size_t n,
-                                    uint32_t max_size, uint8_t* dev_mask_inout) {
-    BOA_REQUIRE(c && dev_roots && dev_sizes && dev_mask_inout, "boa_ccl_remove_small: NULL argument");
-    if (n == 0) return BOA_OK;
-    unsigned grid = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(k_ccl_remove_small, dim3(grid), dim3(256), 0, c->stream, dev_roots, dev_sizes, n, max_size,
-                       dev_mask_inout);
-    BOA_HIP_TRY(hipGetLastError());
-    return BOA_OK;
-}
-
-
-// ------------------------------------------------------------------------------------------------------
-// z-slab sharded connected components (SURVEY 8e "aggregation stages"): each rank labels its slab with boa_ccl26; the
-// components that touch a slab interface are merged on the host over the exchanged boundary planes (boa_hip/agg_shard.py).
-// These helpers move the small per-component tables between the device and the host.
-__global__ __launch_bounds__(256) void k_ccl_list(const unsigned int* __restrict__ sizes, size_t n, int max_out, int* __restrict__ roots_out,
-                                                  unsigned int* __restrict__ sizes_out, int* __restrict__ count) {
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const unsigned s = sizes[i];
-    if (s == 0) return;
-    const int k = atomicAdd(count, 1);
-    if (k < max_out) {
-        roots_out[k] = (int)i;
-        sizes_out[k] = s;
-    }
-}
-
-extern "C" int boa_ccl_list_components(boa_ctx* c, const uint32_t* dev_sizes, size_t n, int max_out, int32_t* host_roots,
-                                       uint32_t* host_sizes, int* host_count) {
-    BOA_REQUIRE(c && dev_sizes && host_roots && host_sizes && host_count && max_out >= 0, "boa_ccl_list_components: bad argument");
-    int* d_cnt = nullptr;
-    int* d_roots = nullptr;
-    unsigned* d_sz = nullptr;
-    BOA_TRY(boa_malloc(c, sizeof(int), (void**)&d_cnt));
-    int rc = boa_malloc(c, (size_t)std::max(max_out, 1) * 4, (void**)&d_roots);
-    if (!rc) rc = boa_malloc(c, (size_t)std::max(max_out, 1) * 4, (void**)&d_sz);
-    if (!rc) {
-        hipMemsetAsync(d_cnt, 0, sizeof(int), c->stream);
-        if (n) hipLaunchKernelGGL(k_ccl_list, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, dev_sizes, n, max_out, d_roots, d_sz, d_cnt);
-        c->prof_break = true;
-        hipError_t e = hipMemcpyAsync(host_count, d_cnt, sizeof(int), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        const int m = std::min(*host_count, max_out);
-        if (e == hipSuccess && m > 0) e = hipMemcpy(host_roots, d_roots, (size_t)m * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && m > 0) e = hipMemcpy(host_sizes, d_sz, (size_t)m * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) {
-            boa_set_error("boa_ccl_list_components: %s", hipGetErrorString(e));
-            rc = BOA_EHIP;
-        }
-    }
-    boa_free(c, d_cnt);
-    if (d_roots) boa_free(c, d_roots);
-    if (d_sz) boa_free(c, d_sz);
-    return rc;
-}
-
-__global__ __launch_bounds__(256) void k_scatter_u32(const int* __restrict__ idx, const unsigned int* __restrict__ val, int m,
-                                                     unsigned int* __restrict__ dst) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < m) dst[idx[i]] = val[i];
-}
-
-extern "C" int boa_scatter_u32(boa_ctx* c, uint32_t* dev_dst, const int32_t* host_idx, const uint32_t* host_val, int m) {
-    BOA_REQUIRE(c && dev_dst && (m == 0 || (host_idx && host_val)) && m >= 0, "boa_scatter_u32: bad argument");
-    if (m == 0) return BOA_OK;
-    int* d_i = nullptr;
-    unsigned* d_v = nullptr;
-    BOA_TRY(boa_malloc(c, (size_t)m * 4, (void**)&d_i));
-    int rc = boa_malloc(c, (size_t)m * 4, (void**)&d_v);
-    if (!rc) {
-        c->prof_break = true;
-        // (stream-ordered copies: d_i / d_v may be recycled blocks whose previous user still has work queued on the stream)
-        hipError_t e = hipMemcpyAsync(d_i, host_idx, (size_t)m * 4, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_v, host_val, (size_t)m * 4, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_scatter_u32, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, d_i, d_v, m, dev_dst);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // the host arrays are borrowed for the duration of the call
-        if (e != hipSuccess) {
-            boa_set_error("boa_scatter_u32: %s", hipGetErrorString(e));
-            rc = BOA_EHIP;
-        }
-    }
-    boa_free(c, d_i);
-    if (d_v) boa_free(c, d_v);
-    return rc;
-}
-
-__global__ __launch_bounds__(256) void k_ccl_fill_unmarked(const int* __restrict__ roots, const unsigned int* __restrict__ sizes, size_t n,
-                                                           unsigned int mark, unsigned char* __restrict__ seg, int fill) {
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int r = roots[i];
-    if (r >= 0 && sizes[r] != mark) seg[i] = (unsigned char)fill;
-}
-
-extern "C" int boa_ccl_fill_unmarked(boa_ctx* c, const int32_t* dev_roots, const uint32_t* dev_sizes, size_t n, uint32_t mark,
-                                     uint8_t* dev_seg, int fill_value) {
-    BOA_REQUIRE(c && dev_roots && dev_sizes && dev_seg, "boa_ccl_fill_unmarked: NULL argument");
-    if (n == 0) return BOA_OK;
-    KernelTimer t(c, BOA_K_MORPH, 0, (double)n * 6.0);
-    hipLaunchKernelGGL(k_ccl_fill_unmarked, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, dev_roots, dev_sizes, n, mark,
-                       dev_seg, fill_value);
-    t.stop();
     BOA_HIP_TRY(hipGetLastError());
     return BOA_OK;
 }

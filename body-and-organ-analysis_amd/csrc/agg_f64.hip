@@ -1,5 +1,6 @@
 // Voxel statistics of CT values held as float64 (what `get_fdata()` returns for float-valued, scaled or out-of-int16-range CTs):
-// per-group exact order statistics by radix select, count / sum / centred sum of squares, and the float form of the tissue pass.
+// per-group exact order statistics by radix select, count / sum / centred sum of squares.  (The float form of the tissue pass is an
+// instantiation of k_tissue_aggregate, agg.hip.)
 // The int16 path (agg.hip) reads order statistics off a (label, HU) histogram; doubles have no such histogram.
 #include <string.h>
 
@@ -374,142 +375,5 @@ extern "C" int boa_group_stats_f64(boa_ctx* c, const double* dev_ct, const uint8
         r[3] = h_m2[g];
         for (int k = 0; k < 6; ++k) r[4 + k] = h_out[g * GS_SLOTS + 1 + k];
     }
-    return BOA_OK;
-}
-
-// ------------------------------------------------------------------------------------------------------
-// The tissue pass of agg.hip (k_tissue_aggregate) on float HU: the rules of BCA/tissue/definition.py:22-30 compare the float value
-// itself (`image >= lo` and `image <= hi`: -29.5 is neither muscle nor adipose tissue, -190.0 is adipose), the per-slice counts
-// are exact, the per-slice HU sums are fp64 (wave and block reduction, then one fp64 atomic per block and counter).
-__device__ __forceinline__ int tissue_of_f64(double hu, int region) {
-    const bool adip = hu >= -190.0 && hu <= -30.0;
-    int t = 0;
-    if (region == 2 && hu >= -29.0 && hu <= 150.0) t = 1;
-    if (region == 5 && hu >= -1000.0 && hu <= 3000.0) t = 2;
-    if (adip) {
-        if (region == 1) t = 3;
-        if (region == 3) t = 4;
-        if (region == 2) t = 5;
-        if (region == 9) t = 6;
-        if (region == 7) t = 7;
-    }
-    return t;
-}
-
-template <int VEC>
-__global__ __launch_bounds__(256) void k_tissue_aggregate_f64(const double* __restrict__ ct, const double* __restrict__ ct_rules,
-                                                              const unsigned char* __restrict__ regions,
-                                                              const unsigned char* __restrict__ parts, unsigned char* __restrict__ tissues,
-                                                              int slice_vox, unsigned int* __restrict__ counts, double* __restrict__ sums) {
-    __shared__ unsigned int s_cnt[16];
-    __shared__ double s_sum[16];
-    const int z = blockIdx.y;
-    if (threadIdx.x < 16) {
-        s_cnt[threadIdx.x] = 0;
-        s_sum[threadIdx.x] = 0.0;
-    }
-    __syncthreads();
-    int cnt[2][8];
-    double sum[2][8];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            cnt[a][t] = 0;
-            sum[a][t] = 0.0;
-        }
-    const size_t base = (size_t)z * slice_vox;
-    const int nvec = slice_vox / VEC;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < nvec; i += gridDim.x * 256) {
-        double hu[VEC] __attribute__((aligned(16)));
-        double hr[VEC] __attribute__((aligned(16)));
-        unsigned char rg[VEC] __attribute__((aligned(4)));
-        unsigned char pt[VEC] __attribute__((aligned(4)));
-        unsigned char ts[VEC] __attribute__((aligned(4)));
-        const size_t o = base + (size_t)i * VEC;
-        if (VEC == 4) {
-            *(double2*)hu = *(const double2*)(ct + o);
-            *(double2*)(hu + 2) = *(const double2*)(ct + o + 2);
-            if (ct_rules) {
-                *(double2*)hr = *(const double2*)(ct_rules + o);
-                *(double2*)(hr + 2) = *(const double2*)(ct_rules + o + 2);
-            } else {
-#pragma unroll
-                for (int j = 0; j < VEC; ++j) hr[j] = hu[j];
-            }
-            *(unsigned int*)rg = *(const unsigned int*)(regions + o);
-            if (parts) *(unsigned int*)pt = *(const unsigned int*)(parts + o);
-        } else {
-            hu[0] = ct[o];
-            hr[0] = ct_rules ? ct_rules[o] : hu[0];
-            rg[0] = regions[o];
-            if (parts) pt[0] = parts[o];
-        }
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-            const int t = tissue_of_f64(hr[j], rg[j]);
-            ts[j] = (unsigned char)t;
-            const bool torso = parts && pt[j] == 1;
-#pragma unroll
-            for (int k = 1; k < 8; ++k) {
-                const bool m = (t == k);
-                cnt[0][k] += m ? 1 : 0;
-                sum[0][k] += m ? hu[j] : 0.0;
-                cnt[1][k] += (m && torso) ? 1 : 0;
-                sum[1][k] += (m && torso) ? hu[j] : 0.0;
-            }
-        }
-        if (tissues) {
-            if (VEC == 4)
-                *(unsigned int*)(tissues + o) = *(const unsigned int*)ts;
-            else
-                tissues[o] = ts[0];
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int k = 1; k < 8; ++k) {
-            int c = cnt[a][k];
-            double s = sum[a][k];
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) {
-                c += __shfl_xor(c, m);
-                s += __shfl_xor(s, m);
-            }
-            if ((threadIdx.x & 63) == 0 && c) {
-                atomicAdd(&s_cnt[a * 8 + k], (unsigned int)c);
-                atomicAdd(&s_sum[a * 8 + k], s);
-            }
-        }
-    __syncthreads();
-    if (threadIdx.x < 16 && s_cnt[threadIdx.x]) {
-        atomicAdd(&counts[(size_t)z * 16 + threadIdx.x], s_cnt[threadIdx.x]);
-        atomicAdd(&sums[(size_t)z * 16 + threadIdx.x], s_sum[threadIdx.x]);
-    }
-}
-
-extern "C" int boa_tissue_aggregate_f64(boa_ctx* c, const double* dev_ct, const double* dev_ct_rules, const uint8_t* dev_regions,
-                                        const uint8_t* dev_parts, uint8_t* dev_tissues_out, int Z, int Y, int X, uint32_t* dev_counts,
-                                        double* dev_hu_sums) {
-    BOA_REQUIRE(c && dev_ct && dev_regions && dev_counts && dev_hu_sums, "boa_tissue_aggregate_f64: NULL argument");
-    BOA_REQUIRE(Z > 0 && Y > 0 && X > 0 && (long long)Y * X < (1ll << 30), "boa_tissue_aggregate_f64: bad dims");
-    BOA_HIP_TRY(hipMemsetAsync(dev_counts, 0, (size_t)Z * 16 * sizeof(uint32_t), c->stream));
-    BOA_HIP_TRY(hipMemsetAsync(dev_hu_sums, 0, (size_t)Z * 16 * sizeof(double), c->stream));   // (all-zero bytes are +0.0)
-    const int sv = Y * X;
-    const bool vec4 = (sv % 4 == 0) && (((uintptr_t)dev_ct) % 16 == 0) && (((uintptr_t)dev_ct_rules) % 16 == 0) && (((uintptr_t)dev_regions) % 4 == 0) &&
-                      (((uintptr_t)dev_parts) % 4 == 0) && (((uintptr_t)dev_tissues_out) % 4 == 0);
-    const int nvec = vec4 ? sv / 4 : sv;
-    const int gx = std::min(ceil_div(nvec, 256), 32);
-    const double vox = (double)Z * sv;
-    KernelTimer t(c, BOA_K_AGG, 0, vox * (9.0 + (dev_ct_rules ? 8 : 0) + (dev_parts ? 1 : 0) + (dev_tissues_out ? 1 : 0)));
-    if (vec4)
-        hipLaunchKernelGGL(k_tissue_aggregate_f64<4>, dim3(gx, Z), dim3(256), 0, c->stream, dev_ct, dev_ct_rules, dev_regions, dev_parts,
-                           dev_tissues_out, sv, dev_counts, dev_hu_sums);
-    else
-        hipLaunchKernelGGL(k_tissue_aggregate_f64<1>, dim3(gx, Z), dim3(256), 0, c->stream, dev_ct, dev_ct_rules, dev_regions, dev_parts,
-                           dev_tissues_out, sv, dev_counts, dev_hu_sums);
-    t.stop();
-    BOA_HIP_TRY(hipGetLastError());
     return BOA_OK;
 }

@@ -5,14 +5,14 @@
 //   BCA/body_regions/postprocess.py:8-40 (_filter_largest_unique_segment: all 26-connected components of a mask but the largest -> 255)
 // on BIT-PACKED masks, batched over the independent masks of a call.
 //
-// Why a second implementation next to boa_ccl26 (agg.hip): that one keeps a 4-byte parent and a 4-byte count PER VOXEL and runs
+// Why a second implementation next to boa_ccl26 (ccl_bytes.hip): that one keeps a 4-byte parent and a 4-byte count PER VOXEL and runs
 // select -> fill -> label -> resolve -> decide as separate passes over byte masks, one label after the other: ~26 bytes per voxel
 // and labelling, 16 labellings per volume, 85 ms per 512^3 `total+bca` step.  What the filters need is one bit per voxel ("is this
 // voxel's component small / not the largest"), so here
 //   * a mask is [Z][Y][ceil(X / 32)] words (bit i of word w <-> x = 32 w + i): 1 bit per voxel, and the six per-label pipelines of
 //     body_parts -- which all read the ORIGINAL label volume (`mask == label`) and are independent until `out[filled] = label` -- are
 //     one batch [M][Z][Y][W];
-//   * the union-find runs on COMPONENTS, not voxels: a 32 x 16 x 16 tile is labelled in LDS exactly as in k_ccl_local, its local
+//   * the union-find runs on COMPONENTS, not voxels: a 32 x 16 x 16 tile is labelled in LDS by the helpers of ccl_tile.h (as in k_ccl_local), its local
 //     components get dense ids 0 .. n - 1 (n <= 1024: components of a 26-connected labelling are >= 2 apart), a voxel keeps its 16-bit
 //     local id (only in tiles that are neither empty nor full), and parent / size / first-voxel live in a table of 1024 entries per
 //     tile of which only the first n are ever touched.  Unions across tile faces, root resolution and size hand-over work on table
@@ -28,15 +28,10 @@
 #include <algorithm>
 
 #include "common.h"
+#include "ccl_tile.h"
 
-#define CB_TX 32
-#define CB_TY 16
-#define CB_TZ 16
-#define CB_TILE (CB_TX * CB_TY * CB_TZ)
 #define CB_CAP 1024          // table entries per tile
 #define CB_BG 0xFFFFu        // local id of a background voxel
-
-#define CB_AGENT_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 
 struct CbGeom {
     int Z, Y, X, W;          // W = words per row
@@ -282,60 +277,6 @@ struct CbTab {
     unsigned short* ids;    // [M][vox]            local id per voxel (mixed tiles only)
 };
 
-__device__ __forceinline__ int cb_find(int* P, int i) {
-    int p = CB_AGENT_LOAD(&P[i]);
-    while (p != i) {
-        const int gp = CB_AGENT_LOAD(&P[p]);
-        if (gp != p) __hip_atomic_store(&P[i], gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (agent-scope like every access to P here:
-        i = p;                                                                                      //  see uf_find in agg.hip)
-        p = gp;
-    }
-    return i;
-}
-
-__device__ __forceinline__ void cb_union(int* P, int a, int b) {
-    while (true) {
-        a = cb_find(P, a);
-        b = cb_find(P, b);
-        if (a == b) return;
-        if (a < b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = atomicMin(&P[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
-__device__ __forceinline__ int cb_lds_find(volatile int* L, int i) {
-    int p = L[i];
-    while (p != i) {
-        const int gp = L[p];
-        if (gp != p) L[i] = gp;
-        i = p;
-        p = gp;
-    }
-    return i;
-}
-
-__device__ __forceinline__ void cb_lds_union(int* L, int a, int b) {
-    while (true) {
-        a = cb_lds_find(L, a);
-        b = cb_lds_find(L, b);
-        if (a == b) return;
-        if (a < b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = atomicMin(&L[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
 // the mask word of row (z, y), word column w, of mask m; `inv`: the complement inside the volume
 __device__ __forceinline__ unsigned cb_word(const unsigned* __restrict__ bits, const CbGeom& g, int m, int z, int y, int w, int inv) {
     if (z < 0 || y < 0 || w < 0 || z >= g.Z || y >= g.Y || w >= g.W) return 0u;
@@ -345,19 +286,19 @@ __device__ __forceinline__ unsigned cb_word(const unsigned* __restrict__ bits, c
 
 // One tile (32 x 16 x 16 = one mask word per row) of one mask: local labelling in LDS, dense local ids, table entries.
 __global__ __launch_bounds__(256) void k_cb_local(const unsigned* __restrict__ bits, CbGeom g, int inv, CbTab T) {
-    __shared__ int lab[CB_TILE];                  // union-find parents; then the per-root counts; then the per-root dense ids
-    __shared__ unsigned int rowbits[CB_TY * CB_TZ];
-    __shared__ unsigned int rootbits[CB_TY * CB_TZ];
-    __shared__ int rowpre[CB_TY * CB_TZ + 1];
+    __shared__ int lab[CCL_TILE];                  // union-find parents; then the per-root counts; then the per-root dense ids
+    __shared__ unsigned int rowbits[CCL_TY * CCL_TZ];
+    __shared__ unsigned int rootbits[CCL_TY * CCL_TZ];
+    __shared__ int rowpre[CCL_TY * CCL_TZ + 1];
     const int tid = threadIdx.x, m = blockIdx.y;
     int t = blockIdx.x;
     const int tx = t % g.tx;
     t /= g.tx;
     const int ty = t % g.ty, tz = t / g.ty;
-    const int x0 = tx * CB_TX, y0 = ty * CB_TY, z0 = tz * CB_TZ;
+    const int x0 = tx * CCL_TX, y0 = ty * CCL_TY, z0 = tz * CCL_TZ;
     const size_t tile = (size_t)m * g.tiles + blockIdx.x;
     {
-        const int ly = tid % CB_TY, lz = tid / CB_TY;
+        const int ly = tid % CCL_TY, lz = tid / CCL_TY;
         rowbits[tid] = cb_word(bits, g, m, z0 + lz, y0 + ly, tx, inv);
     }
     __syncthreads();
@@ -375,65 +316,30 @@ __global__ __launch_bounds__(256) void k_cb_local(const unsigned* __restrict__ b
                 const size_t e = (size_t)m * g.tiles * CB_CAP + gid;
                 T.ncomp[tile] = -1;
                 T.parent[e] = gid;
-                T.size[e] = CB_TILE;
+                T.size[e] = CCL_TILE;
                 T.first[e] = (int)(((size_t)z0 * g.Y + y0) * g.X + x0);
             }
             return;
         }
     }
-    // parents start at the first voxel of the voxel's x-run; ONE union per pair of touching runs of neighbouring rows (k_ccl_local)
-    for (int r2 = tid >> 5; r2 < CB_TY * CB_TZ; r2 += 8) {
-        const int lx = tid & 31;
-        const unsigned int me = rowbits[r2];
-        const unsigned int starts = me & ~(me << 1);
-        const unsigned int upto = starts & (0xffffffffu >> (31 - lx));
-        lab[r2 * CB_TX + lx] = ((me >> lx) & 1u) ? r2 * CB_TX + (31 - __clz((int)upto)) : -1;
-    }
+    // the tile's own labelling (ccl_tile.h): run starts, one union per pair of touching runs, roots
+    ccl_tile_init_runs(rowbits, lab, tid);
     __syncthreads();
-    // (measured and not kept: one neighbour-row class per phase with a pointer-jumping pass in between -- 42.8 -> 50.6 ms on the 512^3
-    //  noise labels: the chains are short, the extra passes are not)
-    for (int r2 = tid >> 5; r2 < CB_TY * CB_TZ; r2 += 8) {
-        const int lx = tid & 31, ly = r2 % CB_TY, lz = r2 / CB_TY;
-        const unsigned int me = rowbits[r2];
-        if (!((me >> lx) & 1u)) continue;
-        const int i = r2 * CB_TX + lx;
-        const bool a_l = lx > 0 && ((me >> (lx - 1)) & 1u), a_r = lx + 1 < CB_TX && ((me >> (lx + 1)) & 1u);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int dz = r == 0 ? 0 : 1, dy = r == 0 ? 1 : r - 2;
-            const int zz = lz + dz, yy = ly + dy;
-            if (zz >= CB_TZ || yy < 0 || yy >= CB_TY) continue;
-            const int rr = zz * CB_TY + yy;
-            const unsigned int w = rowbits[rr];
-            const bool m0 = lx > 0 && ((w >> (lx - 1)) & 1u), m1 = (w >> lx) & 1u, m2 = lx + 1 < CB_TX && ((w >> (lx + 1)) & 1u);
-            const int row = rr * CB_TX;
-            if (m1) {
-                if (!(a_l && m0)) cb_lds_union(lab, i, row + lx);
-            } else {
-                if (m2 && !a_r) cb_lds_union(lab, i, row + lx + 1);
-                if (m0 && !a_l) cb_lds_union(lab, i, row + lx - 1);
-            }
-        }
-    }
+    ccl_tile_union_rows(rowbits, lab, tid);
     __syncthreads();
-    int myroot[CB_TILE / 256];
-#pragma unroll
-    for (int k = 0; k < CB_TILE / 256; ++k) {
-        const int r2 = (tid >> 5) + 8 * k, lx = tid & 31;
-        myroot[k] = -1;
-        if ((rowbits[r2] >> lx) & 1u) myroot[k] = cb_lds_find(lab, r2 * CB_TX + lx);
-    }
+    int myroot[CCL_TILE / 256];
+    ccl_tile_roots(rowbits, lab, tid, myroot);
     __syncthreads();
     // which voxels are roots (one ballot per row pair), their dense ids by a prefix sum over the rows
 #pragma unroll
-    for (int k = 0; k < CB_TILE / 256; ++k) {
+    for (int k = 0; k < CCL_TILE / 256; ++k) {
         const int r2 = (tid >> 5) + 8 * k, lx = tid & 31;
-        const unsigned long long b = __ballot(myroot[k] == r2 * CB_TX + lx);
+        const unsigned long long b = __ballot(myroot[k] == r2 * CCL_TX + lx);
         if (lx == 0) rootbits[r2] = (unsigned int)(b >> (32 * ((tid >> 5) & 1)));
     }
     unsigned int* cnt = (unsigned int*)lab;
 #pragma unroll
-    for (int k = 0; k < CB_TILE / 256; ++k) cnt[tid + 256 * k] = 0;
+    for (int k = 0; k < CCL_TILE / 256; ++k) cnt[tid + 256 * k] = 0;
     __syncthreads();
     {   // exclusive scan of popc(rootbits[row]) over the 256 rows: wave scan + wave totals
         const int c = __popc(rootbits[tid]);
@@ -451,47 +357,35 @@ __global__ __launch_bounds__(256) void k_cb_local(const unsigned* __restrict__ b
         rowpre[tid] = basew + s - c;
         if (tid == 255) rowpre[256] = basew + s;
     }
-#pragma unroll
-    for (int k = 0; k < CB_TILE / 256; ++k) {
-        const int lx = tid & 31;
-        // one LDS atomic per run of equal roots in the row
-        const int prev = __shfl_up(myroot[k], 1);
-        const bool lead = lx == 0 || prev != myroot[k];
-        const unsigned int leads = (unsigned int)(__ballot(lead) >> (32 * ((tid >> 5) & 1)));
-        if (lead && myroot[k] >= 0) {
-            const unsigned int after = lx == 31 ? 0u : (leads >> (lx + 1));
-            const int len = after ? __ffs((int)after) : 32 - lx;
-            atomicAdd(&cnt[myroot[k]], (unsigned int)len);
-        }
-    }
+    ccl_tile_count_runs(cnt, tid, myroot);
     __syncthreads();
     const int n_local = rowpre[256];
     // table entries of the local components; the root's LDS word then becomes its dense id
-    int did[CB_TILE / 256];
+    int did[CCL_TILE / 256];
 #pragma unroll
-    for (int k = 0; k < CB_TILE / 256; ++k) {
+    for (int k = 0; k < CCL_TILE / 256; ++k) {
         const int r2 = (tid >> 5) + 8 * k, lx = tid & 31;
         did[k] = -1;
-        if (myroot[k] == r2 * CB_TX + lx) {
+        if (myroot[k] == r2 * CCL_TX + lx) {
             const int d = rowpre[r2] + __popc(rootbits[r2] & ((1u << lx) - 1u));
             did[k] = d;
             const int gid = (int)blockIdx.x * CB_CAP + d;
             const size_t e = (size_t)m * g.tiles * CB_CAP + gid;
-            const int ly = r2 % CB_TY, lz = r2 / CB_TY;
+            const int ly = r2 % CCL_TY, lz = r2 / CCL_TY;
             T.parent[e] = gid;
-            T.size[e] = cnt[r2 * CB_TX + lx];
+            T.size[e] = cnt[r2 * CCL_TX + lx];
             T.first[e] = (int)(((size_t)(z0 + lz) * g.Y + (y0 + ly)) * g.X + (x0 + lx));
         }
     }
     __syncthreads();
 #pragma unroll
-    for (int k = 0; k < CB_TILE / 256; ++k)
-        if (did[k] >= 0) lab[((tid >> 5) + 8 * k) * CB_TX + (tid & 31)] = did[k];
+    for (int k = 0; k < CCL_TILE / 256; ++k)
+        if (did[k] >= 0) lab[((tid >> 5) + 8 * k) * CCL_TX + (tid & 31)] = did[k];
     if (tid == 0) T.ncomp[tile] = n_local;
     __syncthreads();
 #pragma unroll
-    for (int k = 0; k < CB_TILE / 256; ++k) {
-        const int r2 = (tid >> 5) + 8 * k, lx = tid & 31, ly = r2 % CB_TY, lz = r2 / CB_TY;
+    for (int k = 0; k < CCL_TILE / 256; ++k) {
+        const int r2 = (tid >> 5) + 8 * k, lx = tid & 31, ly = r2 % CCL_TY, lz = r2 / CCL_TY;
         const int x = x0 + lx, y = y0 + ly, z = z0 + lz;
         if (x >= g.X || y >= g.Y || z >= g.Z) continue;
         T.ids[(size_t)m * g.vox + ((size_t)z * g.Y + y) * g.X + x] = myroot[k] >= 0 ? (unsigned short)lab[myroot[k]] : (unsigned short)CB_BG;
@@ -500,15 +394,16 @@ __global__ __launch_bounds__(256) void k_cb_local(const unsigned* __restrict__ b
 
 // global id of a FOREGROUND voxel
 __device__ __forceinline__ int cb_gid(const CbGeom& g, const CbTab& T, int m, int x, int y, int z) {
-    const int tile = ((z / CB_TZ) * g.ty + (y / CB_TY)) * g.tx + (x / CB_TX);
+    const int tile = ((z / CCL_TZ) * g.ty + (y / CCL_TY)) * g.tx + (x / CCL_TX);
     const int nc = T.ncomp[(size_t)m * g.tiles + tile];
     if (nc < 0) return tile * CB_CAP;
     return tile * CB_CAP + (int)T.ids[(size_t)m * g.vox + ((size_t)z * g.Y + y) * g.X + x];
 }
 
-// unions across tile faces (the face voxels are enumerated as in k_ccl_border, agg.hip: same neighbour logic, on component ids)
+// unions across tile faces, on mask words and component ids (the rule: "unions across tile faces" in ccl_tile.h); rows of this tile
+// are skipped early and two all-foreground tiles are linked once per tile pair by k_cb_border_tiles, not here
 __device__ __forceinline__ void cb_border_voxel(const unsigned* __restrict__ bits, const CbGeom& g, const CbTab& T, int m, int inv, int x, int y, int z) {
-    const int lx = x % CB_TX, ly = y % CB_TY, lz = z % CB_TZ;
+    const int lx = x % CCL_TX, ly = y % CCL_TY, lz = z % CCL_TZ;
     const int w = x >> 5;
     const unsigned me = cb_word(bits, g, m, z, y, w, inv);
     if (!((me >> lx) & 1u)) return;
@@ -519,10 +414,10 @@ __device__ __forceinline__ void cb_border_voxel(const unsigned* __restrict__ bit
         return my;
     };
     // (two all-foreground tiles are linked once per tile pair by k_cb_border_tiles, not once per touching voxel pair)
-    const bool me_full = T.ncomp[(size_t)m * g.tiles + ((z / CB_TZ) * g.ty + (y / CB_TY)) * g.tx + (x / CB_TX)] < 0;
+    const bool me_full = T.ncomp[(size_t)m * g.tiles + ((z / CCL_TZ) * g.ty + (y / CCL_TY)) * g.tx + (x / CCL_TX)] < 0;
     auto link = [&](int xx, int yy, int zz) {
-        if (me_full && T.ncomp[(size_t)m * g.tiles + ((zz / CB_TZ) * g.ty + (yy / CB_TY)) * g.tx + (xx / CB_TX)] < 0) return;
-        cb_union(P, mine(), cb_gid(g, T, m, xx, yy, zz));
+        if (me_full && T.ncomp[(size_t)m * g.tiles + ((zz / CCL_TZ) * g.ty + (yy / CCL_TY)) * g.tx + (xx / CCL_TX)] < 0) return;
+        uf_union(P, mine(), cb_gid(g, T, m, xx, yy, zz));
     };
     // the three neighbour bits x - 1, x, x + 1 of a row from ONE mask word (a second one only on the word's first / last bit)
     auto row3 = [&](int yy, int zz, bool& b0, bool& b1, bool& b2) {
@@ -534,15 +429,15 @@ __device__ __forceinline__ void cb_border_voxel(const unsigned* __restrict__ bit
     };
     bool own0, own1, own2;
     row3(y, z, own0, own1, own2);
-    if (lx == CB_TX - 1 && own2) link(x + 1, y, z);
+    if (lx == CCL_TX - 1 && own2) link(x + 1, y, z);
     const bool left = own0;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int dz = r == 0 ? 0 : 1, dy = r == 0 ? 1 : r - 2;
         const int zz = z + dz, yy = y + dy;
         if (zz >= g.Z || yy < 0 || yy >= g.Y) continue;
-        const bool row_other = (dz && lz == CB_TZ - 1) || (dy == 1 && ly == CB_TY - 1) || (dy == -1 && ly == 0);
-        if (!row_other && lx != 0 && lx != CB_TX - 1) continue;   // (a row of this tile: only its x - 1 / x + 1 voxels in the x-neighbour tiles matter)
+        const bool row_other = (dz && lz == CCL_TZ - 1) || (dy == 1 && ly == CCL_TY - 1) || (dy == -1 && ly == 0);
+        if (!row_other && lx != 0 && lx != CCL_TX - 1) continue;   // (a row of this tile: only its x - 1 / x + 1 voxels in the x-neighbour tiles matter)
         bool m0, m1, m2;
         row3(yy, zz, m0, m1, m2);
         if (row_other) {
@@ -558,7 +453,7 @@ __device__ __forceinline__ void cb_border_voxel(const unsigned* __restrict__ bit
             }
         } else if (!m1) {
             if (m0 && lx == 0) link(x - 1, yy, zz);
-            if (m2 && lx == CB_TX - 1) link(x + 1, yy, zz);
+            if (m2 && lx == CCL_TX - 1) link(x + 1, yy, zz);
         }
     }
 }
@@ -585,25 +480,25 @@ __global__ __launch_bounds__(256) void k_cb_border_tiles(const unsigned* __restr
                 const int nt = (nz * g.ty + ny) * g.tx + nx;
                 const int nn = T.ncomp[(size_t)m * g.tiles + nt];
                 if (nn < 0)
-                    cb_union(T.parent + (size_t)m * g.tiles * CB_CAP, (int)blockIdx.x * CB_CAP, nt * CB_CAP);
+                    uf_union(T.parent + (size_t)m * g.tiles * CB_CAP, (int)blockIdx.x * CB_CAP, nt * CB_CAP);
                 else if (nn > 0)
                     mixed = 1;
             }
         }
         if (!__syncthreads_or(mixed)) return;
     }
-    const int x0 = tx * CB_TX, y0 = ty * CB_TY, z0 = tz * CB_TZ;
-    constexpr int N0 = CB_TX * CB_TY, N1 = 2 * (CB_TZ - 1) * CB_TX, N2 = 2 * (CB_TY - 2) * (CB_TZ - 1);
+    const int x0 = tx * CCL_TX, y0 = ty * CCL_TY, z0 = tz * CCL_TZ;
+    constexpr int N0 = CCL_TX * CCL_TY, N1 = 2 * (CCL_TZ - 1) * CCL_TX, N2 = 2 * (CCL_TY - 2) * (CCL_TZ - 1);
     for (int i = tid; i < N0 + N1 + N2; i += 256) {
         int lx, ly, lz;
         if (i < N0) {
-            lx = i % CB_TX; ly = i / CB_TX; lz = CB_TZ - 1;
+            lx = i % CCL_TX; ly = i / CCL_TX; lz = CCL_TZ - 1;
         } else if (i < N0 + N1) {
             const int j = i - N0;
-            lx = j % CB_TX; lz = (j / CB_TX) % (CB_TZ - 1); ly = (j / (CB_TX * (CB_TZ - 1))) ? CB_TY - 1 : 0;
+            lx = j % CCL_TX; lz = (j / CCL_TX) % (CCL_TZ - 1); ly = (j / (CCL_TX * (CCL_TZ - 1))) ? CCL_TY - 1 : 0;
         } else {
             const int j = i - N0 - N1;
-            lx = (j & 1) ? CB_TX - 1 : 0; ly = 1 + (j >> 1) % (CB_TY - 2); lz = (j >> 1) / (CB_TY - 2);
+            lx = (j & 1) ? CCL_TX - 1 : 0; ly = 1 + (j >> 1) % (CCL_TY - 2); lz = (j >> 1) / (CCL_TY - 2);
         }
         const int x = x0 + lx, y = y0 + ly, z = z0 + lz;
         if (x >= g.X || y >= g.Y || z >= g.Z) continue;
@@ -629,10 +524,10 @@ __global__ __launch_bounds__(256) void k_cb_resolve(CbGeom g, CbTab T, int n_mas
         int pend_root = 0, pend_first = 0;
         if (k < nc) {
             const int gid = tile * CB_CAP + k;
-            int root = gid, p = CB_AGENT_LOAD(&P[root]);
+            int root = gid, p = AGENT_LOAD(&P[root]);
             while (p != root) {
                 root = p;
-                p = CB_AGENT_LOAD(&P[root]);
+                p = AGENT_LOAD(&P[root]);
             }
             if (root != gid) {
                 __hip_atomic_store(&P[gid], root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -643,7 +538,7 @@ __global__ __launch_bounds__(256) void k_cb_resolve(CbGeom g, CbTab T, int n_mas
         }
         // hand-over: body-sized masks and the complements of sparse ones are ONE giant component, so nearly every merged local
         // component of the volume adds to the same word -- one device-scope atomic each serialises at that address (k_ccl_resolve in
-        // agg.hip has the same remedy).  Rounds of wave-level aggregation on the root of the first pending lane, then the rest singly.
+        // ccl_bytes.hip has the same remedy).  Rounds of wave-level aggregation on the root of the first pending lane, then the rest singly.
 #pragma unroll 1
         for (int round = 0; round < 3; ++round) {
             const unsigned long long act = __ballot(pend_c != 0u);
@@ -682,7 +577,7 @@ __global__ __launch_bounds__(256) void k_cb_remove_small(unsigned* __restrict__ 
     const unsigned orig = bits[(size_t)m * g.words + wi];
     const unsigned cur = inv ? (~orig & cb_valid_word(g.X, w)) : orig;
     if (!cur) return;
-    const int tile = ((z / CB_TZ) * g.ty + (y / CB_TY)) * g.tx + w;
+    const int tile = ((z / CCL_TZ) * g.ty + (y / CCL_TY)) * g.tx + w;
     const int nc = T.ncomp[(size_t)m * g.tiles + tile];
     const int* P = T.parent + (size_t)m * g.tiles * CB_CAP;
     const unsigned* S = T.size + (size_t)m * g.tiles * CB_CAP;
@@ -747,7 +642,7 @@ __global__ __launch_bounds__(256) void k_cb_apply_largest(const unsigned* __rest
     const int w = (int)(wi % g.W);
     const size_t row = wi / g.W;
     const int y = (int)(row % g.Y), z = (int)(row / g.Y);
-    const int tile = ((z / CB_TZ) * g.ty + (y / CB_TY)) * g.tx + w;
+    const int tile = ((z / CCL_TZ) * g.ty + (y / CCL_TY)) * g.tx + w;
     const int nc = T.ncomp[tile];
     unsigned kill = 0;
     if (nc < 0) {
@@ -782,8 +677,8 @@ static CbGeom cb_geom(int Z, int Y, int X) {
     g.Z = Z; g.Y = Y; g.X = X;
     g.W = (X + 31) / 32;
     g.tx = g.W;
-    g.ty = (Y + CB_TY - 1) / CB_TY;
-    g.tz = (Z + CB_TZ - 1) / CB_TZ;
+    g.ty = (Y + CCL_TY - 1) / CCL_TY;
+    g.tz = (Z + CCL_TZ - 1) / CCL_TZ;
     g.words = (size_t)Z * Y * g.W;
     g.vox = (size_t)Z * Y * X;
     g.tiles = (size_t)g.tx * g.ty * g.tz;

@@ -6,36 +6,13 @@
 //   boa_median3_inplane scipy.ndimage.median_filter(size 3 on two axes, 1 on the slice axis, mode="reflect") of
 //                       tissue/subclassification.py:21-36 on int16 HU.
 //   boa_mask_assign     out[mask (!)= 0] = value   (`out[filled] = label`, body_parts/postprocess.py:50).
+//   boa_binary_erode    erode_region: separable box erosion, on bit masks (ccl_bits.hip) or, for reaches of 32 and more, on bytes.
 #include <algorithm>
 
 #include "common.h"
+#include "ccl_tile.h"
 
-#define AGENT_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-
-__device__ __forceinline__ int uf2_find(int* L, int i) {
-    int p = AGENT_LOAD(&L[i]);
-    while (p != i) {
-        i = p;
-        p = AGENT_LOAD(&L[i]);
-    }
-    return i;
-}
-
-__device__ __forceinline__ void uf2_union(int* L, int a, int b) {
-    while (true) {
-        a = uf2_find(L, a);
-        b = uf2_find(L, b);
-        if (a == b) return;
-        if (a < b) {
-            int t = a;
-            a = b;
-            b = t;
-        }
-        int old = atomicMin(&L[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
+// The background union-find below runs uf_find<false> / uf_union<false>: finds store nothing (no path halving).
 
 __global__ __launch_bounds__(256) void k_bg_init(const unsigned char* __restrict__ mask, size_t n, int* __restrict__ L,
                                                  unsigned char* __restrict__ flag) {
@@ -52,8 +29,8 @@ __global__ __launch_bounds__(256) void k_bg_merge(const unsigned char* __restric
     if (i >= n || mask[i]) return;
     const int x = (int)(i % X);
     const int y = (int)((i / X) % Y);
-    if (x > 0 && !mask[i - 1]) uf2_union(L, (int)i, (int)(i - 1));
-    if (y > 0 && !mask[i - X]) uf2_union(L, (int)i, (int)(i - X));
+    if (x > 0 && !mask[i - 1]) uf_union<false>(L, (int)i, (int)(i - 1));
+    if (y > 0 && !mask[i - X]) uf_union<false>(L, (int)i, (int)(i - X));
 }
 
 __global__ __launch_bounds__(256) void k_bg_flag_border(const unsigned char* __restrict__ mask, size_t n, int Y, int X,
@@ -62,7 +39,7 @@ __global__ __launch_bounds__(256) void k_bg_flag_border(const unsigned char* __r
     if (i >= n || mask[i]) return;
     const int x = (int)(i % X);
     const int y = (int)((i / X) % Y);
-    if (x == 0 || y == 0 || x == X - 1 || y == Y - 1) flag[uf2_find(L, (int)i)] = 1;
+    if (x == 0 || y == 0 || x == X - 1 || y == Y - 1) flag[uf_find<false>(L, (int)i)] = 1;
 }
 
 __global__ __launch_bounds__(256) void k_bg_fill(const unsigned char* __restrict__ mask, size_t n, int* L,
@@ -70,7 +47,7 @@ __global__ __launch_bounds__(256) void k_bg_fill(const unsigned char* __restrict
     size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     unsigned char v = 1;
-    if (!mask[i]) v = flag[uf2_find(L, (int)i)] ? 0 : 1;
+    if (!mask[i]) v = flag[uf_find<false>(L, (int)i)] ? 0 : 1;
     out[i] = v;
 }
 
@@ -536,6 +513,49 @@ extern "C" int boa_nonzero_bbox(boa_ctx* c, const void* dev_in, int dtype, const
         host_bbox[2 * a] = any ? bb[2 * a] : 0;
         host_bbox[2 * a + 1] = any ? bb[2 * a + 1] + 1 : dims[a];
     }
+    return BOA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// erode_region: AND over offsets [-(k/2) .. k - 1 - k/2] for even k (footprint padded at the end), symmetric for
+// odd k; outside the volume counts as set.  One pass per axis.
+__global__ __launch_bounds__(256) void k_erode_axis(const unsigned char* __restrict__ in, unsigned char* __restrict__ out,
+                                                    int Z, int Y, int X, int axis, int lo, int hi) {
+    const size_t n = (size_t)Z * Y * X;
+    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    int x, y, z;
+    idx3(i, Y, X, z, y, x);
+    const int pos = axis == 0 ? z : (axis == 1 ? y : x);
+    const int len = axis == 0 ? Z : (axis == 1 ? Y : X);
+    const size_t st = axis == 0 ? (size_t)Y * X : (axis == 1 ? (size_t)X : 1);
+    unsigned char r = 1;
+    for (int d = lo; d <= hi; ++d) {
+        const int q = pos + d;
+        if (q < 0 || q >= len) continue;
+        r &= (in[i + (long long)d * (long long)st] != 0) ? 1 : 0;
+    }
+    out[i] = r;
+}
+
+extern "C" int boa_binary_erode(boa_ctx* c, const uint8_t* dev_mask, uint8_t* dev_out, uint8_t* dev_tmp, int Z, int Y,
+                                int X, int kernel_value) {
+    BOA_REQUIRE(c && dev_mask && dev_out && dev_tmp && kernel_value >= 1, "boa_binary_erode: bad argument");
+    BOA_REQUIRE(dev_out != dev_mask && dev_tmp != dev_mask && dev_tmp != dev_out, "boa_binary_erode: buffers must differ");
+    const int k = kernel_value;
+    const int center = (k % 2 == 0) ? (k + 1) / 2 : k / 2;  // centre of the (padded) footprint
+    const int lo = -center, hi = k - 1 - center;
+    const size_t n = (size_t)Z * Y * X;
+    // bit-mask form (csrc/ccl_bits.hip): 1 byte read + 1 byte written per voxel and three passes over 1 / 8 byte per voxel, instead of
+    // three byte passes of one thread per voxel (1.9 ms -> 0.2 ms per 512^3 mask); the byte passes take reaches of 32 and more
+    if (lo > -32 && hi < 32) return boa_bits_erode_u8(c, dev_mask, dev_out, Z, Y, X, lo, hi);
+    unsigned grid = (unsigned)((n + 255) / 256);
+    KernelTimer t(c, BOA_K_AGG, 0, (double)n * 6.0);
+    hipLaunchKernelGGL(k_erode_axis, dim3(grid), dim3(256), 0, c->stream, dev_mask, dev_out, Z, Y, X, 2, lo, hi);
+    hipLaunchKernelGGL(k_erode_axis, dim3(grid), dim3(256), 0, c->stream, dev_out, dev_tmp, Z, Y, X, 1, lo, hi);
+    hipLaunchKernelGGL(k_erode_axis, dim3(grid), dim3(256), 0, c->stream, dev_tmp, dev_out, Z, Y, X, 0, lo, hi);
+    t.stop();
+    BOA_HIP_TRY(hipGetLastError());
     return BOA_OK;
 }
 

@@ -86,8 +86,8 @@ int boa_timer_stop(boa_ctx* ctx, int slot, float* ms_out);
 #define BOA_K_HEAD_ACCUM 4
 #define BOA_K_ARGMAX 5
 #define BOA_K_OTHER 6      /* memset, CTNormalization */
-#define BOA_K_AGG 7        /* tissue map / slice tables / label histograms / masks / erosion (agg.hip) */
-#define BOA_K_MORPH 8      /* connected components, contour fill, median (morph.hip) */
+#define BOA_K_AGG 7        /* tissue map / slice tables / label histograms / masks (agg.hip, agg_f64.hip); erosion (morph.hip, ccl_bits.hip) */
+#define BOA_K_MORPH 8      /* connected components (ccl_bytes.hip, ccl_bits.hip), contour fill, median (morph.hip) */
 #define BOA_K_RESAMPLE 9   /* cubic / nearest resampling (resample.hip) */
 #define BOA_K_COPY 10      /* boa_copy3 index remaps (reorientation, transposes, crops) */
 #define BOA_K_COUNT 11

@@ -1,5 +1,5 @@
 """Worst-case masks of tests/test_gpu_morph_worstcase.py: the structures that i.i.d. noise and random balls cannot produce and that
-the connected-component tables (csrc/ccl_bits.hip: 32 x 16 x 16 tiles, 1024 table entries per tile), the slice flood, the erosions
+the connected-component tables (csrc/ccl_bits.hip: 32 x 16 x 16 tiles labelled by csrc/ccl_tile.h, 1024 table entries per tile), the slice flood, the erosions
 and the cross dilation are most likely to get wrong.  numpy only, no device: every generator returns its mask(s) together with the
 facts the case is built to have, and tests/test_morph_cases_cpu.py proves those facts with the flood fills of tests/floodfill.py and
 with scipy.ndimage before a case reaches a GPU."""
@@ -7,7 +7,7 @@ import functools
 
 import numpy as np
 
-TX, TY, TZ = 32, 16, 16          # CB_TX / CB_TY / CB_TZ of ccl_bits.hip (also CCL_* of agg.hip)
+TX, TY, TZ = 32, 16, 16          # CCL_TX / CCL_TY / CCL_TZ of ccl_tile.h (the tiles of ccl_bits.hip and ccl_bytes.hip)
 CAP = 1024                       # CB_CAP: table entries per tile = the most 26-connected components a tile can hold
 S26 = np.ones((3, 3, 3), bool)
 
@@ -369,13 +369,13 @@ def small_volume_labels():
 
 # ---- erosion cases ---------------------------------------------------------------------------------------------------------------
 def erode_reach(k):
-    """offsets [lo, hi] per axis of boa_binary_erode(kernel_value = k) (agg.hip): the k^3 footprint, end-padded to k + 1 for even k"""
+    """offsets [lo, hi] per axis of boa_binary_erode(kernel_value = k) (morph.hip): the k^3 footprint, end-padded to k + 1 for even k"""
     center = (k + 1) // 2 if k % 2 == 0 else k // 2
     return -center, k - 1 - center
 
 
 def erode_on_bits(lo, hi):
-    """the rule of agg.hip: reaches below 32 run on bit masks (k_bits_erode_axis), larger ones on bytes (k_erode_axis)"""
+    """the rule of boa_binary_erode (morph.hip): reaches below 32 run on bit masks (k_bits_erode_axis), larger ones on bytes (k_erode_axis)"""
     return lo > -32 and hi < 32
 
 

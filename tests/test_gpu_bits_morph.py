@@ -1,7 +1,7 @@
 """GPU parity tests of the bit-mask morphology (csrc/ccl_bits.hip, through the C ABI): select / unpack / contour fill / batched
 small-object and small-hole removal / largest-component filter / label assign against scipy.ndimage (the restatement of the
 skimage / cv2 calls of BCA/body_parts/postprocess.py:7-52 and BCA/body_regions/postprocess.py:8-40) and against the
-byte-mask kernels (boa_ccl26 path) they replace.  Everything here is integer work: bit-exact."""
+byte-mask kernels (boa_ccl26 path, csrc/ccl_bytes.hip) they replace.  Everything here is integer work: bit-exact."""
 import ctypes as C
 
 import numpy as np

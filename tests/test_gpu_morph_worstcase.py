@@ -1,5 +1,5 @@
 """Worst-case structure tests of the mask morphology kernels: the bit-packed component filters, contour fill and erosion of
-csrc/ccl_bits.hip, their byte-mask twins in csrc/agg.hip (boa_ccl26, boa_ccl_remove_small, boa_ccl_filter_largest, k_erode_axis) and
+csrc/ccl_bits.hip, their byte-mask twins (boa_ccl26, boa_ccl_remove_small, boa_ccl_filter_largest of csrc/ccl_bytes.hip) and k_erode_axis /
 boa_fill_holes_2d / boa_binary_dilate_cross / boa_mask_assign / boa_label_overlay of csrc/morph.hip, on the masks of
 tests/morph_cases.py: component tables at capacity, ties whose raster order is not the tile order, a first voxel handed over from a
 later tile, 64 roots per wave, full tiles among mixed ones, long chains, baffled corridors of more than 256 rows, slices too large

@@ -33,7 +33,7 @@ def kernels(co):
         return []
     notes = subprocess.check_output([f"{LLVM}/llvm-readelf", "--notes", co], text=True)
     out = []
-    for blk in re.split(r"\n\s+- ", notes):
+    for blk in re.split(r"\n  - ", notes):   # one block per kernel (deeper list items -- .args, .language_version -- stay inside it)
         name = re.search(r"\.name:\s+(\S+)", blk)
         if not name or ".vgpr_count" not in blk:
             continue
