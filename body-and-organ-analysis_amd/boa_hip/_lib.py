@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BOA_HIP_LIB") or os.path.join(_HERE, "libboa_hip.so")
 
 BOA_OK, BOA_EINVAL, BOA_EHIP, BOA_ENOMEM, BOA_EINF = 0, -1, -2, -3, -4
+BOA_DEFLATE_DYNAMIC = 1     # flags of boa_deflate_members2
 K_CONV_MFMA, K_CONV_FIRST, K_CONVT, K_NORM_FINALIZE, K_HEAD_ACCUM, K_ARGMAX, K_OTHER, K_AGG, K_MORPH, K_RESAMPLE, K_COPY, K_COUNT = range(12)
 K_NAMES = ["conv_mfma", "conv_first", "convT_mfma", "norm_finalize", "head_accum", "finalize_argmax", "other", "aggregation",
            "morphology", "resample", "copy_remap"]
@@ -134,6 +135,7 @@ _PROTOS = {
     "boa_j2k_decode": (i32, [vp, vp, u64, i32, ip, i32, ip, vp, ip]),
     "boa_deflate_bound": (u64, [u64, u64]),
     "boa_deflate_members": (i32, [vp, vp, u64, u64, i32, vp, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]),
+    "boa_deflate_members2": (i32, [vp, vp, u64, u64, i32, i32, i32, vp, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]),
 }
 
 EXPORTS = sorted(_PROTOS)

@@ -248,10 +248,12 @@ def write_wrapped_members(f, members):
         f.write(gzip_member(body, crc, size))
 
 
-def device_deflate(ctx, src, n: int, row_bytes: int = 0, member_bytes: int = 0):
+def device_deflate(ctx, src, n: int, row_bytes: int = 0, member_bytes: int = 0, *, near_bytes: int = 1, dynamic: bool = False):
     """Deflate `n` payload bytes that are on the device (`src`: a c_void_p / address, bytes in file order) with
-    `boa_deflate_members` (csrc/deflate.hip): -> [(body, crc32, size)] per member of `member_bytes` (default: the 4 MiB of
-    write_gzip_members).  Only the compressed bytes and the offset / CRC tables are downloaded."""
+    `boa_deflate_members2` (csrc/deflate.hip): -> [(body, crc32, size)] per member of `member_bytes` (default: the 4 MiB of
+    write_gzip_members).  Only the compressed bytes and the offset / CRC tables are downloaded.  `near_bytes` (1 .. 16): the short
+    candidate distance, the item size of the voxels (other than 1 only with `dynamic`); `dynamic`: blocks may carry their own Huffman codes (smaller, and what makes
+    an int16 CT compress at all); the defaults give the fixed-code streams of `boa_deflate_members`."""
     import ctypes as C
     from . import _lib
     member_bytes = int(member_bytes) or _GZ_BLOCK
@@ -264,8 +266,9 @@ def device_deflate(ctx, src, n: int, row_bytes: int = 0, member_bytes: int = 0):
     out = ctx.alloc(cap)
     try:
         src = src if isinstance(src, C.c_void_p) else C.c_void_p(src)
-        _lib.check(ctx.lib.boa_deflate_members(ctx.h, src, n, member_bytes, int(row_bytes), out.vp, cap, offs, crcs),
-                   "boa_deflate_members")
+        flags = _lib.BOA_DEFLATE_DYNAMIC if dynamic else 0
+        _lib.check(ctx.lib.boa_deflate_members2(ctx.h, src, n, member_bytes, int(row_bytes), int(near_bytes), flags, out.vp, cap, offs, crcs),
+                   "boa_deflate_members2")
         comp = memoryview(out.download((int(offs[n_mem]),), np.uint8)) if offs[n_mem] else memoryview(b"")
     finally:
         out.free()
@@ -294,12 +297,15 @@ SAVE_DEVICE_ENV = "BOA_SAVE_DEVICE"
 
 
 def save_volume(path, data, affine, ctx=None, **kw):
-    """`save` for the file-level callers (compute_all_models, the ct_pfav writer): uint8 volumes of a `.gz` path go through the
-    device encoder when $BOA_SAVE_DEVICE is 1 (default off: DESIGN 4.9); everything else, and everything without the switch,
-    takes the CPU path (a DevArray is downloaded first)."""
+    """`save` for the file-level callers (compute_all_models, the ct_pfav writer, get_image_info): with $BOA_SAVE_DEVICE = 1 the
+    uint8 volumes of a `.gz` path go through the device encoder with its fixed codes, with $BOA_SAVE_DEVICE = 2 the uint8 and the
+    int16 volumes with dynamic codes (default off: DESIGN 4.9); everything else, and everything without the switch, takes the CPU
+    path (a DevArray is downloaded first)."""
     from .devarray import DevArray
-    if ctx is not None and os.environ.get(SAVE_DEVICE_ENV) == "1" and np.dtype(data.dtype) == np.uint8 and str(path).endswith(".gz"):
-        return save(path, data, affine, ctx=ctx, **kw)
+    mode = os.environ.get(SAVE_DEVICE_ENV)
+    dtypes = {"1": (np.uint8,), "2": (np.uint8, np.int16)}.get(mode, ())
+    if ctx is not None and np.dtype(data.dtype) in dtypes and str(path).endswith(".gz"):
+        return save(path, data, affine, ctx=ctx, dynamic=mode == "2", **kw)
     return save(path, data.download() if isinstance(data, DevArray) else data, affine, **kw)
 
 
@@ -365,11 +371,11 @@ def quatern_from_affine(affine: np.ndarray) -> Tuple[Tuple[float, float, float],
 
 def save(path, data: np.ndarray, affine: np.ndarray, like: Optional[NiftiHeader] = None,
          extensions: Optional[List[Tuple[int, bytes]]] = None, compresslevel: int = 1, threads: Optional[int] = None,
-         form_codes: Optional[Tuple[int, int]] = None, ctx=None):
+         form_codes: Optional[Tuple[int, int]] = None, ctx=None, dynamic: bool = False):
     """Write `data` (file axis order); `.gz` paths are deflated on `threads` cores (default SAVE_THREADS).  With `ctx` (a device
     Context) the data body of a `.gz` path is deflated on the device instead (device_deflate; same member container, so read_bytes
     inflates it in parallel as well), from a numpy array after an upload or from a 3-D DevArray without a download; the header and
-    the extensions stay on the CPU path.  `like`: header to copy (pixdim units, descrip, q/s-form codes ... as
+    the extensions stay on the CPU path.  `dynamic` (with `ctx`): dynamic Huffman codes, the near distance = the item size.  `like`: header to copy (pixdim units, descrip, q/s-form codes ... as
     `img_in_orig.header.copy()` keeps them); datatype/bitpix/dim/vox_offset and the affine fields are set from the
     arguments; scl_slope/inter are reset (label volumes are stored unscaled).  `form_codes`: also store the affine as a qform."""
     on_device = ctx is not None and str(path).endswith(".gz")
@@ -415,7 +421,10 @@ def save(path, data: np.ndarray, affine: np.ndarray, like: Optional[NiftiHeader]
     if on_device:
         buf, addr, nbytes, row = _device_body(ctx, data)
         try:
-            members = device_deflate(ctx, addr, nbytes, row)
+            if dynamic:
+                members = device_deflate(ctx, addr, nbytes, row, near_bytes=min(16, data.dtype.itemsize), dynamic=True)
+            else:
+                members = device_deflate(ctx, addr, nbytes, row)
         finally:
             if buf is not None:
                 buf.free()

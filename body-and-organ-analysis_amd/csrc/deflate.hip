@@ -1,7 +1,9 @@
 // Deflate encoder for label volumes (boa_deflate_members): the payload of a .nii.gz is cut into gzip members, every member into
 // deflate blocks of DFL_BLK input bytes, one workgroup per block.  RFC 1951 (the stream), RFC 1952 (CRC-32 of each member).
-//   k_deflate_block    match lengths against distance 1 and distance row_bytes, greedy parse by pointer jumping, fixed-Huffman
-//                      bit assembly in LDS (or a stored block where that is not smaller), the block's CRC-32; one slot per block
+//   k_deflate_block    match lengths against a near distance (1 .. 16) and distance row_bytes, greedy parse by pointer jumping, fixed-Huffman
+//                      bit assembly in LDS (or a stored block where that is not smaller), the block's CRC-32; one slot per block.
+//                      <true>: also counts the block's symbols, builds optimal length-limited codes and writes a dynamic-Huffman
+//                      block where that is smaller than both other forms
 //   k_deflate_scan     block sizes -> byte offsets; CRCs of the blocks -> CRC of each member
 //   k_deflate_compact  slots -> one contiguous body per member
 // Every block ends on a byte boundary (an empty stored block after a non-final fixed block, as pigz does), so bodies concatenate
@@ -60,10 +62,138 @@ __device__ __forceinline__ void or_bits(unsigned* words, unsigned bit_off, uint6
     if (hi) atomicOr(&words[(bit_off >> 5) + 1], hi);
 }
 
-// grid = blocks of all members in file order; dynamic LDS = OFF_DATA + hist + DFL_BLK + 16
+// ---- dynamic-Huffman blocks: work arrays inside the s_next region, which is dead once the parse is known.  What the bit assembly
+// still reads (DW_*) lies above the words s_out can use: a block is written dynamic only where that is smaller than stored, so
+// s_out ends below DFL_BLK + 16 bytes.  The scratch of the code construction (DS_*) lies below and is dead before s_out is zeroed.
+constexpr int DW_KEEP = OFF_NEXT + DFL_BLK + 32;
+constexpr int DW_HLL = DW_KEEP;                    // uint32 [288]: literal/length counts
+constexpr int DW_HD = DW_HLL + 288 * 4;            // uint32 [32]: distance counts
+constexpr int DW_HCL = DW_HD + 32 * 4;             // uint32 [32]: code-length symbol counts
+constexpr int DW_CNT = DW_HCL + 32 * 4;            // uint32 [16]: scalars (DC_*)
+constexpr int DW_ZERO_WORDS = 288 + 32 + 32 + 16;  // the four above are zeroed together
+constexpr int DW_TLL = DW_CNT + 16 * 4;            // uint32 [288]: stream bits | length << 16 per literal/length symbol
+constexpr int DW_TD = DW_TLL + 288 * 4;            // uint32 [32]
+constexpr int DW_TCL = DW_TD + 32 * 4;             // uint32 [32]
+constexpr int DW_LLL = DW_TCL + 32 * 4;            // uint8 [288]: code lengths
+constexpr int DW_LD = DW_LLL + 288;                // uint8 [32]
+constexpr int DW_LCL = DW_LD + 32;                 // uint8 [32]
+constexpr int DW_SEQ = DW_LCL + 32;                // uint8 [320]: the lengths the header codes, HLIT then HDIST of them
+constexpr int DW_HSYM = DW_SEQ + 320;              // uint16 [320]: their run-length code
+constexpr int DW_END = DW_HSYM + 320 * 2;
+constexpr int DS_CUR = OFF_NEXT;                   // uint32 [2][576]: item weights of the last two levels
+constexpr int DS_LEAFW = DS_CUR + 2 * 576 * 4;     // uint32 [288]: counts of the used symbols, sorted
+constexpr int DS_LEAFS = DS_LEAFW + 288 * 4;       // uint16 [288]: their symbols
+constexpr int DS_PKPOS = DS_LEAFS + 288 * 2;       // uint16 [16][288]: position of every package in its level
+constexpr int DS_LEV = DS_PKPOS + 16 * 288 * 2;    // uint32 [2][16]: packages of a level; leaves taken from a level
+static_assert(DS_LEV + 32 * 4 <= DW_KEEP && DW_END <= OFF_TOK && DW_KEEP % 16 == 0, "dynamic-code carve");
+static_assert(DW_KEEP - OFF_NEXT >= ((5 + DFL_BLK + 3) / 4 + 1) * 4, "s_out of a block smaller than stored ends below the kept arrays");
+enum { DC_LL_USED = 0, DC_LL_LAST, DC_D_USED, DC_D_LAST, DC_CL_USED, DC_CL_LAST, DC_EXTRA, DC_TOKBITS, DC_HDRBITS, DC_NHSYM, DC_HCLEN };
+
+// Code lengths of at most `limit` bits with the least total cost for the counts freq[0 .. nsym) (0 = unused symbol -> length 0), by
+// package-merge, the whole workgroup at work; one used symbol gets length 1.  cnt[0] / cnt[1] (zero on entry) return the number of
+// used symbols and the last one + 1.  The leaves are sorted by (count, symbol) with a rank count.  Level 1 is the leaves; level l
+// merges the leaves with the packages (pairs in order) of level l - 1, every item finding its place by a binary search in the other
+// list (a tie puts the leaf first), cut at 2 n - 2 items.  The first 2 n - 2 items of the last level are the solution: the packages
+// among them stand for twice as many items of the level below, and a symbol's length is the number of levels that take its leaf.
+// nsym <= 286, 2^limit >= nsym; ends with a barrier.
+__device__ void dfl_limited_lengths(const unsigned* freq, int nsym, int limit, unsigned char* len, unsigned* cnt, unsigned char* smem, int t) {
+    unsigned* cur = (unsigned*)(smem + DS_CUR);
+    unsigned* leafw = (unsigned*)(smem + DS_LEAFW);
+    unsigned short* leafs = (unsigned short*)(smem + DS_LEAFS);
+    unsigned short* pkpos = (unsigned short*)(smem + DS_PKPOS);
+    unsigned* lev = (unsigned*)(smem + DS_LEV);
+    if (t < nsym) {
+        const unsigned f = freq[t];
+        len[t] = 0;
+        if (f) {
+            int rank = 0;
+            for (int s = 0; s < nsym; ++s) {
+                const unsigned fs = freq[s];
+                rank += (fs && (fs < f || (fs == f && s < t))) ? 1 : 0;
+            }
+            leafw[rank] = f;
+            leafs[rank] = (unsigned short)t;
+            atomicAdd(&cnt[0], 1u);
+            atomicMax(&cnt[1], (unsigned)t + 1);
+        }
+    }
+    __syncthreads();
+    const int n = (int)cnt[0];
+    if (n < 2) {
+        if (n == 1 && t == 0) len[leafs[0]] = 1;
+        __syncthreads();
+        return;
+    }
+    const int cap = 2 * n - 2;
+    if (t < n) cur[t] = leafw[t];
+    int m = n;                                               // items of the level below
+    __syncthreads();
+    for (int l = 2; l <= limit; ++l) {
+        const unsigned* below = cur + ((l & 1) ? 576 : 0);
+        unsigned* here = cur + ((l & 1) ? 0 : 576);
+        const int np = m >> 1;
+        if (t < n) {
+            const unsigned w = leafw[t];
+            int lo = 0, hi = np;                             // the packages lighter than this leaf
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (below[2 * mid] + below[2 * mid + 1] < w) lo = mid + 1; else hi = mid;
+            }
+            if (t + lo < cap) here[t + lo] = w;
+        } else if (t >= 512 && t - 512 < np) {
+            const int q = t - 512;
+            const unsigned w = below[2 * q] + below[2 * q + 1];
+            int lo = 0, hi = n;                              // the leaves that are not heavier than this package
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (leafw[mid] <= w) lo = mid + 1; else hi = mid;
+            }
+            const int pos = q + lo;
+            pkpos[l * 288 + q] = (unsigned short)(pos < cap ? pos : cap);
+            if (pos < cap) here[pos] = w;
+        }
+        if (t == 0) lev[l] = (unsigned)np;
+        m = n + np < cap ? n + np : cap;
+        __syncthreads();
+    }
+    if (t == 0) {
+        int take = cap;                                      // items taken from the level
+        for (int l = limit; l >= 2; --l) {
+            int lo = 0, hi = (int)lev[l];                    // the packages among them
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (pkpos[l * 288 + mid] < take) lo = mid + 1; else hi = mid;
+            }
+            lev[16 + l] = (unsigned)(take - lo);
+            take = 2 * lo;
+        }
+        lev[16 + 1] = (unsigned)take;
+    }
+    __syncthreads();
+    if (t < n) {
+        unsigned L = 0;
+        for (int l = 1; l <= limit; ++l) L += (unsigned)t < lev[16 + l] ? 1u : 0u;
+        len[leafs[t]] = (unsigned char)L;
+    }
+    __syncthreads();
+}
+
+// f(position, token) for every token start of a thread's piece
+template <class F>
+__device__ __forceinline__ void for_each_token(unsigned starts, int p0, const unsigned short* s_tok, F f) {
+    for (unsigned m = starts; m; m &= m - 1) {
+        const int i = p0 + __builtin_ctz(m);
+        f(i, (unsigned)s_tok[i]);
+    }
+}
+
+// grid = blocks of all members in file order; dynamic LDS = OFF_DATA + hist + DFL_BLK + 16.  DYN: also try a dynamic-Huffman block
+// (BTYPE = 10) and take it where it is smaller than both other forms; near = the short candidate distance (1 without DYN).
+template <bool DYN>
 __global__ __launch_bounds__(DFL_NT) void k_deflate_block(const unsigned char* __restrict__ src, size_t n, unsigned member_bytes,
-                                                          unsigned bpm, int row, int hist, const unsigned* __restrict__ pw, unsigned* __restrict__ ws,
-                                                          unsigned* __restrict__ blk_size, unsigned* __restrict__ blk_crc) {
+                                                          unsigned bpm, int row, int hist, int near_arg, const unsigned* __restrict__ pw,
+                                                          unsigned* __restrict__ ws, unsigned* __restrict__ blk_size, unsigned* __restrict__ blk_crc) {
+    const int near = DYN ? near_arg : 1;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned short* s_next = (unsigned short*)(smem + OFF_NEXT);
     unsigned* s_out = (unsigned*)(smem + OFF_NEXT);
@@ -133,9 +263,9 @@ __global__ __launch_bounds__(DFL_NT) void k_deflate_block(const unsigned char* _
         const int inside = blen - p0;                                             // positions of this piece inside the block
         const unsigned in_mask = inside >= DFL_PIECE ? 0xffffu : inside > 0 ? (1u << inside) - 1 : 0u;
         if (in_mask) {
-            const int first1 = 1 - avail - p0;                                    // first k whose source byte is in the member
+            const int first1 = near - avail - p0;                                 // first k whose source byte is in the member
             const unsigned m1 = in_mask & (first1 <= 0 ? 0xffffu : first1 >= DFL_PIECE ? 0u : 0xffffu << first1);
-            if (m1) eq1 = eq_mask16(s_d, H + p0 - 1, own) & m1;
+            if (m1) eq1 = eq_mask16(s_d, H + p0 - near, own) & m1;
             if (row > 0) {
                 const int firstr = row - avail - p0;
                 const unsigned mr = in_mask & (firstr <= 0 ? 0xffffu : firstr >= DFL_PIECE ? 0u : 0xffffu << firstr);
@@ -165,7 +295,7 @@ __global__ __launch_bounds__(DFL_NT) void k_deflate_block(const unsigned char* _
             run1 = (eq1 >> k) & 1 ? run1 + 1 : 0;
             runr = (eqr >> k) & 1 ? runr + 1 : 0;
             const int l1 = run1 < DFL_MAXLEN ? run1 : DFL_MAXLEN, lr = runr < DFL_MAXLEN ? runr : DFL_MAXLEN;
-            int L = l1 >= lr ? l1 : lr;                    // a tie goes to distance 1: no extra distance bits
+            int L = l1 >= lr ? l1 : lr;                    // a tie goes to the near distance: no or fewer extra distance bits
             const unsigned far = l1 >= lr ? 0u : 0x8000u;
             if (L < 3) L = 0;
             const int i = p0 + k;
@@ -226,7 +356,7 @@ __global__ __launch_bounds__(DFL_NT) void k_deflate_block(const unsigned char* _
         const unsigned tv = s_tok[i];
         int nb;
         if (tv & 0x7fffu)
-            dfl_match(tv & 0x7fffu, (tv & 0x8000u) ? far_dist : 1, &nb);
+            dfl_match(tv & 0x7fffu, (tv & 0x8000u) ? far_dist : near, &nb);
         else
             dfl_literal(s_d[H + i], &nb);
         my_bits += nb;
@@ -255,6 +385,166 @@ __global__ __launch_bounds__(DFL_NT) void k_deflate_block(const unsigned char* _
     const unsigned out_bytes = fixed ? fixed_bytes : stored_bytes;
     const unsigned out_words = (out_bytes + 3) >> 2;            // <= DFL_SLOT / 4
     unsigned* slot = ws + g * (size_t)(DFL_SLOT / 4);
+    if constexpr (DYN) {
+        unsigned* h_ll = (unsigned*)(smem + DW_HLL);
+        unsigned* h_d = (unsigned*)(smem + DW_HD);
+        unsigned* h_cl = (unsigned*)(smem + DW_HCL);
+        unsigned* cnt = (unsigned*)(smem + DW_CNT);
+        unsigned* t_ll = (unsigned*)(smem + DW_TLL);
+        unsigned* t_d = (unsigned*)(smem + DW_TD);
+        unsigned* t_cl = (unsigned*)(smem + DW_TCL);
+        unsigned char* l_ll = smem + DW_LLL;
+        unsigned char* l_d = smem + DW_LD;
+        unsigned char* l_cl = smem + DW_LCL;
+        unsigned char* seq = smem + DW_SEQ;
+        unsigned short* hsym = (unsigned short*)(smem + DW_HSYM);
+        int near_eb, far_eb = 0;
+        unsigned near_ev, far_ev = 0, far_sym = 0;
+        const unsigned near_sym = dfl_dist_symbol((unsigned)near, &near_eb, &near_ev);
+        if (far_dist > 0) far_sym = dfl_dist_symbol((unsigned)far_dist, &far_eb, &far_ev);
+
+        // ---- counts of the literal/length and distance symbols over the token starts; a thread adds runs of one symbol at once ----
+        for (int i = t; i < DW_ZERO_WORDS; i += DFL_NT) h_ll[i] = 0;
+        __syncthreads();
+        {
+            unsigned extra = 0, n_near = 0, n_far = 0, run = 0, cur = 0;
+            for_each_token(starts, p0, s_tok, [&](int i, unsigned tv) {
+                unsigned sym;
+                if (tv & 0x7fffu) {
+                    int eb;
+                    unsigned ev;
+                    sym = dfl_len_symbol(tv & 0x7fffu, &eb, &ev);
+                    extra += (unsigned)eb;
+                    if (tv & 0x8000u) ++n_far; else ++n_near;
+                } else
+                    sym = s_d[H + i];
+                if (run && sym != cur) {
+                    atomicAdd(&h_ll[cur], run);
+                    run = 0;
+                }
+                cur = sym;
+                ++run;
+            });
+            if (run) atomicAdd(&h_ll[cur], run);
+            if (n_near) atomicAdd(&h_d[near_sym], n_near);
+            if (n_far) atomicAdd(&h_d[far_sym], n_far);
+            extra += n_near * (unsigned)near_eb + n_far * (unsigned)far_eb;
+            if (extra) atomicAdd(&cnt[DC_EXTRA], extra);
+            if (t == 0) h_ll[256] = 1;                      // end of block (no token counts it)
+        }
+        __syncthreads();
+
+        // ---- code lengths, the header's run-length code and its code lengths ----
+        dfl_limited_lengths(h_ll, DFL_NLL, 15, l_ll, cnt + DC_LL_USED, smem, t);
+        dfl_limited_lengths(h_d, DFL_ND, 15, l_d, cnt + DC_D_USED, smem, t);
+        const int hlit = (int)cnt[DC_LL_LAST];                                  // >= 257: the end-of-block symbol is in use
+        const int hdist = cnt[DC_D_LAST] ? (int)cnt[DC_D_LAST] : 1;             // no match at all: one distance code of length zero
+        if (t < hlit) seq[t] = l_ll[t];
+        else if (t < hlit + hdist) seq[t] = l_d[t - hlit];
+        __syncthreads();
+        if (t == 0) cnt[DC_NHSYM] = (unsigned)dfl_rle_lengths(seq, hlit + hdist, hsym, h_cl);
+        __syncthreads();
+        dfl_limited_lengths(h_cl, DFL_NCL, 7, l_cl, cnt + DC_CL_USED, smem, t);
+
+        // ---- code tables; the size of the dynamic form ----
+        {
+            unsigned bits = 0;
+            if (t < DFL_NLL) {
+                t_ll[t] = dfl_code_entry(l_ll, DFL_NLL, t);
+                bits = h_ll[t] * l_ll[t];
+            } else if (t >= 320 && t < 320 + DFL_ND) {
+                t_d[t - 320] = dfl_code_entry(l_d, DFL_ND, t - 320);
+                bits = h_d[t - 320] * l_d[t - 320];
+            } else if (t >= 384 && t < 384 + DFL_NCL) {
+                t_cl[t - 384] = dfl_code_entry(l_cl, DFL_NCL, t - 384);
+                const unsigned hb = h_cl[t - 384] * (l_cl[t - 384] + (unsigned)dfl_cl_extra_bits(t - 384));
+                if (hb) atomicAdd(&cnt[DC_HDRBITS], hb);
+            } else if (t == 448) {
+                int k = DFL_NCL;
+                while (k > 4 && l_cl[dfl_cl_order(k - 1)] == 0) --k;
+                cnt[DC_HCLEN] = (unsigned)k;
+            }
+            if (bits) atomicAdd(&cnt[DC_TOKBITS], bits);
+        }
+        __syncthreads();
+        const unsigned hclen = cnt[DC_HCLEN];
+        const unsigned hdr_bits = 3 + 5 + 5 + 4 + 3 * hclen + cnt[DC_HDRBITS];
+        const unsigned dyn_end = hdr_bits + cnt[DC_TOKBITS] + cnt[DC_EXTRA];    // (the end-of-block code is in DC_TOKBITS)
+        const unsigned dyn_sync = (dyn_end + 3 + 7) >> 3;
+        const unsigned dyn_bytes = bfinal ? (dyn_end + 7) >> 3 : dyn_sync + 4;
+        if (dyn_bytes < fixed_bytes && dyn_bytes < stored_bytes) {
+            // ---- bit offsets from the table's lengths, then the assembly as in the fixed form ----
+            unsigned dbits = 0;
+            for_each_token(starts, p0, s_tok, [&](int i, unsigned tv) {
+                if (tv & 0x7fffu) {
+                    int eb;
+                    unsigned ev;
+                    const unsigned sym = dfl_len_symbol(tv & 0x7fffu, &eb, &ev);
+                    dbits += (t_ll[sym] >> 16) + (unsigned)eb;
+                    dbits += (tv & 0x8000u) ? (t_d[far_sym] >> 16) + (unsigned)far_eb : (t_d[near_sym] >> 16) + (unsigned)near_eb;
+                } else
+                    dbits += t_ll[s_d[H + i]] >> 16;
+            });
+            unsigned dincl = dbits;
+#pragma unroll
+            for (int k = 1; k < 64; k <<= 1) {
+                const unsigned up = __shfl_up(dincl, k, 64);
+                if (lane >= k) dincl += up;
+            }
+            if (lane == 63) s_misc[wave] = dincl;
+            const unsigned dyn_words = (dyn_bytes + 3) >> 2;
+            for (unsigned w = t; w < dyn_words + 1; w += DFL_NT) s_out[w] = 0;
+            __syncthreads();
+            unsigned off = hdr_bits + (dincl - dbits);
+            for (int w = 0; w < wave; ++w) off += s_misc[w];
+            for_each_token(starts, p0, s_tok, [&](int i, unsigned tv) {
+                if (tv & 0x7fffu) {
+                    int eb;
+                    unsigned ev;
+                    const unsigned e = t_ll[dfl_len_symbol(tv & 0x7fffu, &eb, &ev)];
+                    or_bits(s_out, off, (e & 0xffffu) | (uint64_t)ev << (e >> 16));
+                    off += (e >> 16) + (unsigned)eb;
+                    const bool is_far = (tv & 0x8000u) != 0;
+                    const unsigned d = t_d[is_far ? far_sym : near_sym];
+                    or_bits(s_out, off, (d & 0xffffu) | (uint64_t)(is_far ? far_ev : near_ev) << (d >> 16));
+                    off += (d >> 16) + (unsigned)(is_far ? far_eb : near_eb);
+                } else {
+                    const unsigned e = t_ll[s_d[H + i]];
+                    or_bits(s_out, off, e & 0xffffu);
+                    off += e >> 16;
+                }
+            });
+            if (t == 0) {
+                // BFINAL, BTYPE = 10, HLIT, HDIST, HCLEN, the code-length code's lengths, the coded lengths; then the end of block
+                unsigned o = 0;
+                auto put = [&](unsigned v, unsigned nb) {
+                    or_bits(s_out, o, v);
+                    o += nb;
+                };
+                put((bfinal ? 1u : 0u) | 4u, 3);
+                put((unsigned)hlit - 257, 5);
+                put((unsigned)hdist - 1, 5);
+                put(hclen - 4, 4);
+                for (unsigned k = 0; k < hclen; ++k) put(l_cl[dfl_cl_order((int)k)], 3);
+                const unsigned nh = cnt[DC_NHSYM];
+                for (unsigned k = 0; k < nh; ++k) {
+                    const unsigned hs = hsym[k], e = t_cl[hs & 0xffu];
+                    put(e & 0xffffu, e >> 16);
+                    put(hs >> 8, (unsigned)dfl_cl_extra_bits(hs & 0xffu));
+                }
+                or_bits(s_out, dyn_end - (t_ll[256] >> 16), t_ll[256] & 0xffffu);
+                if (!bfinal) {
+                    atomicOr(&s_out[(dyn_sync + 2) >> 2], 0xffu << (((dyn_sync + 2) & 3) * 8));
+                    atomicOr(&s_out[(dyn_sync + 3) >> 2], 0xffu << (((dyn_sync + 3) & 3) * 8));
+                }
+            }
+            __syncthreads();
+            for (unsigned w = t; w < dyn_words; w += DFL_NT) slot[w] = s_out[w];
+            if (t == 0) blk_size[g] = dyn_bytes;
+            return;
+        }
+        __syncthreads();      // (the fixed form zeroes s_out next: every read of the arrays above is done)
+    }
     if (fixed) {
         for (unsigned w = t; w < out_words + 1; w += DFL_NT) s_out[w] = 0;
         __syncthreads();
@@ -263,7 +553,7 @@ __global__ __launch_bounds__(DFL_NT) void k_deflate_block(const unsigned char* _
             const int i = p0 + __builtin_ctz(m);
             const unsigned tv = s_tok[i];
             int nb;
-            const uint64_t bits = (tv & 0x7fffu) ? dfl_match(tv & 0x7fffu, (tv & 0x8000u) ? far_dist : 1, &nb) : dfl_literal(s_d[H + i], &nb);
+            const uint64_t bits = (tv & 0x7fffu) ? dfl_match(tv & 0x7fffu, (tv & 0x8000u) ? far_dist : near, &nb) : dfl_literal(s_d[H + i], &nb);
             or_bits(s_out, off, bits);
             off += nb;
         }
@@ -396,11 +686,15 @@ extern "C" size_t boa_deflate_bound(size_t n, size_t member_bytes) {
     return n + 5 * nblocks;      // every block as a stored block: 5 bytes of header each
 }
 
-extern "C" int boa_deflate_members(boa_ctx* c, const uint8_t* dev_src, size_t n, size_t member_bytes, int row_bytes, uint8_t* dev_out,
-                                   size_t out_capacity, size_t* host_offsets, uint32_t* host_crc32) {
+extern "C" int boa_deflate_members2(boa_ctx* c, const uint8_t* dev_src, size_t n, size_t member_bytes, int row_bytes, int near_bytes, int flags,
+                                    uint8_t* dev_out, size_t out_capacity, size_t* host_offsets, uint32_t* host_crc32) {
     BOA_REQUIRE(c && dev_out && host_offsets && host_crc32 && (dev_src || n == 0), "boa_deflate_members: NULL argument");
     BOA_REQUIRE(member_bytes >= 1 && member_bytes <= DFL_MAX_MEMBER, "boa_deflate_members: member_bytes %zu outside [1, 2^30]", member_bytes);
     BOA_REQUIRE(n <= DFL_MAX_N, "boa_deflate_members: %zu payload bytes (at most 2^40)", n);
+    BOA_REQUIRE(near_bytes >= 1 && near_bytes <= 16, "boa_deflate_members: near_bytes %d outside [1, 16]", near_bytes);
+    BOA_REQUIRE((flags & ~BOA_DEFLATE_DYNAMIC) == 0, "boa_deflate_members: unknown flags 0x%x", (unsigned)flags);
+    const bool dyn = (flags & BOA_DEFLATE_DYNAMIC) != 0;
+    BOA_REQUIRE(dyn || near_bytes == 1, "boa_deflate_members: near_bytes %d without BOA_DEFLATE_DYNAMIC (the fixed-code kernel has distance 1)", near_bytes);
     size_t nmem, bpm, nblocks;
     deflate_shape(n, member_bytes, &nmem, &bpm, &nblocks);
     BOA_REQUIRE(nblocks <= 0x7fffffffu && nmem <= 0x7fffffffu, "boa_deflate_members: %zu blocks in %zu members", nblocks, nmem);
@@ -423,7 +717,8 @@ extern "C" int boa_deflate_members(boa_ctx* c, const uint8_t* dev_src, size_t n,
     unsigned* d_mcrc = (unsigned*)(blk + slots_b + boff_b + moff_b + bsz_b + bcrc_b);
     unsigned* d_pw = (unsigned*)(blk + slots_b + boff_b + moff_b + bsz_b + bcrc_b + mcrc_b);
 
-    static bool once = (hipFuncSetAttribute((const void*)k_deflate_block, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), true);
+    static bool once = (hipFuncSetAttribute((const void*)k_deflate_block<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
+                        hipFuncSetAttribute((const void*)k_deflate_block<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), true);
     (void)once;
     std::vector<unsigned long long> offs(nmem + 1);
     hipError_t e = hipMemcpyAsync(d_pw, crc_pow().x, sizeof(DflCrcPow), hipMemcpyHostToDevice, c->stream);
@@ -433,8 +728,12 @@ extern "C" int boa_deflate_members(boa_ctx* c, const uint8_t* dev_src, size_t n,
     }
     c->prof_break = true;
     KernelTimer t(c, BOA_K_OTHER, 0, (double)n * 2 + (double)nblocks * 16);
-    hipLaunchKernelGGL(k_deflate_block, dim3((unsigned)nblocks), dim3(DFL_NT), lds, c->stream, dev_src, n, (unsigned)member_bytes,
-                       (unsigned)bpm, row, hist, d_pw, d_slots, d_bsz, d_bcrc);
+    if (dyn)
+        hipLaunchKernelGGL(k_deflate_block<true>, dim3((unsigned)nblocks), dim3(DFL_NT), lds, c->stream, dev_src, n, (unsigned)member_bytes,
+                           (unsigned)bpm, row, hist, near_bytes, d_pw, d_slots, d_bsz, d_bcrc);
+    else
+        hipLaunchKernelGGL(k_deflate_block<false>, dim3((unsigned)nblocks), dim3(DFL_NT), lds, c->stream, dev_src, n, (unsigned)member_bytes,
+                           (unsigned)bpm, row, hist, near_bytes, d_pw, d_slots, d_bsz, d_bcrc);
     hipLaunchKernelGGL(k_deflate_scan, dim3(1), dim3(DFL_NT), 0, c->stream, d_bsz, d_bcrc, (unsigned)nblocks, (unsigned)bpm,
                        (unsigned)nmem, n, (unsigned)member_bytes, d_pw, d_boff, d_moff, d_mcrc);
     hipLaunchKernelGGL(k_deflate_compact, dim3((unsigned)nblocks), dim3(256), 0, c->stream, d_slots, d_bsz, d_boff, dev_out);
@@ -447,4 +746,9 @@ extern "C" int boa_deflate_members(boa_ctx* c, const uint8_t* dev_src, size_t n,
     BOA_HIP_TRY(e);
     for (size_t m = 0; m <= nmem; ++m) host_offsets[m] = (size_t)offs[m];
     return BOA_OK;
+}
+
+extern "C" int boa_deflate_members(boa_ctx* c, const uint8_t* dev_src, size_t n, size_t member_bytes, int row_bytes, uint8_t* dev_out,
+                                   size_t out_capacity, size_t* host_offsets, uint32_t* host_crc32) {
+    return boa_deflate_members2(c, dev_src, n, member_bytes, row_bytes, 1, 0, dev_out, out_capacity, host_offsets, host_crc32);
 }

@@ -660,6 +660,20 @@ int boa_j2k_decode(boa_ctx* ctx, const uint8_t* dev_data, size_t data_bytes, int
 size_t boa_deflate_bound(size_t n, size_t member_bytes);
 int boa_deflate_members(boa_ctx* ctx, const uint8_t* dev_src, size_t n, size_t member_bytes, int row_bytes, uint8_t* dev_out,
                         size_t out_capacity, size_t* host_offsets, uint32_t* host_crc32);
+/* The same with two more choices; boa_deflate_members is this call with near_bytes = 1, flags = 0.
+ * near_bytes (1 .. 16): the short candidate distance, the item size of the voxels (a tie between the candidates goes to it).
+ * flags = BOA_DEFLATE_DYNAMIC: every block is also sized as a dynamic-Huffman block (BTYPE = 10) over the same tokens: the
+ * literal/length and distance symbols are counted, each alphabet gets the code lengths of least cost within 15 bits (7 bits for
+ * the code-length code of the header: package-merge, so the cost is the optimum also where the Huffman tree would be deeper), the
+ * lengths are run-length coded by zlib's greedy rule (zero runs of 11 .. 138 -> 18, of 3 .. 10 -> 17, a non-zero length once and
+ * its repeats in groups of 3 .. 6 -> 16, the rest literally; one sequence over both alphabets), HLIT / HDIST / HCLEN end at the last
+ * used symbol; a block without a match has HDIST = 1 with a zero length, one with a single distance symbol a 1-bit code.  The
+ * block is written in that form only where it is smaller than both the fixed and the stored form, so boa_deflate_bound holds.
+ * near_bytes outside 1 .. 16, near_bytes other than 1 without BOA_DEFLATE_DYNAMIC (the fixed-code kernel is the one it was, with
+ * distance 1) or an unknown flag bit: BOA_EINVAL before anything is launched. */
+#define BOA_DEFLATE_DYNAMIC 1
+int boa_deflate_members2(boa_ctx* ctx, const uint8_t* dev_src, size_t n, size_t member_bytes, int row_bytes, int near_bytes, int flags,
+                         uint8_t* dev_out, size_t out_capacity, size_t* host_offsets, uint32_t* host_crc32);
 
 #ifdef __cplusplus
 }
