@@ -11,6 +11,8 @@ LIB_PATH = os.environ.get("BOA_HIP_LIB") or os.path.join(_HERE, "libboa_hip.so")
 
 BOA_OK, BOA_EINVAL, BOA_EHIP, BOA_ENOMEM, BOA_EINF = 0, -1, -2, -3, -4
 BOA_DEFLATE_DYNAMIC = 1     # flags of boa_deflate_members2
+BOA_INF_INFO_WORDS, BOA_INF_MS_WORDS = 8, 8     # boa_inflate_streams: host_info (chunks, candidates, rejected, rounds, live), host_ms
+BOA_INF_STATUS = ("ok", "truncated", "invalid", "far", "overrun", "size", "crc", "repair", "trailing")
 K_CONV_MFMA, K_CONV_FIRST, K_CONVT, K_NORM_FINALIZE, K_HEAD_ACCUM, K_ARGMAX, K_OTHER, K_AGG, K_MORPH, K_RESAMPLE, K_COPY, K_COUNT = range(12)
 K_NAMES = ["conv_mfma", "conv_first", "convT_mfma", "norm_finalize", "head_accum", "finalize_argmax", "other", "aggregation",
            "morphology", "resample", "copy_remap"]
@@ -136,6 +138,9 @@ _PROTOS = {
     "boa_deflate_bound": (u64, [u64, u64]),
     "boa_deflate_members": (i32, [vp, vp, u64, u64, i32, vp, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]),
     "boa_deflate_members2": (i32, [vp, vp, u64, u64, i32, i32, i32, vp, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]),
+    "boa_inflate_default_chunk": (u64, []),
+    "boa_inflate_streams": (i32, [vp, vp, u64, i32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_uint32), u64, vp, u64, ip,
+                                  C.POINTER(u64), C.POINTER(C.c_float)]),
 }
 
 EXPORTS = sorted(_PROTOS)

@@ -101,7 +101,7 @@ def compute_all_models(
     if totalsegmentator_params.get("nr_thr_saving"):      # the reference's saving workers = deflate threads of nifti.save here
         nifti.SAVE_THREADS = max(1, int(totalsegmentator_params["nr_thr_saving"]))
     ctx = get_context(totalsegmentator_params.get("device"))
-    data, affine, hdr = nifti.load(ct_path)
+    data, affine, hdr = nifti.load(ct_path, ctx=nifti.load_context(ctx))
     ct = _ct_array(data, hdr)
     fast = bool(totalsegmentator_params.get("fast", False))
     for name in measurement_models:
@@ -166,7 +166,7 @@ def _run_bca_model(ctx, name, ct, affine, hdr, folder, fast_bca, bca_params, spl
         f = folder / f"{task}.nii.gz"
         if not recompute and f.is_file():
             logger.info("Loading already computed %s...", task)
-            done[task] = np.ascontiguousarray(nifti.load(f)[0], dtype=np.uint8)
+            done[task] = np.ascontiguousarray(nifti.load(f, ctx=nifti.load_context(ctx))[0], dtype=np.uint8)
     if name != "bca" and name in done:
         return
     models = {t: (model_store.load_task_models(t, fast_bca)[0][1:3] if t not in done else None) for t in wanted}
@@ -176,7 +176,7 @@ def _run_bca_model(ctx, name, ct, affine, hdr, folder, fast_bca, bca_params, spl
             nifti.save_volume(folder / f"{name}.nii.gz", pipe.inference(name, ct, affine, force_split=split), affine, ctx=ctx, like=hdr)
             return
         total_file = folder / "total.nii.gz"
-        out = pipe.run(ct, affine, total_seg=nifti.load(total_file)[0] if total_file.is_file() else None, force_split=split,
+        out = pipe.run(ct, affine, total_seg=nifti.load(total_file, ctx=nifti.load_context(ctx))[0] if total_file.is_file() else None, force_split=split,
                        median_filtering=bool(bca_params.get("median_filtering", False)),
                        examined_body_region=bca_params.get("examined_body_region"),
                        done_parts=done.get("body_parts"), done_regions=done.get("body_regions"))

@@ -38,7 +38,7 @@ def compute_measurements(ct_path: pathlib.Path, segmentation_folder: pathlib.Pat
     pool = ThreadPoolExecutor(max_workers=max(1, min(4, len(ordered))))
     pending = {m: pool.submit(nifti.load, path_of(m)) for m in ordered if path_of(m).exists()}
     pool.shutdown(wait=False)
-    data, _, hdr = nifti.load(ct_path)
+    data, _, hdr = nifti.load(ct_path, ctx=nifti.load_context(ctx))
     # SimpleITK view (z,y,x) of the file, made on the device (a 512^3 host transpose costs ~0.5 s): int16 HU when the values
     # are int16-exact, otherwise get_fdata()'s float64 for the float statistics path (M.ct_for_stats decides)
     if data.dtype == np.int16 and not nifti.is_scaled(hdr) and not M.force_float_stats():

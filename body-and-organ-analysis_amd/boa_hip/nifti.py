@@ -107,16 +107,118 @@ def _member_table(raw) -> Optional[list]:
 READ_THREADS = int(os.environ.get("BOA_READ_THREADS", "0")) or min(8, os.cpu_count() or 1)
 
 
-def read_bytes(path, threads: Optional[int] = None) -> bytes:
+LOAD_DEVICE_ENV = "BOA_LOAD_DEVICE"
+
+
+def load_context(ctx):
+    """`ctx` for the readers of the file-level callers (compute_all_models, compute_measurements, the BCA file readers): the
+    context with $BOA_LOAD_DEVICE = 1, which sends their .nii.gz inputs through the device inflate, else None (default off:
+    DESIGN 4.10)."""
+    return ctx if os.environ.get(LOAD_DEVICE_ENV) == "1" else None
+
+
+def gzip_header_end(raw, off: int = 0) -> Optional[int]:
+    """The offset of the deflate body of the gzip member that starts at `off` (RFC 1952 section 2.3: the fixed ten bytes, then
+    FEXTRA, FNAME, FCOMMENT and FHCRC as FLG says; FTEXT changes nothing), or None where that is no complete deflate member header
+    (bad magic, a method other than 8, a reserved flag bit, a field that runs past the end, an FHCRC that does not match)."""
+    import zlib
+    mv = memoryview(raw)
+    n = len(mv)
+    if n - off < 10 or mv[off] != 0x1F or mv[off + 1] != 0x8B or mv[off + 2] != 8:
+        return None
+    flg = mv[off + 3]
+    if flg & 0xE0:
+        return None
+    at = off + 10
+    if flg & 4:
+        if at + 2 > n:
+            return None
+        at += 2 + (mv[at] | (mv[at + 1] << 8))
+        if at > n:
+            return None
+    for bit in (8, 16):
+        if flg & bit:
+            while at < n and mv[at] != 0:
+                at += 1
+            if at >= n:
+                return None
+            at += 1
+    if flg & 2:
+        if at + 2 > n or (zlib.crc32(mv[off:at]) & 0xFFFF) != (mv[at] | (mv[at + 1] << 8)):
+            return None
+        at += 2
+    return at
+
+
+def _gzip_streams(raw) -> Optional[list]:
+    """[(deflate start, deflate end, payload size, CRC-32)] for the device inflate: the members of this module's index, or the one
+    member of a foreign file (whether it is the only one shows when its final block ends: a second member is trailing data to the
+    decoder).  ISIZE is the size modulo 2^32; it is taken as the size, and a stream that counts differently goes to the host."""
+    mv = memoryview(raw)
+    tab = _member_table(raw)
+    if tab:
+        return [(lo, hi, size, struct.unpack("<I", mv[hi:hi + 4])[0]) for lo, hi, size in tab]
+    body = gzip_header_end(raw)
+    if body is None or len(mv) - body < 8 + 1:
+        return None
+    crc, isize = struct.unpack("<II", mv[len(mv) - 8:])
+    return [(body, len(mv) - 8, isize, crc)]
+
+
+def device_inflate(ctx, raw, *, chunk_bytes: Optional[int] = None):
+    """The payload of the gzip file `raw` (bytes-like) inflated on the device with `boa_inflate_streams` (csrc/inflate.hip):
+    -> (uint8 array, info).  Only the file's bytes go up and the payload comes down.  info: "chunks", "candidates" (block starts
+    the find pass accepted), "rejected" (those the chain check dropped), "rounds" (repair rounds), "live", "streams", "status"
+    (one name per stream, "ok" = decoded and equal to the trailer's CRC-32 and size), "ms" (device-event times of find, count,
+    store, windows, resolve) and "host": True where the device did not decode the file -- a container this path does not take
+    (status []), or a status other than ok -- in which case the array is None and the caller inflates on the host.
+    `chunk_bytes`: compressed bytes per chunk (default boa_inflate_default_chunk(), 64 KiB)."""
+    import ctypes as C
+    from . import _lib
+    info = {"chunks": 0, "candidates": 0, "rejected": 0, "rounds": 0, "live": 0, "streams": 0, "status": [], "ms": {}, "host": True}
+    streams = _gzip_streams(raw)
+    if not streams:
+        return None, info
+    n = len(streams)
+    total = sum(s[2] for s in streams)
+    u64 = C.c_uint64 * n
+    offs, lens, sizes = u64(*[s[0] for s in streams]), u64(*[s[1] - s[0] for s in streams]), u64(*[s[2] for s in streams])
+    crcs = (C.c_uint32 * n)(*[s[3] for s in streams])
+    status, words, ms = (C.c_int * n)(), (C.c_uint64 * _lib.BOA_INF_INFO_WORDS)(), (C.c_float * _lib.BOA_INF_MS_WORDS)()
+    chunk_bytes = int(chunk_bytes) if chunk_bytes else int(ctx.lib.boa_inflate_default_chunk())
+    src = ctx.from_numpy(np.frombuffer(raw, dtype=np.uint8))
+    out = ctx.alloc(max(total, 16))
+    try:
+        _lib.check(ctx.lib.boa_inflate_streams(ctx.h, src.vp, len(raw), n, offs, lens, sizes, crcs, chunk_bytes, out.vp, total, status,
+                                               words, ms), "boa_inflate_streams")
+        info.update(chunks=int(words[0]), candidates=int(words[1]), rejected=int(words[2]), rounds=int(words[3]), live=int(words[4]),
+                    streams=n, status=[_lib.BOA_INF_STATUS[s] for s in status],
+                    ms=dict(zip(("find", "count", "store", "windows", "resolve"), (float(v) for v in ms))))
+        if any(status):
+            return None, info
+        info["host"] = False
+        return (out.download((total,), np.uint8) if total else np.zeros(0, np.uint8)), info
+    finally:
+        src.free()
+        out.free()
+
+
+def read_bytes(path, threads: Optional[int] = None, ctx=None) -> bytes:
     """The decompressed content of `path`.  A .gz file written by this module (indexed members) is inflated on `threads` cores
     (zlib releases the GIL): a 512^3 label volume in 0.15 s instead of 0.6 s; any other gzip stream takes the ordinary
-    sequential path (a deflate stream has no entry points -- files of other writers are parallelised across FILES, load_many)."""
+    sequential path (a deflate stream has no entry points -- files of other writers are parallelised across FILES, load_many).
+    With `ctx` (a device Context) an indexed or a single-member .gz file is inflated on the device (device_inflate); whatever the
+    device does not decode -- another container, a damaged stream -- takes the host path above and raises what it raises."""
     if not str(path).endswith(".gz"):
         with open(path, "rb") as f:
             return f.read()
     threads = READ_THREADS if threads is None else int(threads)
     with open(path, "rb") as f:
         raw = f.read()
+    if ctx is not None:
+        data, info = device_inflate(ctx, raw)
+        if not info["host"]:
+            return data
     tab = _member_table(raw) if threads > 1 else None
     if not tab or len(tab) == 1:
         return gzip.decompress(raw)
@@ -151,9 +253,10 @@ def load_many(paths, threads: Optional[int] = None) -> list:
         return list(ex.map(lambda p: load(p, threads=inner), paths))
 
 
-def load(path, threads: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, NiftiHeader]:
-    """-> (raw data array in file axis order and dtype, affine (4,4) float64, header).  `get_fdata` = fdata(...)."""
-    blob = read_bytes(path, threads)
+def load(path, threads: Optional[int] = None, ctx=None) -> Tuple[np.ndarray, np.ndarray, NiftiHeader]:
+    """-> (raw data array in file axis order and dtype, affine (4,4) float64, header).  `get_fdata` = fdata(...).  `ctx`: see
+    read_bytes."""
+    blob = read_bytes(path, threads, ctx)
     if len(blob) < 352:
         raise ValueError(f"{path}: not a NIfTI-1 file")
     endian = "<"

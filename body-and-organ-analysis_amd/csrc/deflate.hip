@@ -11,6 +11,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "crc32_dev.h"
 #include "deflate_codes.h"
 
 namespace {
@@ -223,11 +224,7 @@ __global__ __launch_bounds__(DFL_NT) void k_deflate_block(const unsigned char* _
         for (int i = t; i < n16; i += DFL_NT) ((uint4*)ldst)[i] = ((const uint4*)gsrc)[i];
         for (int i = n16 * 16 + t; i < total; i += DFL_NT) ldst[i] = gsrc[i];
     }
-    if (t < 256) {
-        unsigned c = t;
-        for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1) ? DFL_CRC_POLY : 0u);
-        s_tab[t] = c;
-    }
+    if (t < 256) s_tab[t] = crc32_table_entry((unsigned)t);
     for (int i = t; i < DFL_BLK / 32 + 4; i += DFL_NT) s_mark[i] = (i == 0 && blen > 0) ? 1u : 0u;
     __syncthreads();
 
@@ -235,9 +232,8 @@ __global__ __launch_bounds__(DFL_NT) void k_deflate_block(const unsigned char* _
     // a tree inside each wave, then across the 16 waves ----
     {
         const int hi = blen - DFL_PIECE * (DFL_NT - 1 - t);
-        unsigned c = 0xffffffffu;
-        for (int i = hi - DFL_PIECE > 0 ? hi - DFL_PIECE : 0; i < hi; ++i) c = s_tab[(c ^ s_d[H + i]) & 0xffu] ^ (c >> 8);
-        c ^= 0xffffffffu;
+        const unsigned c0 = crc32_update(s_tab, 0xffffffffu, s_d + H, hi - DFL_PIECE > 0 ? hi - DFL_PIECE : 0, hi);
+        unsigned c = c0 ^ 0xffffffffu;
 #pragma unroll
         for (int k = 0; k < 6; ++k) {        // after step k the lanes that are multiples of 2^(k+1) hold 2^(k+1) pieces
             const unsigned right = __shfl_down(c, 1 << k, 64);
@@ -651,15 +647,6 @@ __global__ __launch_bounds__(256) void k_deflate_compact(const unsigned* __restr
     }
     const unsigned tail = head + 4 * nw;
     if (tail + t < sz) d[tail + t] = (unsigned char)slot_byte(w, tail + t);
-}
-
-const DflCrcPow& crc_pow() {
-    static const DflCrcPow t = [] {
-        DflCrcPow p;
-        dfl_crc_pow_init(&p);
-        return p;
-    }();
-    return t;
 }
 
 // (members, blocks per full member, blocks in all) of n payload bytes; the empty payload is one member of one empty block

@@ -675,6 +675,51 @@ int boa_deflate_members(boa_ctx* ctx, const uint8_t* dev_src, size_t n, size_t m
 int boa_deflate_members2(boa_ctx* ctx, const uint8_t* dev_src, size_t n, size_t member_bytes, int row_bytes, int near_bytes, int flags,
                          uint8_t* dev_out, size_t out_capacity, size_t* host_offsets, uint32_t* host_crc32);
 
+/* ------------------------------------------------------------------ inflate of .nii.gz inputs (inflate.hip) --- */
+/* Raw deflate streams (RFC 1951) decoded on the device, each checked against its gzip trailer (RFC 1952).  A stream is one member's
+ * body: stream_off[m] / stream_len[m] = its place in dev_src (src_bytes), an empty history, stream_size[m] = its payload bytes (the
+ * trailer's ISIZE, taken as the whole size) and stream_crc32[m] = the trailer's CRC-32; all HOST arrays of n_streams entries.  The
+ * payloads are written back to back into dev_out (out_capacity >= the sum of stream_size).  A file with a member index is many
+ * streams, a foreign single-member file is one.
+ * Every stream is cut into chunks of chunk_bytes (64 .. 2^30; boa_inflate_default_chunk() = 64 KiB) of compressed input.  Chunk 0
+ * starts at bit 0; every other chunk looks for the first bit offset of its range that passes the block-start test (BFINAL = 0,
+ * BTYPE = 2, HLIT / HDIST <= 29, a complete code-length code, the lengths decode as one sequence without a leading repeat or an
+ * overrun, symbol 256 has a length, both codes complete or incomplete as zlib's inflate_table accepts), and drops out without one.
+ * Each live chunk decodes up to the first block end at or beyond the next live chunk's start, counting bytes; the chain is accepted
+ * where every end is the next start.  A chunk behind a false candidate is restarted at its predecessor's end, a bounded number of
+ * rounds.  The chunks are then decoded into 16-bit symbols (a literal, or a reference into the unknown 32 KiB in front of the
+ * chunk), the windows are resolved chunk after chunk, and the symbols become bytes with a CRC-32 per chunk, combined per stream.
+ * host_status[m]: BOA_INF_OK, or why the stream was not decoded; with any status other than OK the content of dev_out is undefined
+ * and the caller inflates on the host.  host_info[BOA_INF_INFO_WORDS]: BOA_INF_I_*.  host_ms (may be NULL): BOA_INF_MS_WORDS floats,
+ * the device-event times of the passes in ms.  Every offset is validated first (BOA_EINVAL), malformed streams are reported per
+ * stream, never by a fault: lengths 286 / 287 and distances 30 / 31, a stored block whose LEN is not ~NLEN, a read past the
+ * stream's end (zero bits, BOA_INF_TRUNCATED), a distance before the stream's first byte (BOA_INF_FAR).  Synchronous. */
+#define BOA_INF_OK 0
+#define BOA_INF_TRUNCATED 1
+#define BOA_INF_INVALID 2
+#define BOA_INF_FAR 3
+#define BOA_INF_OVERRUN 4
+#define BOA_INF_SIZE 5
+#define BOA_INF_CRC 6
+#define BOA_INF_REPAIR 7
+#define BOA_INF_TRAILING 8
+#define BOA_INF_INFO_WORDS 8
+#define BOA_INF_I_CHUNKS 0       /* chunks of all streams */
+#define BOA_INF_I_CANDIDATES 1   /* block starts the find pass accepted */
+#define BOA_INF_I_REJECTED 2     /* candidates the chain check dropped */
+#define BOA_INF_I_ROUNDS 3       /* repair rounds */
+#define BOA_INF_I_LIVE 4         /* chunks that decoded in the end */
+#define BOA_INF_MS_WORDS 8
+#define BOA_INF_MS_FIND 0
+#define BOA_INF_MS_COUNT 1
+#define BOA_INF_MS_STORE 2
+#define BOA_INF_MS_WINDOWS 3
+#define BOA_INF_MS_RESOLVE 4
+size_t boa_inflate_default_chunk(void);
+int boa_inflate_streams(boa_ctx* ctx, const uint8_t* dev_src, size_t src_bytes, int n_streams, const uint64_t* stream_off,
+                        const uint64_t* stream_len, const uint64_t* stream_size, const uint32_t* stream_crc32, size_t chunk_bytes,
+                        uint8_t* dev_out, size_t out_capacity, int* host_status, uint64_t* host_info, float* host_ms);
+
 #ifdef __cplusplus
 }
 #endif
