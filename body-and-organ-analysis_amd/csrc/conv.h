@@ -1,4 +1,4 @@
-// Conv-stack kernels of the PlainConvUNet engine (gfx950): launch wrappers shared by net.hip and the test seams.
+// Conv-stack kernels of the PlainConvUNet engine (gfx950): launch wrappers shared by the network driver (net.hip, net_stash.hip) and the test seams (net_debug.hip).
 #pragma once
 #include "common.h"
 
@@ -150,11 +150,44 @@ __device__ __forceinline__ uint4 norm_act8(uint4 raw, const float* sc, const flo
 int launch_conv_ws(boa_ctx* ctx, const ConvArgs& a, const ConvTile& t, double flops, double bytes, bool x3 = false);
 // fused gather head (head_gather.hip): all covering tiles of a voxel -> label, from the stash of last decoder activations
 int launch_pack_head_ss(boa_ctx* ctx, const float* ss, unsigned* out, int n_tiles);
-int launch_gather_head(boa_ctx* ctx, const __half* act, const unsigned* ssp, const float* w, const float* bias, const uint16_t* gauss,
-                       int C, const int P[3], const int PV[3], const int ntile[3], const int* dev_tab, uint16_t* fold, int fold_mode,
-                       int n_folds, const uint8_t* host_lut, int merge, uint8_t* labels, const int* crop_off, const int* crop_dims,
-                       int* inf_flag, float slope, int tiles_total, bool x3 = false, const int* x_range = nullptr, uint16_t* raw_n = nullptr,
-                       int raw_init = 0);
+// what a pass does with the running sums of a voxel (the values are GatherArgs::fold_mode)
+enum class FoldMode : int {
+    Single = 0,   // the only fold: normalise, argmax, write labels
+    First = 1,    // first of several folds: store the normalised logits in `fold`
+    Middle = 2,   // add them to `fold`
+    Last = 3,     // add, divide by n_folds, argmax, write labels
+    Raw = 4,      // tile sharding: write the partial sums themselves into the accumulator planes `fold` [C][V] and `raw_n` [V]
+};
+struct GatherHead {
+    // the stash: activations of all tiles, the head's (scale, shift) table (packed fp16; fp32 when x3), the walk table (device)
+    const __half* act = nullptr;
+    const unsigned* ssp = nullptr;
+    const int* dev_tab = nullptr;
+    int ntile[3] = {0, 0, 0};
+    int tiles_total = 0;
+    bool x3 = false;
+    // the head and the geometry: P = extent of a stashed tile, PV = the padded volume
+    const float* w = nullptr;
+    const float* bias = nullptr;
+    const uint16_t* gauss = nullptr;   // nullptr: weight 1
+    int C = 0, P[3] = {0, 0, 0}, PV[3] = {0, 0, 0};
+    float slope = 0.f;
+    // what to do with the sums
+    FoldMode fold_mode = FoldMode::Single;
+    int n_folds = 1;
+    uint16_t* fold = nullptr;
+    const uint8_t* host_lut = nullptr;   // nullptr: identity
+    int merge = 0;
+    uint8_t* labels = nullptr;
+    const int* crop_off = nullptr;       // nullptr: labels cover the padded volume
+    const int* crop_dims = nullptr;
+    int* inf_flag = nullptr;
+    // FoldMode::Raw: the axis-0 planes [x_lo, x_hi) (x_hi < 0: up to PV[0]); raw_init: continue from the planes' contents
+    int x_lo = 0, x_hi = -1;
+    uint16_t* raw_n = nullptr;
+    int raw_init = 0;
+};
+int launch_gather_head(boa_ctx* ctx, const GatherHead& g);
 // k_conv_ns (conv_ns.hip): consumer waves split the cout axis, weights straight from L2 (stride-2 / deep 3x3x3 layers)
 bool conv_ns_applicable(const ConvGeom& g);
 void conv_ns_tile(const ConvGeom& g, ConvTile* t);

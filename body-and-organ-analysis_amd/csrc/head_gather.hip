@@ -611,32 +611,31 @@ int launch_pack_head_ss(boa_ctx* ctx, const float* ss, unsigned* out, int n_tile
     return BOA_OK;
 }
 
-int launch_gather_head(boa_ctx* ctx, const __half* act, const unsigned* ssp, const float* w, const float* bias, const uint16_t* gauss,
-                       int C, const int P[3], const int PV[3], const int ntile[3], const int* dev_tab, uint16_t* fold, int fold_mode,
-                       int n_folds, const uint8_t* host_lut, int merge, uint8_t* labels, const int* crop_off, const int* crop_dims,
-                       int* inf_flag, float slope, int tiles_total, bool x3, const int* x_range, uint16_t* raw_n, int raw_init) {
+int launch_gather_head(boa_ctx* ctx, const GatherHead& g) {
+    const int C = g.C, *P = g.P, *PV = g.PV, *ntile = g.ntile, fold_mode = (int)g.fold_mode, tiles_total = g.tiles_total, raw_init = g.raw_init;
+    const bool x3 = g.x3;
     BOA_REQUIRE(C >= 1 && C <= 32 && ntile[0] < 256 && ntile[1] < 256 && ntile[2] < 256, "gather head: C=%d / %d+%d+%d tiles per axis unsupported", C,
                 ntile[0], ntile[1], ntile[2]);
     GatherArgs a;
-    a.act = act; a.ssp = ssp; a.w = w; a.bias = bias; a.gauss = gauss; a.C = C;
+    a.act = g.act; a.ssp = g.ssp; a.w = g.w; a.bias = g.bias; a.gauss = g.gauss; a.C = C;
     a.P0 = P[0]; a.P1 = P[1]; a.P2 = P[2]; a.V0 = PV[0]; a.V1 = PV[1]; a.V2 = PV[2];
-    a.n0 = ntile[0]; a.n1 = ntile[1]; a.n2 = ntile[2]; a.tab = dev_tab;
-    a.fold = fold; a.fold_mode = fold_mode; a.n_folds = n_folds; a.labels = labels; a.merge = merge;
-    a.crop = crop_off != nullptr;
+    a.n0 = ntile[0]; a.n1 = ntile[1]; a.n2 = ntile[2]; a.tab = g.dev_tab;
+    a.fold = g.fold; a.fold_mode = fold_mode; a.n_folds = g.n_folds; a.labels = g.labels; a.merge = g.merge;
+    a.crop = g.crop_off != nullptr;
     a.o0 = a.o1 = a.o2 = 0;
     a.c0 = PV[0]; a.c1 = PV[1]; a.c2 = PV[2];
-    if (crop_off) {
-        a.o0 = crop_off[0]; a.o1 = crop_off[1]; a.o2 = crop_off[2];
-        a.c0 = crop_dims[0]; a.c1 = crop_dims[1]; a.c2 = crop_dims[2];
+    if (g.crop_off) {
+        a.o0 = g.crop_off[0]; a.o1 = g.crop_off[1]; a.o2 = g.crop_off[2];
+        a.c0 = g.crop_dims[0]; a.c1 = g.crop_dims[1]; a.c2 = g.crop_dims[2];
     }
-    a.inf_flag = inf_flag; a.slope = slope;
-    a.x_lo = x_range ? x_range[0] : 0;
-    a.x_hi = x_range ? x_range[1] : PV[0];
-    a.raw_n = raw_n; a.raw_init = raw_init;
-    BOA_REQUIRE(a.x_lo >= 0 && a.x_lo <= a.x_hi && a.x_hi <= PV[0] && (fold_mode != 4 || (fold && raw_n)), "gather head: plane range / raw buffers");
+    a.inf_flag = g.inf_flag; a.slope = g.slope;
+    a.x_lo = g.x_lo;
+    a.x_hi = g.x_hi < 0 ? PV[0] : g.x_hi;
+    a.raw_n = g.raw_n; a.raw_init = raw_init;
+    BOA_REQUIRE(a.x_lo >= 0 && a.x_lo <= a.x_hi && a.x_hi <= PV[0] && (fold_mode != 4 || (g.fold && g.raw_n)), "gather head: plane range / raw buffers");
     a.wscale = X3_HEAD_WSCALE;
     a.winv = 1.0f / a.wscale;
-    for (int i = 0; i < 256; ++i) a.lut[i] = host_lut ? host_lut[i] : (unsigned char)i;
+    for (int i = 0; i < 256; ++i) a.lut[i] = g.host_lut ? g.host_lut[i] : (unsigned char)i;
     const long long n_mt = (long long)PV[0] * PV[1] * ((PV[2] + 31) / 32);
     BOA_REQUIRE(n_mt < (1ll << 31), "gather head: volume too large for 32-bit run indices");
     const long long n_mt_run = (long long)(a.x_hi - a.x_lo) * PV[1] * ((PV[2] + 31) / 32);
@@ -667,9 +666,9 @@ int launch_gather_head(boa_ctx* ctx, const __half* act, const unsigned* ssp, con
             hipLaunchKernelGGL((k_gather_head_pf<G, S, M>), dim3(grid), dim3(256), lds, ctx->stream, a); \
     } while (0)
     const bool multi = fold_mode != 0;
-    if (gauss && a.ss_in_lds) {
+    if (g.gauss && a.ss_in_lds) {
         if (multi) GH_LAUNCH(true, true, true); else GH_LAUNCH(true, true, false);
-    } else if (gauss) {
+    } else if (g.gauss) {
         if (multi) GH_LAUNCH(true, false, true); else GH_LAUNCH(true, false, false);
     } else if (a.ss_in_lds) {
         if (multi) GH_LAUNCH(false, true, true); else GH_LAUNCH(false, true, false);

@@ -6,59 +6,13 @@
 
 #include <vector>
 
-#include "conv.h"
+#include "net.h"
 
 namespace {
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
-
-// The network's arithmetic; the values are boa_net_create's `precision`.  F16: fp16 storage + f16 MFMA (production); F32Ref: the
-// fp32 reference mode (net_f32.hip); Split: split precision (fp32 storage, hi / lo fp16 operands on the matrix cores: k_conv_ws<X3>,
-// net_x3.hip).  Only the functions that answer the mode's questions look at it: in_granule, act_layout, conv_weight_piece /
-// convt_weight_piece, head_kernel and the forward's launch steps (net_forward_stack, conv_step, convt_step and their kernel reports),
-// besides boa_net_create's choice of the first conv's input buffer.
-enum class NetMode : int { F16 = 0, F32Ref = 1, Split = 2 };
 
 // input channels per staged MFMA chunk of a conv and of a transposed conv: 16 fp16 channels, 8 split-precision channels; the
 // fp32_ref kernels take any count (0)
 int in_granule(NetMode m) { return m == NetMode::F16 ? 16 : m == NetMode::Split ? 8 : 0; }
-
-// Record format of a layer's activation buffer of C channels.  fp16 chunk planes [N][C/16][voxel][16] and split-precision octet
-// planes [N][C/8][voxel][8] (fp32) both hold 32-byte records in planes that span all voxels of a tile; fp32_ref holds channels-last
-// records [N][voxel][C] (fp32) of 4 C bytes in one plane.
-struct ActLayout {
-    int C;
-    int esz;       // bytes per channel value
-    bool planar;   // 32-byte records in C * esz / 32 planes, else channels-last
-    size_t rec() const { return planar ? 32 : (size_t)C * esz; }
-    size_t bytes(size_t vox) const { return vox * C * esz; }              // one tile of `vox` voxels
-    size_t tile(size_t i, size_t vox) const { return i * bytes(vox); }    // byte offset of tile i
-    // byte offset, inside every record plane, that skips a tile's first n axis-0 planes of `plane` voxels
-    size_t skip(int n, size_t plane) const { return (size_t)n * plane * rec(); }
-    // the plane stride (voxels) the scatter-form heads take; 0 = channels-last
-    size_t plane_stride(size_t vox) const { return planar ? vox : 0; }
-    // copies the first dp axis-0 planes of a tile (vox voxels, `plane` per axis-0 plane) to dst, in the same format with dp * plane
-    // voxels per record plane
-    hipError_t copy_head(unsigned char* dst, const void* tile, int dp, size_t plane, size_t vox, hipStream_t s) const {
-        const size_t n = (size_t)dp * plane * rec();
-        const int planes = planar ? C * esz / 32 : 1;
-        hipError_t e = hipSuccess;
-        for (int k = 0; k < planes && e == hipSuccess; ++k)
-            e = hipMemcpyAsync(dst + k * n, (const unsigned char*)tile + k * vox * rec(), n, hipMemcpyDeviceToDevice, s);
-        return e;
-    }
-    // fp32 NCDHW of one tile through the (scale, shift) table ss (nullptr: raw) and LeakyReLU
-    int to_nchw(boa_ctx* c, const void* tile, const float* ss, float slope, size_t vox, float* out) const {
-        if (!planar) return launch_ndhwc32_to_nchw_f32(c, (const float*)tile, ss, slope, C, vox, out);
-        if (esz == 4) return launch_octet_to_nchw_f32(c, (const float*)tile, ss, slope, C, vox, out);
-        return launch_ndhwc_to_nchw_f32(c, (const __half*)tile, ss, slope, 1, C, vox, out);
-    }
-};
-
-ActLayout act_layout(NetMode m, int C) { return {C, m == NetMode::F16 ? 2 : 4, m != NetMode::F32Ref}; }
 
 // The pieces of a weight set in blob order, each in the device form its kernel reads.
 enum class Piece {
@@ -82,86 +36,7 @@ Piece conv_weight_piece(NetMode m, bool first) {
 
 Piece convt_weight_piece(NetMode m) { return m == NetMode::F32Ref ? Piece::UpW32 : m == NetMode::Split ? Piece::UpWX3 : Piece::UpW16; }
 
-struct ConvLayer {
-    ConvGeom g{};
-    ConvTile t{};
-    int Cin0 = 0, Cin1 = 0;  // channels of the two concatenated sources (Cin1 = 0: single source)
-    bool first = false;      // stage-0 conv-0: fp32 VALU kernel reading the volume
-    __half* wpk = nullptr;   // MFMA layers
-    float* wfirst = nullptr; // first layer [Cin][taps][Cout]
-    float* w32 = nullptr;    // fp32 mode: [taps][Cin][Cout]
-    float wscale = 1.f;      // split-precision mode: power-of-two scale of the packed weights (per weight set)
-    float *bias = nullptr, *gamma = nullptr, *beta = nullptr;
-    void* act = nullptr;     // raw conv output in the mode's ActLayout
-    float* partials = nullptr;
-    float* ss = nullptr;
-    unsigned* ss16 = nullptr;
-    int nblk = 0;
-    size_t w_elems = 0;  // fp32 elements of W in the blob
-};
-
-struct UpLayer {
-    int Cin = 0, Cout = 0;
-    int s[3] = {1, 1, 1};
-    int din[3] = {0, 0, 0};
-    __half* wpk = nullptr;
-    float* w32 = nullptr;    // fp32 mode: [taps][Cin][Cout]
-    float* bias = nullptr;
-    void* act = nullptr;     // output in the mode's ActLayout
-    float wscale = 1.f;      // split-precision mode
-    float fold = 1.f;        // split-precision mode: power of two folded into the stored output (act = fold * convT output)
-};
-
 }  // namespace
-
-// The tile shapes of a network are chosen for a REFERENCE tile batch, not for the batch of a call or the net's max_batch: the shape
-// decides how the InstanceNorm partial sums are grouped, and results must not depend on how many tiles share a launch.
-// 16 = the product's default tile batch (with 8, the value of rounds 1-2, the 8^3 layers got half-size tiles -- 2 x 10 workgroups
-// per sample -- which at the batches actually run (16, 25) only doubled the weight streaming: 116 -> 82, 200 -> 134, 111 -> 73 us
-// per 25 tiles for the three 8^3 convs).
-constexpr int TILE_REF_BATCH = 16;
-
-struct boa_net {
-    boa_ctx* ctx = nullptr;
-    boa_net_desc d{};
-    int maxN = 1;
-    NetMode mode = NetMode::F16;
-    int mirror_mask = 0;       // test-time mirroring axes (bit a = array axis a), predict_from_raw_data.py:541-557
-    float* mirror_tmp = nullptr;  // [maxN][C][P] fp32 logits of one mirror variant
-    float* mirror_sum = nullptr;  // [maxN][C][P] running sum / mean
-    float* tiles32 = nullptr;  // fp32 mode: gathered input tiles [N][P][Cin]
-    std::vector<std::vector<ConvLayer>> enc;  // [stage][conv]
-    std::vector<UpLayer> up;                  // decoder order (deepest first)
-    std::vector<std::vector<ConvLayer>> dec;  // [d][conv]
-    float *head_w = nullptr, *head_b = nullptr;
-    int* dev_origins = nullptr;
-    float* first_padded = nullptr;  // zero-padded fp32 gather buffer of the first conv
-    std::vector<void*> allocs;
-    // Activation buffers (one per layer, ~1 GB per tile at 128^3: 25 GB at tile batch 25) live in ONE arena per context that all
-    // of its networks share: the networks of a context run one after the other on its stream and every forward overwrites a
-    // layer's buffer before reading it, so seven resident networks need the largest network's activations once, not seven times
-    // (175 GB -> 25 GB at the bench's batch; what persists across forwards -- statistics partials, (scale, shift) tables, weight
-    // arenas, the gather head's stash -- stays outside).  A layer records its offset; pointers are (re)bound whenever the arena
-    // has been re-allocated for a larger network (boa_ctx::act_gen).
-    struct ActSlot {
-        void** where;
-        size_t offset;
-    };
-    std::vector<ActSlot> act_slots;
-    size_t act_need = 0;
-    unsigned long long act_gen_seen = 0;
-    int dims[BOA_MAX_STAGES][3];
-    // packed weight sets (one device arena each), cached per host blob: switching folds is a pointer swap, not a re-pack
-    struct WeightSet {
-        const float* key;
-        size_t n;
-        unsigned long long sample_hash;  // FNV-1a over ~4096 evenly spaced floats: guards against a recycled host address
-        unsigned char* arena;
-        std::vector<float> scales;       // split-precision mode: weight scale of every conv / transposed conv (+ the output fold of a
-                                         // transposed conv), blob order
-    };
-    std::vector<WeightSet> wsets;
-};
 
 static int net_alloc(boa_net* net, size_t bytes, void** out) {
     BOA_TRY(boa_malloc_raw(net->ctx, bytes, out));   // (long-lived: not through the caching allocator; freed with hipFree)
@@ -178,7 +53,7 @@ static int net_alloc_act(boa_net* net, size_t bytes, void** out) {
 }
 
 // make the arena large enough for this network (re-allocating it if another, smaller network sized it) and point the layers at it
-static int net_bind_arena(boa_net* net) {
+int net_bind_arena(boa_net* net) {
     boa_ctx* c = net->ctx;
     if (net->act_slots.empty()) return BOA_OK;
     if (c->act_bytes < net->act_need) {
@@ -290,8 +165,6 @@ static int setup_conv(boa_net* net, ConvLayer& L, int N, const int din[3], int c
 // Device layout of one weight set: every tensor of the blob, in blob order, at a 256-byte aligned offset of one arena.
 // `visit(piece, layer pointers..., byte size)` is called in blob order; used both to size / fill the arena and
 // to point the layers at it.
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 template <typename F>
 static void for_each_weight_piece(boa_net* net, F&& f) {
     auto conv = [&](ConvLayer& L) {
@@ -705,7 +578,7 @@ static int convt_step(boa_net* net, const Fwd& f, const LayerProf& prof, UpLayer
 
 // what conv_step / convt_step launch for a layer, as boa_net_debug_layer reports it: {BOA_LK_* kernel, R (MT of k_convt_x3), row reuse
 // of k_conv_ws (log2 of a split-precision transposed conv's output fold)}
-static void conv_kernel_info(const boa_net* net, const ConvLayer& L, int info[3]) {
+void conv_kernel_info(const boa_net* net, const ConvLayer& L, int info[3]) {
     if (net->mode == NetMode::F32Ref) {
         info[0] = BOA_LK_CONV_F32;
     } else if (L.first) {
@@ -718,7 +591,7 @@ static void conv_kernel_info(const boa_net* net, const ConvLayer& L, int info[3]
     }
 }
 
-static void convt_kernel_info(const boa_net* net, const UpLayer& U, int info[3]) {
+void convt_kernel_info(const boa_net* net, const UpLayer& U, int info[3]) {
     switch (net->mode) {
         case NetMode::F16: {
             const int form = convt_mfma_form(U.Cin, U.s, true);   // (the source of a transposed conv is always a normalised conv output)
@@ -737,8 +610,7 @@ static void convt_kernel_info(const boa_net* net, const UpLayer& U, int info[3])
 }
 
 // run the conv stack for N tiles; leaves the last decoder activation (+ its ss) in net->dec.back().back()
-static int net_forward_stack(boa_net* net, const float* volume, const int V[3], const int vol_off[3],
-                             const int* host_origins, int N, int flip_mask = 0) {
+int net_forward_stack(boa_net* net, const float* volume, const int V[3], const int vol_off[3], const int* host_origins, int N, int flip_mask) {
     boa_ctx* c = net->ctx;
     const boa_net_desc& d = net->d;
     BOA_REQUIRE(N >= 1 && N <= net->maxN, "forward: batch %d exceeds max_batch %d", N, net->maxN);
@@ -786,16 +658,15 @@ static int net_forward_stack(boa_net* net, const float* volume, const int V[3], 
 // The scatter-form head (one launch per tile) of a network, as its BOA_LK_* code: fp16 -> the MFMA head; split precision -> k_head_x3
 // (the gather head's arithmetic: label path == logits API, bit for bit) for F0 = 32 and up to 32 classes, else the fp32 head;
 // fp32_ref -> the fp32 head.
-static int head_kernel(const boa_net* net) {
+int head_kernel(const boa_net* net) {
     const boa_net_desc& d = net->d;
     if (net->mode == NetMode::F16) return BOA_LK_HEAD_MFMA;
     return net->mode == NetMode::Split && d.features[0] == 32 && d.num_classes <= 32 ? BOA_LK_HEAD_X3 : BOA_LK_HEAD_F32;
 }
 
 // runs it on one tile: `act` at the first record it reads, `plane_stride` as ActLayout::plane_stride
-static int scatter_head(const boa_net* net, const void* act, const float* ss, const int P[3], size_t plane_stride, const float* w,
-                        const float* b, float* logits_out, const uint16_t* gauss, uint16_t* acc, uint16_t* nacc, const int PV[3],
-                        const int start[3]) {
+int scatter_head(const boa_net* net, const void* act, const float* ss, const int P[3], size_t plane_stride, const float* w, const float* b,
+                 float* logits_out, const uint16_t* gauss, uint16_t* acc, uint16_t* nacc, const int PV[3], const int start[3]) {
     const boa_net_desc& d = net->d;
     switch (head_kernel(net)) {
         case BOA_LK_HEAD_MFMA:
@@ -811,8 +682,8 @@ static int scatter_head(const boa_net* net, const void* act, const float* ss, co
 }
 
 // head of tile i of the current batch without its first plane_skip axis-0 planes
-static int net_head(boa_net* net, int i, const int P[3], int plane_skip, float* logits_out, const uint16_t* gauss, uint16_t* acc,
-                    uint16_t* nacc, const int PV[3], const int start[3]) {
+int net_head(boa_net* net, int i, const int P[3], int plane_skip, float* logits_out, const uint16_t* gauss, uint16_t* acc, uint16_t* nacc,
+             const int PV[3], const int start[3]) {
     const boa_net_desc& d = net->d;
     const ConvLayer& last = net->dec.back().back();
     const ActLayout lay = act_layout(net->mode, d.features[0]);
@@ -889,7 +760,7 @@ extern "C" int boa_net_forward(boa_net* net, const float* dev_volume, const int 
 }
 
 // the sliding-window entry points' padded volume PV must hold a patch and the volume V at offset `off`, along every axis
-static int check_padded(const boa_net* net, const int V[3], const int PV[3], const int off[3], const char* who) {
+int check_padded(const boa_net* net, const int V[3], const int PV[3], const int off[3], const char* who) {
     for (int a = 0; a < 3; ++a)
         BOA_REQUIRE(PV[a] >= net->d.patch[a] && off[a] >= 0 && off[a] + V[a] <= PV[a],
                     "%s: padded dim %d (%d) must cover patch (%d) and volume (%d at %d)", who, a, PV[a], net->d.patch[a], V[a], off[a]);
@@ -923,665 +794,4 @@ extern "C" int boa_net_predict_sliding_window(boa_net* net, const float* dev_vol
         }
     }
     return BOA_OK;
-}
-
-// ------------------------------------------------------------------------------------------------------
-// Fused sliding window -> labels (head_gather.hip): the conv stack writes the last decoder activation of EVERY tile of the
-// volume into the context's stash, then one gather pass per fold walks the volume.  Conditions (else the caller uses
-// boa_net_predict_sliding_window + boa_finalize_labels): production or split-precision mode, no test-time mirroring, features[0] == 32,
-// <= 32 classes, tile origins = the full cartesian grid of per-axis steps in canonical (x outer, z inner) order.
-static bool grid_origins(const int* o, int n, std::vector<int> (&steps)[3]) {
-    for (int a = 0; a < 3; ++a) steps[a].clear();
-    if (n < 1) return false;
-    // canonical order: the last axis varies fastest
-    for (int t = 0; t < n && (t == 0 || o[t * 3 + 2] > o[(t - 1) * 3 + 2]); ++t) steps[2].push_back(o[t * 3 + 2]);
-    const int n2 = (int)steps[2].size();
-    if (n % n2) return false;
-    for (int t = 0; t < n; t += n2) {
-        if (t > 0 && o[t * 3 + 1] <= o[(t - n2) * 3 + 1]) break;
-        steps[1].push_back(o[t * 3 + 1]);
-    }
-    const int n1 = (int)steps[1].size();
-    if (n % (n1 * n2)) return false;
-    for (int t = 0; t < n; t += n1 * n2) steps[0].push_back(o[t * 3]);
-    const int n0 = (int)steps[0].size();
-    if ((long long)n0 * n1 * n2 != n) return false;
-    for (int a = 0; a < 3; ++a)
-        for (size_t i = 1; i < steps[a].size(); ++i)
-            if (steps[a][i] <= steps[a][i - 1]) return false;
-    for (int t = 0; t < n; ++t) {
-        const int iz = t % n2, iy = (t / n2) % n1, ix = t / (n1 * n2);
-        if (o[t * 3] != steps[0][ix] || o[t * 3 + 1] != steps[1][iy] || o[t * 3 + 2] != steps[2][iz]) return false;
-    }
-    return n0 < 256 && n1 < 256 && n2 < 256;
-}
-
-// The last decoder activation of EVERY tile of a fold, kept in the context's stash for the gather head (k_gather_head): layout
-// [activations][fp32 ss][packed ss16 of the conv stack][head ss table][walk table]
-struct TileStash {
-    const __half* act = nullptr;   // fp16 chunk planes (fp32 octet planes in the split-precision mode)
-    float* ss = nullptr;           // [tile][F0][2] fp32 (scale, shift) of the last InstanceNorm
-    unsigned* ssp = nullptr;       // [tile][2][16] packed fp16 (scale, shift): the fp16 head's table
-    int* tab = nullptr;            // walk table (device)
-    bool x3 = false;
-    std::vector<int> steps[3];     // tile origins per axis
-};
-
-// byte offsets of a gather-head stash's sub-buffers after act_bytes of activations (the ss16 slot only when `ss16`) and its size
-struct StashOffsets {
-    size_t ss, ss16, ssp, tab, bytes;
-};
-
-static StashOffsets stash_offsets(size_t act_bytes, int n_tiles, int F, bool ss16, size_t tab_ints) {
-    StashOffsets o;
-    o.ss = align256(act_bytes);
-    o.ss16 = align256(o.ss + (size_t)n_tiles * F * 2 * sizeof(float));
-    o.ssp = ss16 ? align256(o.ss16 + (size_t)n_tiles * F * sizeof(unsigned)) : o.ss16;
-    o.tab = align256(o.ssp + (size_t)n_tiles * 32 * sizeof(unsigned));
-    o.bytes = align256(o.tab + tab_ints * sizeof(int));
-    return o;
-}
-
-// The gather head's walk table: the tile origins per axis, then per coordinate the first covering tile and the count (x, y), per
-// 32-voxel z run the tiles that intersect the run, as `first | count << 8` (a tile at origin o covers [o, o + ext[a]) along axis a)
-static std::vector<int> walk_table(const std::vector<int>& s0, const std::vector<int>& s1, const std::vector<int>& s2, const int ext[3],
-                                   const int PV[3]) {
-    const std::vector<int>* steps[3] = {&s0, &s1, &s2};
-    std::vector<int> tab;
-    for (const std::vector<int>* s : steps) tab.insert(tab.end(), s->begin(), s->end());
-    auto cover = [&](int a, int lo, int hi) {
-        const std::vector<int>& st = *steps[a];
-        int first = 0, cnt = 0;
-        for (size_t i = 0; i < st.size(); ++i)
-            if (st[i] <= hi && st[i] + ext[a] > lo) {
-                if (!cnt) first = (int)i;
-                ++cnt;
-            }
-        return first | (cnt << 8);
-    };
-    for (int x = 0; x < PV[0]; ++x) tab.push_back(cover(0, x, x));
-    for (int y = 0; y < PV[1]; ++y) tab.push_back(cover(1, y, y));
-    for (int zb = 0; zb < PV[2]; zb += 32) tab.push_back(cover(2, zb, std::min(zb + 31, PV[2] - 1)));
-    return tab;
-}
-
-// Keeps the context's tile stash out of boa_trim's reach (an allocation that fails under memory pressure trims, and a trim frees an
-// idle stash) from before the tiles are written until the LAST consumer of the TileStash pointers -- the deferred planes' copies, the
-// gather head launch -- is queued on the stream; a later trim synchronises the stream before it frees anything.
-struct StashHold {
-    boa_ctx* c;
-    explicit StashHold(boa_ctx* ctx) : c(ctx) { c->stash_busy = true; }
-    ~StashHold() { c->stash_busy = false; }
-    StashHold(const StashHold&) = delete;
-    StashHold& operator=(const StashHold&) = delete;
-};
-
-// runs the conv stack over all tiles (batches of max_batch), the last decoder conv writing straight into the stash slots of its tiles, and
-// builds the gather head's walk table.  BOA_ENOMEM when the stash does not fit (the caller falls back to the scatter form).
-static int net_forward_into_stash(boa_net* net, const float* dev_volume, const int V[3], const int PV[3], const int* off, const int* host_origins,
-                                  int n_tiles, TileStash& ts) {
-    boa_ctx* c = net->ctx;
-    const boa_net_desc& d = net->d;
-    std::vector<int> (&steps)[3] = ts.steps;
-    grid_origins(host_origins, n_tiles, steps);
-    const int F0 = d.features[0];
-    const size_t pv = (size_t)d.patch[0] * d.patch[1] * d.patch[2];
-    const ActLayout lay = act_layout(net->mode, F0);
-    const StashOffsets o = stash_offsets(lay.tile(n_tiles, pv), n_tiles, F0, true, (size_t)n_tiles + PV[0] + PV[1] + PV[2] + 64);
-    const size_t need = o.bytes;
-    if (c->stash_bytes < need) {
-        BOA_HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->stash) hipFree(c->stash);
-        c->stash = nullptr;
-        c->stash_bytes = 0;
-        boa_trim(c);
-        // The stash may take a bounded share of what is free NOW ($BOA_STASH_FRAC, default 0.6): what follows the network on this
-        // context and on the GPU's other contexts -- fold buffers, post-processing volumes, the second lane, RCCL buffers -- has no
-        // fallback of its own, the tile loop has one (BOA_ENOMEM here sends the caller to the scatter form, which needs
-        // (C + 1) fp16 planes instead of a tile stash).
-        {
-            static const double frac = getenv("BOA_STASH_FRAC") ? atof(getenv("BOA_STASH_FRAC")) : 0.6;
-            size_t fr = 0, tot = 0;
-            if (hipMemGetInfo(&fr, &tot) == hipSuccess && (double)need > frac * (double)fr) {
-                boa_set_error("fused sliding window: stash of %zu bytes exceeds %.2f of the %zu free bytes", need, frac, fr);
-                return BOA_ENOMEM;
-            }
-        }
-        if (hipMalloc(&c->stash, need) != hipSuccess) {
-            (void)hipGetLastError();
-            c->stash = nullptr;
-            boa_set_error("fused sliding window: %zu bytes of stash do not fit", need);
-            return BOA_ENOMEM;
-        }
-        c->stash_bytes = need;
-    }
-    unsigned char* base = (unsigned char*)c->stash;
-    ts.x3 = lay.esz == 4;   // split-precision mode: the stash holds the fp32 octet planes, the head reads the fp32 (scale, shift)
-    float* s_ss = (float*)(base + o.ss);
-    unsigned* s_ss16 = (unsigned*)(base + o.ss16);
-    unsigned* s_ssp = (unsigned*)(base + o.ssp);
-    int* s_steps = (int*)(base + o.tab);
-    ConvLayer& last = net->dec.back().back();
-    void* keep_act = last.act;
-    float* keep_ss = last.ss;
-    unsigned* keep_ss16 = last.ss16;
-    int rc = BOA_OK;
-    // (the caller holds c->stash_busy -- StashHold -- until every use of the returned pointers has been queued: boa_trim must not
-    //  release the stash while tiles are being written into it, nor between this call and the caller's copies / gather launch)
-    for (int t0 = 0; t0 < n_tiles && rc == BOA_OK; t0 += net->maxN) {
-        const int nb = std::min(net->maxN, n_tiles - t0);
-        // the last decoder conv of this batch writes straight into the stash slots of its tiles
-        last.act = base + lay.tile(t0, pv);
-        last.ss = s_ss + (size_t)t0 * F0 * 2;
-        last.ss16 = keep_ss16 ? s_ss16 + (size_t)t0 * F0 : nullptr;
-        rc = net_forward_stack(net, dev_volume, V, off, host_origins + (size_t)t0 * 3, nb);
-    }
-    last.act = keep_act;
-    last.ss = keep_ss;
-    last.ss16 = keep_ss16;
-    if (rc) return rc;
-    if (!ts.x3) BOA_TRY(launch_pack_head_ss(c, s_ss, s_ssp, n_tiles));
-    const std::vector<int> tab = walk_table(steps[0], steps[1], steps[2], d.patch, PV);
-    BOA_HIP_TRY(hipMemcpyAsync(s_steps, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    BOA_HIP_TRY(hipStreamSynchronize(c->stream));   // (the table is a stack-lifetime host vector)
-    c->prof_break = true;
-    ts.act = (const __half*)base;
-    ts.ss = s_ss;
-    ts.ssp = s_ssp;
-    ts.tab = s_steps;
-    return BOA_OK;
-}
-
-extern "C" int boa_net_labels_supported(boa_net* net, const int* host_origins, int n_tiles) {
-    if (!net || !host_origins) return 0;
-    // (record planes -- not fp32_ref's channels-last records --, patch z extent a multiple of 32 and <= 31 classes: the shapes for which
-    //  the scatter loop's head runs on the matrix cores too, so that the label path and the logits API share one head arithmetic)
-    if (!act_layout(net->mode, net->d.features[0]).planar || net->mirror_mask != 0 || net->d.features[0] != 32 || net->d.num_classes > 31 || net->d.patch[2] % 32 != 0) return 0;
-    std::vector<int> steps[3];
-    return grid_origins(host_origins, n_tiles, steps) ? 1 : 0;
-}
-
-extern "C" int boa_net_predict_labels_fold(boa_net* net, const float* dev_volume, const int V[3], const int PV[3], const int* vol_off,
-                                           const int* host_origins, int n_tiles, const uint16_t* dev_gauss, uint16_t* dev_fold,
-                                           int fold_index, int n_folds, const uint8_t* host_lut, int merge, uint8_t* dev_labels_out,
-                                           const int* crop_off, const int* crop_dims, int* dev_inf_flag) {
-    BOA_REQUIRE(net && dev_volume && V && PV && host_origins && dev_inf_flag, "boa_net_predict_labels_fold: NULL argument");
-    BOA_REQUIRE(boa_net_labels_supported(net, host_origins, n_tiles), "boa_net_predict_labels_fold: unsupported network / tile layout");
-    BOA_TRY(net_bind_arena(net));
-    BOA_REQUIRE(n_folds >= 1 && fold_index >= 0 && fold_index < n_folds && (n_folds == 1 || dev_fold), "boa_net_predict_labels_fold: folds");
-    BOA_REQUIRE(fold_index + 1 < n_folds || dev_labels_out, "boa_net_predict_labels_fold: the last fold needs the label buffer");
-    boa_ctx* c = net->ctx;
-    const boa_net_desc& d = net->d;
-    const int zero[3] = {0, 0, 0};
-    const int* off = vol_off ? vol_off : zero;
-    BOA_TRY(check_padded(net, V, PV, off, "fused sliding window"));
-    TileStash ts;
-    StashHold hold(net->ctx);   // until launch_gather_head below is queued
-    BOA_TRY(net_forward_into_stash(net, dev_volume, V, PV, off, host_origins, n_tiles, ts));
-    float* s_ss = ts.ss;
-    unsigned* s_ssp = ts.ssp;
-    int* s_steps = ts.tab;
-    const __half* s_act = ts.act;
-    const bool x3 = ts.x3;
-    std::vector<int> (&steps)[3] = ts.steps;
-    const int ntile[3] = {(int)steps[0].size(), (int)steps[1].size(), (int)steps[2].size()};
-    const int mode = n_folds == 1 ? 0 : (fold_index == 0 ? 1 : (fold_index + 1 == n_folds ? 3 : 2));
-    return launch_gather_head(c, s_act, x3 ? (const unsigned*)s_ss : s_ssp, net->head_w, net->head_b, dev_gauss, d.num_classes, d.patch, PV, ntile,
-                              s_steps, dev_fold, mode, n_folds, host_lut, merge, dev_labels_out, crop_off, crop_dims, dev_inf_flag, d.lrelu_slope,
-                              n_tiles, x3);
-}
-
-// ------------------------------------------------------------------------------------------------------
-// tile-sharded sliding window (several GPUs on one volume): the rank that owns tile rows [b0, b1) along
-// axis 0 cannot add the first `defer` planes of its row-b0 tiles before the lower rank's partial sums for those
-// planes have arrived (the reference's fp16 `+=` runs in ascending tile order per voxel).  The head input of those
-// planes is kept in a stash and applied afterwards; everything else is accumulated at once.
-struct boa_stash {
-    boa_ctx* ctx = nullptr;
-    unsigned char* arena = nullptr;
-    // head weights of the weight set that produced the stashed activations: the stash may be applied after the network has
-    // switched to the next fold's weights (the exchange of fold f overlaps the tiles of fold f + 1); the sets are cached device
-    // arenas (boa_net::wsets), so the pointers outlive the switch
-    const float* head_w = nullptr;
-    const float* head_b = nullptr;
-    struct Item {
-        size_t act_off, ss_off;
-        int planes;
-        int start[3];
-    };
-    std::vector<Item> items;
-    // gather form (boa_net_predict_sliding_window_deferred ran the gather head): the first dp planes of every deferring tile (the block's
-    // first tile row; with steps below half a patch also the rows behind it, which defer fewer planes) in the gather head's own stash
-    // layout -- [tile][F / 16 planes][dp * P1 * P2 voxels][32 B], the (scale, shift) tables, the walk table -- so that
-    // boa_net_apply_deferred is ONE more k_gather_head launch over planes [x0, x_split), started from the lower rank's sums
-    bool gather = false, x3 = false;
-    int dp = 0, x0 = 0, x_split = 0, n0 = 0, n1 = 0, n2 = 0, n_items = 0;
-    StashOffsets o{};
-};
-
-extern "C" void boa_stash_destroy(boa_stash* st) {
-    if (!st) return;
-    if (st->arena) boa_free(st->ctx, st->arena);
-    delete st;
-}
-
-extern "C" int boa_net_predict_sliding_window_deferred(boa_net* net, const float* dev_volume, const int V[3],
-                                                       const int PV[3], const int* vol_off, const int* host_origins,
-                                                       int n_tiles, const uint16_t* dev_gauss, uint16_t* dev_acc,
-                                                       uint16_t* dev_n, const int* host_defer_planes,
-                                                       boa_stash** stash_out) {
-    BOA_REQUIRE(net && dev_volume && V && PV && host_origins && dev_acc && dev_n && host_defer_planes && stash_out,
-                "boa_net_predict_sliding_window_deferred: NULL argument");
-    BOA_TRY(net_bind_arena(net));
-    const boa_net_desc& d = net->d;
-    BOA_REQUIRE(net->mirror_mask == 0, "deferred sliding window (tile sharding) is not available with test-time mirroring");
-    const int zero[3] = {0, 0, 0};
-    const int* off = vol_off ? vol_off : zero;
-    BOA_TRY(check_padded(net, V, PV, off, "sliding window"));
-    const int F = d.features[0];
-    const size_t plane = (size_t)d.patch[1] * d.patch[2];
-    const size_t pv = (size_t)d.patch[0] * plane;
-    const ActLayout lay = act_layout(net->mode, F);
-    boa_stash* st = new boa_stash;
-    st->ctx = net->ctx;
-    st->head_w = net->head_w;
-    st->head_b = net->head_b;
-    size_t bytes = 0;
-    for (int i = 0; i < n_tiles; ++i) {
-        int dp = host_defer_planes[i];
-        if (dp < 0 || dp > d.patch[0]) {
-            delete st;
-            BOA_REQUIRE(false, "deferred sliding window: tile %d defers %d planes of %d", i, dp, d.patch[0]);
-        }
-        if (dp == 0) continue;
-        boa_stash::Item it;
-        it.act_off = bytes;
-        bytes += align256(lay.bytes((size_t)dp * plane));
-        it.ss_off = bytes;
-        bytes += 256 * ((F * 2 * 4 + 255) / 256);
-        it.planes = dp;
-        for (int a = 0; a < 3; ++a) it.start[a] = host_origins[(size_t)i * 3 + a];
-        st->items.push_back(it);
-    }
-    int rc = BOA_OK;
-    // Gather form (the product path when the network / tile grid allow it, as in boa_net_predict_labels_fold): every tile's last
-    // activation goes to the context's stash, the planes to defer are copied out of it, and ONE k_gather_head launch in raw mode
-    // writes the partial sums of all other planes of this rank -- [x_split, end of its last row) -- instead of one accumulator
-    // read-modify-write per covering tile.  The planes below x_split are exactly the deferred ones (checked) and all belong to the
-    // block's first tile row: they stay untouched until boa_net_apply_deferred adds them, with the same kernel, on top of the
-    // lower rank's sums.  Same head arithmetic for every tile (the matrix-core head), whatever the tile origins' alignment.
-    if (n_tiles > 0 && boa_net_labels_supported(net, host_origins, n_tiles)) {
-        // dp0 = the deepest deferral (the block's first row); rows that start further up defer fewer planes -- actual steps below
-        // half a patch make the block's second row reach the lower block's last row too.  Every deferred tile keeps dp0 planes (the
-        // later rows more than they defer: valid planes of the tile, never visited by the launch over [x0, x_split)).
-        int x_first = host_origins[0], x_split = -1, x_end = 0, dp0 = 0, x0 = 0, n_def = 0;
-        std::vector<int> def_rows;
-        bool consistent = true;
-        for (int i = 0; i < n_tiles; ++i) {
-            const int xo = host_origins[(size_t)i * 3], dpi = host_defer_planes[i];
-            x_first = std::min(x_first, xo);
-            x_end = std::max(x_end, xo + d.patch[0]);
-            if (dpi > 0) {
-                if (n_def == 0) {
-                    dp0 = dpi;
-                    x0 = xo;
-                    x_split = xo + dpi;
-                }
-                consistent = consistent && xo + dpi == x_split && xo >= x0;   // all end at the same plane (canonical order: x0 first)
-                if (def_rows.empty() || def_rows.back() != xo) def_rows.push_back(xo);
-                ++n_def;
-            }
-        }
-        if (x_split < 0) x_split = x_first;
-        for (int i = 0; i < n_tiles; ++i) {   // every tile that reaches below x_split defers exactly its planes below x_split
-            const int below = std::max(0, std::min(x_split - host_origins[(size_t)i * 3], d.patch[0]));
-            consistent = consistent && host_defer_planes[i] == below;
-        }
-        TileStash ts;
-        StashHold hold(net->ctx);   // across the arena allocation below (it may trim), the stash copies and the raw gather launch
-        int grc = consistent ? net_forward_into_stash(net, dev_volume, V, PV, off, host_origins, n_tiles, ts) : BOA_ENOMEM;
-        if (grc == BOA_OK) {
-            boa_ctx* c = net->ctx;
-            // the deferred planes in the gather head's layout
-            st->gather = true;
-            st->x3 = ts.x3;
-            st->dp = dp0;
-            st->x0 = x0;
-            st->n1 = (int)ts.steps[1].size();
-            st->n2 = (int)ts.steps[2].size();
-            st->n_items = n_def;
-            const size_t item_act = lay.bytes((size_t)dp0 * plane);
-            st->o = stash_offsets((size_t)n_def * item_act, n_def, F, false,
-                                  def_rows.size() + st->n1 + st->n2 + PV[0] + PV[1] + PV[2] / 32 + 8);
-            st->n0 = (int)def_rows.size();
-            st->x_split = x_split;
-            if (n_def > 0) {
-                if ((rc = boa_malloc(c, st->o.bytes, (void**)&st->arena)) != BOA_OK) {
-                    boa_stash_destroy(st);
-                    return rc;
-                }
-                if (n_def != (int)def_rows.size() * st->n1 * st->n2) {
-                    boa_stash_destroy(st);
-                    boa_set_error("deferred sliding window: %d deferred tiles in %d rows of %d x %d", n_def, (int)def_rows.size(), st->n1, st->n2);
-                    return BOA_EINVAL;
-                }
-                bool ok_copy = true;
-                int item = 0;
-                for (int i = 0; i < n_tiles && ok_copy; ++i) {
-                    if (host_defer_planes[i] == 0) continue;
-                    ok_copy = lay.copy_head(st->arena + (size_t)item * item_act, (const unsigned char*)ts.act + lay.tile(i, pv), dp0, plane, pv,
-                                            c->stream) == hipSuccess;
-                    ok_copy = ok_copy && hipMemcpyAsync(st->arena + st->o.ss + (size_t)item * F * 2 * sizeof(float), ts.ss + (size_t)i * F * 2,
-                                                        (size_t)F * 2 * sizeof(float), hipMemcpyDeviceToDevice, c->stream) == hipSuccess;
-                    ++item;
-                }
-                if (!ok_copy) {
-                    boa_stash_destroy(st);
-                    boa_set_error("deferred sliding window: stash copy failed");
-                    return BOA_EHIP;
-                }
-                if (!ts.x3 && (rc = launch_pack_head_ss(c, (const float*)(st->arena + st->o.ss), (unsigned*)(st->arena + st->o.ssp), n_def)) != BOA_OK) {
-                    boa_stash_destroy(st);
-                    return rc;
-                }
-                // walk table of the deferring tile rows with dp0 planes per tile
-                const int ext[3] = {dp0, d.patch[1], d.patch[2]};
-                const std::vector<int> tab = walk_table(def_rows, ts.steps[1], ts.steps[2], ext, PV);
-                if (hipMemcpyAsync(st->arena + st->o.tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-                    hipStreamSynchronize(c->stream) != hipSuccess) {   // (the table is a stack-lifetime host vector)
-                    boa_stash_destroy(st);
-                    boa_set_error("deferred sliding window: walk table copy failed");
-                    return BOA_EHIP;
-                }
-            }
-            c->prof_break = true;
-            const int ntile[3] = {(int)ts.steps[0].size(), (int)ts.steps[1].size(), (int)ts.steps[2].size()};
-            const int xr[2] = {x_split, std::min(x_end, PV[0])};
-            rc = launch_gather_head(c, ts.act, ts.x3 ? (const unsigned*)ts.ss : ts.ssp, net->head_w, net->head_b, dev_gauss, d.num_classes, d.patch, PV, ntile,
-                                    ts.tab, dev_acc, 4, 1, nullptr, 0, nullptr, nullptr, nullptr, nullptr, d.lrelu_slope, n_tiles, ts.x3, xr, dev_n, 0);
-            if (rc != BOA_OK) {
-                boa_stash_destroy(st);
-                return rc;
-            }
-            *stash_out = st;
-            return BOA_OK;
-        }
-        if (grc != BOA_ENOMEM) {
-            boa_stash_destroy(st);
-            return grc;
-        }
-        // (stash does not fit / unusual deferral pattern: the scatter loop below)
-    }
-    rc = bytes ? boa_malloc(net->ctx, bytes, (void**)&st->arena) : BOA_OK;
-    if (rc != BOA_OK) {
-        delete st;
-        return rc;
-    }
-    size_t item = 0;
-    for (int t0 = 0; t0 < n_tiles && rc == BOA_OK; t0 += net->maxN) {
-        int nb = std::min(net->maxN, n_tiles - t0);
-        rc = net_forward_stack(net, dev_volume, V, off, host_origins + (size_t)t0 * 3, nb);
-        ConvLayer& last = net->dec.back().back();
-        for (int i = 0; i < nb && rc == BOA_OK; ++i) {
-            const int* stt = host_origins + (size_t)(t0 + i) * 3;
-            const float* ss = last.ss + (size_t)i * F * 2;
-            int dp = host_defer_planes[t0 + i];
-            if (dp > 0) {
-                const boa_stash::Item& it = st->items[item++];
-                // the first dp axis-0 planes in the stash, with its own plane stride (dp * plane voxels)
-                const bool ok_copy = lay.copy_head(st->arena + it.act_off, (const unsigned char*)last.act + lay.tile(i, pv), dp, plane, pv,
-                                                   net->ctx->stream) == hipSuccess;
-                if (!ok_copy ||
-                    hipMemcpyAsync(st->arena + it.ss_off, ss, (size_t)F * 2 * 4, hipMemcpyDeviceToDevice,
-                                   net->ctx->stream) != hipSuccess) {
-                    boa_set_error("deferred sliding window: stash copy failed");
-                    rc = BOA_EHIP;
-                    break;
-                }
-                net->ctx->prof_break = true;
-            }
-            if (dp < d.patch[0]) {
-                int P[3] = {d.patch[0] - dp, d.patch[1], d.patch[2]};
-                int s2[3] = {stt[0] + dp, stt[1], stt[2]};
-                rc = net_head(net, i, P, dp, nullptr, dev_gauss ? dev_gauss + (size_t)dp * plane : nullptr, dev_acc, dev_n, PV, s2);
-            }
-        }
-    }
-    if (rc != BOA_OK) {
-        boa_stash_destroy(st);
-        return rc;
-    }
-    *stash_out = st;
-    return BOA_OK;
-}
-
-extern "C" int boa_net_apply_deferred(boa_net* net, const boa_stash* st, const uint16_t* dev_gauss, uint16_t* dev_acc,
-                                      uint16_t* dev_n, const int PV[3]) {
-    BOA_REQUIRE(net && st && dev_acc && dev_n && PV, "boa_net_apply_deferred: NULL argument");
-    const boa_net_desc& d = net->d;
-    if (st->gather) {
-        if (st->n_items == 0) return BOA_OK;
-        const int P[3] = {st->dp, d.patch[1], d.patch[2]};
-        const int ntile[3] = {st->n0, st->n1, st->n2};
-        const int xr[2] = {st->x0, std::min(st->x_split, PV[0])};
-        return launch_gather_head(net->ctx, (const __half*)st->arena, (const unsigned*)(st->arena + (st->x3 ? st->o.ss : st->o.ssp)), st->head_w, st->head_b,
-                                  dev_gauss, d.num_classes, P, PV, ntile, (const int*)(st->arena + st->o.tab), dev_acc, 4, 1, nullptr, 0, nullptr, nullptr,
-                                  nullptr, nullptr, d.lrelu_slope, st->n_items, st->x3, xr, dev_n, 1);
-    }
-    const ActLayout lay = act_layout(net->mode, d.features[0]);
-    for (const boa_stash::Item& it : st->items) {  // the stash keeps the canonical tile order
-        int P[3] = {it.planes, d.patch[1], d.patch[2]};
-        BOA_TRY(scatter_head(net, st->arena + it.act_off, (const float*)(st->arena + it.ss_off), P,
-                             lay.plane_stride((size_t)it.planes * d.patch[1] * d.patch[2]), st->head_w, st->head_b, nullptr, dev_gauss,
-                             dev_acc, dev_n, PV, it.start));
-    }
-    return BOA_OK;
-}
-
-// ------------------------------------------------------------------------------------------------------
-// unit-test seams
-extern "C" int boa_conv_block_test(boa_ctx* ctx, const float* dev_in, int N, int Cin, const int dims[3],
-                                   const float* host_w, const float* host_b, const float* host_gamma,
-                                   const float* host_beta, int Cout, const int kernel[3], const int stride[3],
-                                   int with_norm_act, int impl, float* dev_out) {
-    BOA_REQUIRE(ctx && dev_in && dims && host_w && host_b && kernel && stride && dev_out, "conv test: NULL argument");
-    BOA_REQUIRE(impl == 0, "conv test: impl %d not available", impl);
-    ConvGeom g;
-    g.N = N; g.Di = dims[0]; g.Hi = dims[1]; g.Wi = dims[2]; g.Cout = Cout; g.Cin = Cin;
-    int dout[3];
-    for (int a = 0; a < 3; ++a) {
-        g.k[a] = kernel[a];
-        g.s[a] = stride[a];
-        dout[a] = (dims[a] + 2 * ((kernel[a] - 1) / 2) - kernel[a]) / stride[a] + 1;
-    }
-    g.Do = dout[0]; g.Ho = dout[1]; g.Wo = dout[2];
-    ConvTile t;
-    ConvGeom gref = g;
-    gref.N = TILE_REF_BATCH;  // as the network does: the tile shape must not depend on the batch size
-    BOA_REQUIRE(choose_conv_tile(gref, ctx->cu_count, &t), "conv test: no tile configuration");
-    size_t vin = (size_t)dims[0] * dims[1] * dims[2], vout = (size_t)dout[0] * dout[1] * dout[2];
-    __half *in16 = nullptr, *out16 = nullptr, *wpk = nullptr;
-    float *bias = nullptr, *gamma = nullptr, *beta = nullptr, *partials = nullptr, *ss = nullptr;
-    int nblk = conv_nblk(t, ctx->cu_count, Cout);
-    std::vector<__half> tmp(conv_wpk_halves(Cin, Cout, kernel));
-    pack_conv_weights(host_w, Cin, Cout, kernel, tmp.data());
-    std::vector<float> ones(Cout, 1.f), zeros(Cout, 0.f);
-    int rc = BOA_OK;
-#define T_(x) do { if (rc == BOA_OK) rc = (x); } while (0)
-    T_(boa_malloc(ctx, (size_t)N * vin * Cin * 2, (void**)&in16));
-    T_(boa_malloc(ctx, (size_t)N * vout * Cout * 2, (void**)&out16));
-    T_(boa_malloc(ctx, tmp.size() * 2, (void**)&wpk));
-    T_(boa_malloc(ctx, Cout * 4, (void**)&bias));
-    T_(boa_malloc(ctx, Cout * 4, (void**)&gamma));
-    T_(boa_malloc(ctx, Cout * 4, (void**)&beta));
-    T_(boa_malloc(ctx, (size_t)N * Cout * 2 * nblk * 4, (void**)&partials));
-    T_(boa_memset(ctx, partials, 0, (size_t)N * Cout * 2 * nblk * 4));
-    T_(boa_malloc(ctx, (size_t)N * Cout * 2 * 4, (void**)&ss));
-    T_(boa_h2d(ctx, wpk, tmp.data(), tmp.size() * 2));
-    T_(boa_h2d(ctx, bias, host_b, Cout * 4));
-    T_(boa_h2d(ctx, gamma, host_gamma ? host_gamma : ones.data(), Cout * 4));
-    T_(boa_h2d(ctx, beta, host_beta ? host_beta : zeros.data(), Cout * 4));
-    T_(launch_nchw_to_ndhwc_f16(ctx, dev_in, N, Cin, vin, in16));
-    ActSrc a, none;
-    a.data = in16; a.ss = nullptr; a.C = Cin;
-    T_(launch_conv_mfma(ctx, a, none, g, t, wpk, bias, 0.01f, out16, partials));
-    T_(launch_norm_finalize(ctx, partials, nblk, N, Cout, (double)vout, gamma, beta, 1e-5f, ss, nullptr, 1));
-    T_(launch_ndhwc_to_nchw_f32(ctx, out16, with_norm_act ? ss : nullptr, 0.01f, N, Cout, vout, dev_out));
-    if (rc == BOA_OK) rc = boa_sync(ctx);
-#undef T_
-    boa_free(ctx, in16); boa_free(ctx, out16); boa_free(ctx, wpk); boa_free(ctx, bias); boa_free(ctx, gamma);
-    boa_free(ctx, beta); boa_free(ctx, partials); boa_free(ctx, ss);
-    return rc;
-}
-
-// fp32 NCDHW of one stored tile for the debug seams, with a transposed conv's output fold taken out again (x / fold is exact): through
-// the conversion's (scale, shift) path with scale 1 / fold, shift 0 and slope 1 (LeakyReLU with slope 1 is the identity)
-static int debug_to_nchw(boa_net* net, const ActLayout& lay, const void* tile, const float* ss, float fold, size_t vox, float* out) {
-    if (fold == 1.f) return lay.to_nchw(net->ctx, tile, ss, net->d.lrelu_slope, vox, out);
-    std::vector<float> tab((size_t)lay.C * 2);
-    for (int i = 0; i < lay.C; ++i) {
-        tab[2 * i] = 1.f / fold;
-        tab[2 * i + 1] = 0.f;
-    }
-    float* dss = nullptr;
-    BOA_TRY(boa_malloc(net->ctx, tab.size() * sizeof(float), (void**)&dss));
-    int rc = boa_h2d(net->ctx, dss, tab.data(), tab.size() * sizeof(float));
-    if (rc == BOA_OK) rc = lay.to_nchw(net->ctx, tile, dss, 1.f, vox, out);
-    if (rc == BOA_OK) rc = boa_sync(net->ctx);
-    boa_free(net->ctx, dss);
-    return rc;
-}
-
-extern "C" int boa_net_debug_activation(boa_net* net, int kind, int stage, int conv, int tile, float* dev_out, int* channels_out,
-                                        int dims_out[3]) {
-    BOA_REQUIRE(net && channels_out && dims_out, "boa_net_debug_activation: NULL argument");
-    BOA_REQUIRE(tile >= 0 && tile < net->maxN, "boa_net_debug_activation: tile %d outside the batch", tile);
-    BOA_TRY(net_bind_arena(net));
-    const float* ss = nullptr;
-    const void* act = nullptr;
-    float fold = 1.f;
-    int Cc = 0, dm[3] = {0, 0, 0};
-    if (kind == 1) {
-        BOA_REQUIRE(stage >= 0 && stage < (int)net->up.size(), "boa_net_debug_activation: no transposed conv %d", stage);
-        const UpLayer& U = net->up[stage];
-        Cc = U.Cout;
-        for (int a = 0; a < 3; ++a) dm[a] = U.din[a] * U.s[a];
-        act = U.act;
-        fold = U.fold;
-    } else {
-        auto& stages = kind == 0 ? net->enc : net->dec;
-        BOA_REQUIRE((kind == 0 || kind == 2) && stage >= 0 && stage < (int)stages.size() && conv >= 0 && conv < (int)stages[stage].size(),
-                    "boa_net_debug_activation: no layer (kind %d, stage %d, conv %d)", kind, stage, conv);
-        const ConvLayer& L = stages[stage][conv];
-        Cc = L.g.Cout;
-        dm[0] = L.g.Do; dm[1] = L.g.Ho; dm[2] = L.g.Wo;
-        act = L.act;
-        ss = L.ss + (size_t)tile * Cc * 2;
-    }
-    *channels_out = Cc;
-    for (int a = 0; a < 3; ++a) dims_out[a] = dm[a];
-    if (!dev_out) return BOA_OK;  // size query
-    const size_t vox = (size_t)dm[0] * dm[1] * dm[2];
-    const ActLayout lay = act_layout(net->mode, Cc);
-    return debug_to_nchw(net, lay, (const unsigned char*)act + lay.tile(tile, vox), ss, fold, vox, dev_out);
-}
-
-extern "C" int boa_net_debug_layer(boa_net* net, int kind, int stage, int conv, int tile, float* dev_raw, float* host_ss,
-                                   uint16_t* host_ss16, int* channels_out, int dims_out[3], int* host_info) {
-    BOA_REQUIRE(net && channels_out && dims_out, "boa_net_debug_layer: NULL argument");
-    BOA_REQUIRE(tile >= 0 && tile < net->maxN, "boa_net_debug_layer: tile %d outside the batch", tile);
-    BOA_TRY(net_bind_arena(net));
-    const boa_net_desc& d = net->d;
-    const void* act = nullptr;
-    const ConvLayer* L = nullptr;
-    float fold = 1.f;
-    int Cc = 0, dm[3] = {0, 0, 0}, info[3] = {0, 0, 0};
-    if (kind == 3) {   // the head: which kernel net_head launches (its output is the logits of boa_net_forward, nothing is stored)
-        BOA_REQUIRE(!dev_raw && !host_ss && !host_ss16, "boa_net_debug_layer: the head stores no output (kind 3 reports the kernel only)");
-        *channels_out = d.num_classes;
-        for (int a = 0; a < 3; ++a) dims_out[a] = d.patch[a];
-        if (host_info) {
-            host_info[0] = head_kernel(net);
-            host_info[1] = host_info[2] = 0;
-        }
-        return BOA_OK;
-    }
-    if (kind == 1) {
-        BOA_REQUIRE(stage >= 0 && stage < (int)net->up.size(), "boa_net_debug_layer: no transposed conv %d", stage);
-        const UpLayer& U = net->up[stage];
-        Cc = U.Cout;
-        for (int a = 0; a < 3; ++a) dm[a] = U.din[a] * U.s[a];
-        act = U.act;
-        fold = U.fold;
-        convt_kernel_info(net, U, info);
-    } else {
-        auto& stages = kind == 0 ? net->enc : net->dec;
-        BOA_REQUIRE((kind == 0 || kind == 2) && stage >= 0 && stage < (int)stages.size() && conv >= 0 && conv < (int)stages[stage].size(),
-                    "boa_net_debug_layer: no layer (kind %d, stage %d, conv %d)", kind, stage, conv);
-        L = &stages[stage][conv];
-        Cc = L->g.Cout;
-        dm[0] = L->g.Do; dm[1] = L->g.Ho; dm[2] = L->g.Wo;
-        act = L->act;
-        conv_kernel_info(net, *L, info);
-    }
-    *channels_out = Cc;
-    for (int a = 0; a < 3; ++a) dims_out[a] = dm[a];
-    if (host_info)
-        for (int i = 0; i < 3; ++i) host_info[i] = info[i];
-    if (host_ss) {
-        if (L) {
-            BOA_TRY(boa_sync(net->ctx));
-            BOA_HIP_TRY(hipMemcpy(host_ss, L->ss + (size_t)tile * Cc * 2, (size_t)Cc * 2 * sizeof(float), hipMemcpyDeviceToHost));
-        } else {
-            for (int i = 0; i < 2 * Cc; ++i) host_ss[i] = i & 1 ? 0.f : 1.f;   // (raw source: identity)
-        }
-    }
-    if (host_ss16) {
-        BOA_REQUIRE(L && L->ss16, "boa_net_debug_layer: fp16 (scale, shift) exist for the convs of the fp16 mode only");
-        BOA_TRY(boa_sync(net->ctx));
-        BOA_HIP_TRY(hipMemcpy(host_ss16, L->ss16 + (size_t)tile * Cc, (size_t)Cc * sizeof(unsigned), hipMemcpyDeviceToHost));
-    }
-    if (!dev_raw) return BOA_OK;
-    const size_t vox = (size_t)dm[0] * dm[1] * dm[2];
-    const ActLayout lay = act_layout(net->mode, Cc);
-    return debug_to_nchw(net, lay, (const unsigned char*)act + lay.tile(tile, vox), nullptr, fold, vox, dev_raw);
-}
-
-extern "C" int boa_head_tile(boa_ctx* ctx, const uint16_t* dev_act, const float* dev_ss, int F0, const int P[3], int C,
-                             const float* dev_w, const float* dev_b, float slope, float* dev_logits_out,
-                             const uint16_t* dev_gauss, uint16_t* dev_acc, uint16_t* dev_n, const int PV[3],
-                             const int start[3]) {
-    BOA_REQUIRE(ctx && dev_act && dev_ss && P && dev_w && dev_b, "boa_head_tile: NULL argument");
-    BOA_REQUIRE(dev_logits_out || (dev_acc && dev_n && PV && start), "boa_head_tile: neither logits_out nor accumulators given");
-    return launch_head(ctx, (const __half*)dev_act, dev_ss, F0, P, C, dev_w, dev_b, slope, dev_logits_out, dev_gauss, dev_acc,
-                       dev_n, PV, start);
-}
-
-extern "C" int boa_convtranspose_test(boa_ctx* ctx, const float* dev_in, int N, int Cin, const int dims[3],
-                                      const float* host_w, const float* host_b, int Cout, const int stride[3],
-                                      float* dev_out) {
-    BOA_REQUIRE(ctx && dev_in && dims && host_w && host_b && stride && dev_out, "convT test: NULL argument");
-    size_t vin = (size_t)dims[0] * dims[1] * dims[2];
-    size_t vout = vin * stride[0] * stride[1] * stride[2];
-    __half *in16 = nullptr, *out16 = nullptr, *wpk = nullptr;
-    float* bias = nullptr;
-    std::vector<__half> tmp(convt_wpk_halves(Cin, Cout, stride));
-    pack_convt_weights(host_w, Cin, Cout, stride, tmp.data());
-    int rc = BOA_OK;
-#define T_(x) do { if (rc == BOA_OK) rc = (x); } while (0)
-    T_(boa_malloc(ctx, (size_t)N * vin * Cin * 2, (void**)&in16));
-    T_(boa_malloc(ctx, (size_t)N * vout * Cout * 2, (void**)&out16));
-    T_(boa_malloc(ctx, tmp.size() * 2, (void**)&wpk));
-    T_(boa_malloc(ctx, Cout * 4, (void**)&bias));
-    T_(boa_h2d(ctx, wpk, tmp.data(), tmp.size() * 2));
-    T_(boa_h2d(ctx, bias, host_b, Cout * 4));
-    T_(launch_nchw_to_ndhwc_f16(ctx, dev_in, N, Cin, vin, in16));
-    ActSrc a;
-    a.data = in16; a.ss = nullptr; a.C = Cin;
-    T_(launch_convt_mfma(ctx, a, N, dims, stride, Cout, wpk, bias, 0.01f, out16));
-    T_(launch_ndhwc_to_nchw_f32(ctx, out16, nullptr, 0.01f, N, Cout, vout, dev_out));
-    if (rc == BOA_OK) rc = boa_sync(ctx);
-#undef T_
-    boa_free(ctx, in16); boa_free(ctx, out16); boa_free(ctx, wpk); boa_free(ctx, bias);
-    return rc;
 }

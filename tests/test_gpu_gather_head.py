@@ -302,3 +302,51 @@ def test_raw_partial_sums_equal_the_scatter_accumulators(ctx, precision, split_r
         for b in bufs + [dvol]:
             b.free()
         p.close()
+
+
+@pytest.mark.parametrize("precision", ["fp16", "fp32"])
+def test_an_unusual_deferral_takes_the_scatter_form(ctx, precision):
+    """boa_net_predict_sliding_window_deferred with a pattern the gather form does not take -- only the LAST tile row defers, while
+    the row before it reaches below the split plane and defers nothing -- runs the per-tile scatter form in the fp16 and split-precision
+    modes as well: no gather head, and the planes after boa_net_apply_deferred are the scatter loop's, bit for bit.  (The last row's
+    tiles are the last of every voxel's covering tiles in canonical order, so adding their first planes afterwards, in tile order, keeps
+    the reference's per-voxel `+=` sequence.)  Same shapes as test_raw_partial_sums_equal_the_scatter_accumulators; 9 planes: odd."""
+    from boa_hip._lib import check, int3
+    patch, shape, nc, dp = (32, 32, 32), (88, 48, 64), 6, 9
+    p = _pred(ctx, patch, nc, 1, 0.5, True, precision=precision)
+    x = np.random.default_rng(5).standard_normal((1, *shape)).astype(np.float32)
+    V, PV, below, origins = p._setup(x)
+    origins = np.ascontiguousarray(origins, dtype=np.int32).reshape(-1, 3)
+    rows = sorted(set(int(v) for v in origins[:, 0]))
+    assert (origins[:, 2] % 8 == 0).all() and len(rows) >= 4 and rows[-2] + patch[0] > rows[-1] + dp
+    defer = np.ascontiguousarray(np.where(origins[:, 0] == rows[-1], dp, 0), dtype=np.int32)
+    nvox = int(np.prod(PV))
+    dvol = ctx.from_numpy(x)
+    bufs = [ctx.alloc(nc * nvox * 2), ctx.alloc(nvox * 2), ctx.alloc(nc * nvox * 2), ctx.alloc(nvox * 2)]
+    acc_s, n_s, acc_d, n_d = bufs
+    try:
+        p._run_fold(dvol, V, PV, below, origins, acc_s, n_s, 0)             # scatter loop
+        p._ensure_net(0)
+        acc_d.zero()
+        n_d.zero()
+        g = p._gaussian()
+        ctx.counters(reset=True)
+        st = C.c_void_p()
+        check(p.lib.boa_net_predict_sliding_window_deferred(
+            p._net, dvol.vp, int3(V), int3(PV), int3(below), origins.ctypes.data_as(C.POINTER(C.c_int)), len(origins),
+            g.vp if g else None, acc_d.vp, n_d.vp, defer.ctypes.data_as(C.POINTER(C.c_int)), C.byref(st)), "deferred")
+        before = acc_d.download((nc, *PV), np.uint16)
+        check(p.lib.boa_net_apply_deferred(p._net, st, g.vp if g else None, acc_d.vp, n_d.vp, int3(PV)), "apply")
+        p.lib.boa_stash_destroy(st)
+        cd = ctx.counters(reset=True)
+        n_heads = len(origins) + int((defer > 0).sum())                     # one head per tile, one more per deferring tile
+        assert cd["head_gather"] == 0 and cd["head_valu"] == 0 and cd["f32"] == 0, cd
+        assert cd["head_mfma"] == n_heads if precision == "fp16" else (cd["head_mfma"] == 0 and cd["x3"] >= n_heads), cd
+        want = acc_s.download((nc, *PV), np.uint16)
+        assert (before[:, rows[-1]:rows[-1] + dp] != want[:, rows[-1]:rows[-1] + dp]).any()      # the deferred planes were kept back
+        np.testing.assert_array_equal(acc_d.download((nc, *PV), np.uint16), want)
+        np.testing.assert_array_equal(n_d.download(tuple(PV), np.uint16), n_s.download(tuple(PV), np.uint16))
+    finally:
+        for b in bufs + [dvol]:
+            b.free()
+        p.close()
