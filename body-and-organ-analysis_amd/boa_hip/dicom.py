@@ -7,10 +7,10 @@ only -- PARITY UNPINNED vs GDCM / SimpleITK.
 
 Scope (everything else raises, nothing is guessed):
   * transfer syntaxes: implicit VR little endian (1.2.840.10008.1.2), explicit VR little endian (1.2.840.10008.1.2.1),
-    JPEG Lossless Process 14 (1.2.840.10008.1.2.4.57, .70 -- boa_hip/jpeg_lossless.py) and JPEG 2000 holding a reversible
-    5/3 stream (1.2.840.10008.1.2.4.90, .91 -- boa_hip/jpeg2000.py): encapsulated PixelData, one frame per file, the frames
-    of a series decoded on the GPU in one call per codec; other compressed, deflated and big-endian files raise
-    NotImplementedError;
+    JPEG Lossless Process 14 (1.2.840.10008.1.2.4.57, .70 -- boa_hip/jpeg_lossless.py), JPEG 2000 holding a reversible
+    5/3 stream (1.2.840.10008.1.2.4.90, .91 -- boa_hip/jpeg2000.py) and RLE Lossless (1.2.840.10008.1.2.5 --
+    boa_hip/rle_lossless.py): encapsulated PixelData, one frame per file, the frames of a series decoded on the GPU in one
+    call per codec; other compressed (JPEG-LS, lossy JPEG), deflated and big-endian files raise NotImplementedError;
   * single-frame, MONOCHROME2, SamplesPerPixel 1, BitsAllocated 16 (8 and 32 are read too);
   * one series per call: like `GetGDCMSeriesFileNames(dir)` without a series id, the FIRST series (smallest SeriesInstanceUID
     in sorted order) of the folder is taken, other series' files are ignored;
@@ -31,7 +31,7 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
 
-from . import jpeg2000, jpeg_lossless
+from . import jpeg2000, jpeg_lossless, rle_lossless
 
 IMPLICIT_LE = "1.2.840.10008.1.2"
 EXPLICIT_LE = "1.2.840.10008.1.2.1"
@@ -80,6 +80,10 @@ TAGS: Dict[Tuple[int, int], Tuple[str, str]] = {
     (0x7FE0, 0x0010): ("PixelData", "OW"),
 }
 _STRUCT = {"US": "<H", "SS": "<h", "UL": "<I", "SL": "<i", "FL": "<f", "FD": "<d"}
+
+
+# the codec of every encapsulated transfer syntax this reader decodes
+_CODECS = {ts: codec for codec in (jpeg_lossless, jpeg2000, rle_lossless) for ts in codec.SYNTAXES}
 
 
 class DicomError(ValueError):
@@ -186,12 +190,12 @@ def read_file(path, stop_before_pixels: bool = False) -> Dict[str, Any]:
             tsuid = _convert("UI", raw)
     if tsuid is None:
         raise DicomError(f"{path}: no TransferSyntaxUID in the file meta information")
-    if tsuid not in (IMPLICIT_LE, EXPLICIT_LE) + jpeg_lossless.SYNTAXES + jpeg2000.SYNTAXES:
+    if tsuid not in (IMPLICIT_LE, EXPLICIT_LE) and tsuid not in _CODECS:
         raise NotImplementedError(f"{path}: transfer syntax {tsuid} (compressed, deflated or big endian) is not supported; "
-                                  "only implicit / explicit VR little endian (uncompressed), JPEG Lossless (Process 14) "
-                                  "and JPEG 2000 (reversible) are read")
+                                  "only implicit / explicit VR little endian (uncompressed), JPEG Lossless (Process 14), "
+                                  "JPEG 2000 (reversible) and RLE Lossless are read")
     explicit = tsuid != IMPLICIT_LE
-    jpeg = tsuid in jpeg_lossless.SYNTAXES + jpeg2000.SYNTAXES
+    encapsulated = tsuid in _CODECS
     out["TransferSyntaxUID"] = tsuid
     out["_explicit"] = explicit
     want = set(TAGS)
@@ -199,13 +203,19 @@ def read_file(path, stop_before_pixels: bool = False) -> Dict[str, Any]:
         g, e = struct.unpack("<HH", buf[cur.pos:cur.pos + 4])
         if stop_before_pixels and (g, e) >= (0x7FE0, 0x0010):
             break
-        if jpeg and (g, e) == (0x7FE0, 0x0010):     # PS3.5 A.4: encapsulated, undefined length, explicit VR OB / OW
+        if encapsulated and (g, e) == (0x7FE0, 0x0010):     # PS3.5 A.4: encapsulated, undefined length, explicit VR OB / OW
             vr_b = buf[cur.pos + 4:cur.pos + 6]
             length = struct.unpack_from("<I", buf, cur.pos + 8)[0] if cur.pos + 12 <= len(buf) else 0
             if vr_b not in (b"OB", b"OW") or length != 0xFFFFFFFF:
                 raise NotImplementedError(f"{path}: transfer syntax {tsuid} with native (not encapsulated) PixelData is "
                                           "not read")
             frame, cur.pos = jpeg_lossless.read_encapsulated(buf, cur.pos + 12, str(path))
+            # An RLE frame has no signature, and the syntax is also met on files that hold something else: what does not
+            # even start like an RLE header (64 bytes, 1 .. 15 segments, the first at offset 64) is refused here as an
+            # unsupported file; the finer checks of the header are rle_lossless.parse_frame's, when the series is loaded.
+            if tsuid in rle_lossless.SYNTAXES and not rle_lossless.plausible_header(frame):
+                raise NotImplementedError(f"{path}: transfer syntax {tsuid}: PixelData does not start with an RLE header "
+                                          "(64 bytes: a segment count in 1..15, the first segment at offset 64)")
             out["PixelData"] = jpeg_lossless.CompressedFrame(frame)
             out["PixelData"].transfer_syntax = tsuid
             continue
@@ -342,7 +352,7 @@ def _slice_pixels(ds: Dict[str, Any], decoded: Optional[np.ndarray] = None) -> n
 def load_series(folder, ctx=None) -> Tuple[np.ndarray, Dict[str, Any], List[str]]:
     """Folder -> (volume [x, y, z] in the file axis order of the NIfTI that `sitk.WriteImage` would write, geometry, files).
     geometry: LPS `origin` (3), `spacing` (3), `direction` (3 x 3, columns = row-direction / column-direction / slice normal),
-    and the RAS `affine` (4 x 4) of the NIfTI file.  JPEG Lossless and JPEG 2000 slices are decoded on the device in one
+    and the RAS `affine` (4 x 4) of the NIfTI file.  JPEG Lossless, JPEG 2000 and RLE Lossless slices are decoded on the device in one
     batched call per codec (ctx: a device Context; default the process's `compute.inference.get_context()`, used only when
     the series holds such a slice)."""
     files = series_file_names(folder)
@@ -411,7 +421,7 @@ def load_series(folder, ctx=None) -> Tuple[np.ndarray, Dict[str, Any], List[str]
 
 def _decode_compressed(sl: List[Dict[str, Any]], rows: int, cols: int, ctx=None) -> Dict[int, np.ndarray]:
     """{slice index: decoded uint16 samples} of the series' compressed slices: every frame is parsed on the host first (refusals
-    raise before the device is touched), then the frames of each codec (JPEG Lossless, JPEG 2000) are decoded in one device
+    raise before the device is touched), then the frames of each codec (`_CODECS`, by transfer syntax) are decoded in one device
     call per codec."""
     idx = [i for i, d in enumerate(sl) if isinstance(d.get("PixelData"), jpeg_lossless.CompressedFrame)]
     if not idx:
@@ -421,7 +431,7 @@ def _decode_compressed(sl: List[Dict[str, Any]], rows: int, cols: int, ctx=None)
         d = sl[i]
         _pixel_dtype(d)
         alloc = int(d["BitsAllocated"])
-        codec = jpeg2000 if d["PixelData"].transfer_syntax in jpeg2000.SYNTAXES else jpeg_lossless
+        codec = _CODECS[d["PixelData"].transfer_syntax]
         fr = codec.parse_frame(d["PixelData"], rows=rows, cols=cols, bits_allocated=alloc,
                                bits_stored=int(d.get("BitsStored", alloc)), name=d["_path"])
         g = groups.setdefault(codec, ([], []))

@@ -644,6 +644,34 @@ int boa_ljpeg_decode(boa_ctx* ctx, const uint8_t* dev_data, size_t data_bytes, i
 int boa_j2k_decode(boa_ctx* ctx, const uint8_t* dev_data, size_t data_bytes, int n_frames, const int* frames, int n_blocks,
                    const int* blocks, uint16_t* dev_out, int* host_status);
 
+/* ------------------------------------------------------------------ RLE Lossless decode (rle.hip) --- */
+/* DICOM transfer syntax 1.2.840.10008.1.2.5 = PS3.5 Annex G: every byte plane of a frame's samples is one PackBits stream (a
+ * segment), the most significant plane first.  The host reads the 64-byte RLE header of every frame (boa_hip/rle_lossless.py) and
+ * passes, as a HOST array:
+ *   frames  int32 [n_frames][BOA_RLE_FRAME_WORDS]: fields BOA_RLE_F_* (byte offset and length of the frame in dev_data, no
+ *           alignment asked; 1 or 2 segments = 8- or 16-bit samples; per segment its first byte and the byte behind its last,
+ *           relative to the frame); every frame of a batch has rows x cols samples, frames of 1 and of 2 segments may be mixed.
+ * Decoding rule, per segment: control byte c < 128 copies the next c + 1 bytes, c > 128 repeats the next byte 257 - c times,
+ * c == 128 does nothing; the decode stops when rows x cols bytes are produced (a run that crosses that count is clipped, whatever
+ * follows is ignored) or at the first control whose operand bytes are not all inside the segment (it produces nothing); fewer
+ * bytes than rows x cols = BOA_RLE_TRUNCATED for the frame, whose samples are then unspecified.  Runs may cross row ends.
+ * serial = 0: every segment is cut into chunks of chunk_bytes (a power of two in 256 .. 4096); the chunks are mapped, chained and
+ * expanded in parallel (rle.hip); serial = 1: one lane per segment, the plain loop.  Both write byte planes that one more kernel
+ * interleaves into dev_out uint16 [n_frames][rows][cols] (plane 0 = the high byte; a frame of one segment is widened).  Batches
+ * whose workspace (two planes per frame, 129 + 2 words per chunk) would pass 1 GiB (or BOA_RLE_WS_MB MiB, where that
+ * environment variable holds a positive number) are decoded in groups of frames within the call.  Every offset is validated on the host first (BOA_EINVAL); malformed streams are reported per frame in host_status,
+ * never by a fault.  Synchronous. */
+#define BOA_RLE_FRAME_WORDS 8
+#define BOA_RLE_F_OFF_LO 0
+#define BOA_RLE_F_OFF_HI 1
+#define BOA_RLE_F_LEN 2
+#define BOA_RLE_F_N_SEG 3
+#define BOA_RLE_F_SEG 4          /* then [segment][first byte, end byte] */
+#define BOA_RLE_OK 0
+#define BOA_RLE_TRUNCATED 1
+int boa_rle_decode(boa_ctx* ctx, const uint8_t* dev_data, size_t data_bytes, int n_frames, const int* frames, int rows, int cols,
+                   int chunk_bytes, uint16_t* dev_out, int* host_status, int serial);
+
 /* ------------------------------------------------------------------ deflate encoder for label volumes (deflate.hip) --- */
 /* The data body of a .nii.gz label volume as raw deflate streams (RFC 1951), one per gzip member (RFC 1952), encoded on the
  * device.  dev_src: n payload bytes in file order.  The payload is cut into members of member_bytes (1 .. 2^30; the last may be
