@@ -136,6 +136,7 @@ _PROTOS = {
     "boa_ljpeg_decode": (i32, [vp, vp, u64, i32, ip, i32, ip, i32, ip, i32, C.POINTER(C.c_uint32), vp, ip, i32]),
     "boa_j2k_decode": (i32, [vp, vp, u64, i32, ip, i32, ip, vp, ip]),
     "boa_rle_decode": (i32, [vp, vp, u64, i32, ip, i32, i32, i32, vp, ip, i32]),
+    "boa_jls_decode": (i32, [vp, vp, u64, i32, ip, i32, i32, vp, ip, i32]),
     "boa_deflate_bound": (u64, [u64, u64]),
     "boa_deflate_members": (i32, [vp, vp, u64, u64, i32, vp, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]),
     "boa_deflate_members2": (i32, [vp, vp, u64, u64, i32, i32, i32, vp, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]),

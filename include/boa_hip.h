@@ -672,6 +672,41 @@ int boa_j2k_decode(boa_ctx* ctx, const uint8_t* dev_data, size_t data_bytes, int
 int boa_rle_decode(boa_ctx* ctx, const uint8_t* dev_data, size_t data_bytes, int n_frames, const int* frames, int rows, int cols,
                    int chunk_bytes, uint16_t* dev_out, int* host_status, int serial);
 
+/* ------------------------------------------------------------------ JPEG-LS decode (jls.hip) --- */
+/* DICOM transfer syntaxes 1.2.840.10008.1.2.4.80 / .81 = ITU-T T.87, one component, no interleaving, no restart interval, no
+ * mapping table.  The host reads the markers of every frame (boa_hip/jpeg_ls.py) and passes, as a HOST array:
+ *   frames  int32 [n_frames][BOA_JLS_FRAME_WORDS]: fields BOA_JLS_F_* (byte offset, a multiple of 4, and length of the frame's
+ *           scan in dev_data, whose bytes up to the next multiple of 4 behind the scan must lie inside dev_data; the coding
+ *           parameters MAXVAL, NEAR, T1, T2, T3, RESET with the defaults resolved, in the ranges of T.87 C.2.4.1.1); every frame
+ *           of a batch has rows x cols samples, the parameters may differ from frame to frame.
+ * Decoding rule: the scan is read most significant bit first; after a 0xFF byte the next byte carries 7 bits, and a byte >= 0x80
+ * there is a marker that ends the stream; behind the end zero bits are read.  Samples are decoded in raster order as T.87 Annex A
+ * lays down (the first row sees zeros above it; Ra at a row's start is Rb, Rc there is the row above's starting Ra, Rd at a
+ * row's end is Rb; RUNindex persists over the rows; a run that reaches the row's end has no interruption sample).  A Golomb code
+ * with more zeros than its limit allows, a mapped error above RANGE or a run that passes the row's end end the frame with
+ * BOA_JLS_INVALID; a frame whose decoding took a bit from behind the stream's end is BOA_JLS_TRUNCATED instead (also where it
+ * met an invalid code there).  The samples of a failed frame are unspecified; bytes behind the last sample's code are ignored.
+ * serial = 0: one wave per frame (k_jls_wave: the chain on wave-uniform values, the other lanes on what the row above decides,
+ * the run fills and the stores; rows up to BOA_JLS_WAVE_MAX_COLS samples, wider frames take the other path); serial = 1: one
+ * lane per frame, the plain loop (k_jls_serial).  dev_out: uint16 [n_frames][rows][cols].  Every range is validated on the host
+ * first (BOA_EINVAL); malformed scans are reported per frame in host_status, never by a fault.  Synchronous. */
+#define BOA_JLS_FRAME_WORDS 16
+#define BOA_JLS_F_OFF_LO 0
+#define BOA_JLS_F_OFF_HI 1
+#define BOA_JLS_F_LEN 2
+#define BOA_JLS_F_MAXVAL 3
+#define BOA_JLS_F_NEAR 4
+#define BOA_JLS_F_T1 5
+#define BOA_JLS_F_T2 6
+#define BOA_JLS_F_T3 7
+#define BOA_JLS_F_RESET 8
+#define BOA_JLS_WAVE_MAX_COLS 4096
+#define BOA_JLS_OK 0
+#define BOA_JLS_TRUNCATED 1
+#define BOA_JLS_INVALID 2
+int boa_jls_decode(boa_ctx* ctx, const uint8_t* dev_data, size_t data_bytes, int n_frames, const int* frames, int rows, int cols,
+                   uint16_t* dev_out, int* host_status, int serial);
+
 /* ------------------------------------------------------------------ deflate encoder for label volumes (deflate.hip) --- */
 /* The data body of a .nii.gz label volume as raw deflate streams (RFC 1951), one per gzip member (RFC 1952), encoded on the
  * device.  dev_src: n payload bytes in file order.  The payload is cut into members of member_bytes (1 .. 2^30; the last may be
