@@ -1,5 +1,8 @@
 """JPEG 2000 lossless (ITU T.800, reversible 5/3, one component, one tile) for DICOM CT: transfer syntaxes
-1.2.840.10008.1.2.4.90 (lossless only) and 1.2.840.10008.1.2.4.91 (holding a reversible stream).  The reference reads these
+1.2.840.10008.1.2.4.90 (lossless only) and 1.2.840.10008.1.2.4.91 (holding a reversible stream).  A .91 stream may be lossy
+while reversible: its layers stop code blocks before their last coding pass.  Such blocks are reconstructed as OpenJPEG
+reconstructs them (every coefficient at the midpoint of what its undecoded bit-planes leave open), so the pixels equal the
+reference's.  The reference reads these
 series through GDCM / OpenJPEG (BOA/compute/io.py:254-259); here the host parses the codestream and runs tier-2, and tier-1 and
 the inverse wavelet transform of the whole series run in one batched HIP call (csrc/j2k.hip, `boa_j2k_decode`).
 

@@ -1,5 +1,5 @@
-// JPEG 2000 lossless (ITU T.800, reversible 5/3, one component, one tile): tier-1 and the inverse wavelet transform of a batch
-// of frames (the compressed slices of a DICOM series, transfer syntaxes 1.2.840.10008.1.2.4.90 / .91) in one call.
+// JPEG 2000 with the reversible 5/3 transform (ITU T.800, one component, one tile; lossless, or stopped early by its layers):
+// tier-1 and the inverse wavelet transform of a batch of frames (the compressed slices of a DICOM series, transfer syntaxes 1.2.840.10008.1.2.4.90 / .91) in one call.
 //
 // The host (boa_hip/jpeg2000.py) parses the codestream and runs tier-2, and hands over a flat table of code blocks: frame,
 // subband orientation, position and size in the frame's coefficient plane (Mallat layout), number of magnitude bit-planes,
@@ -11,7 +11,10 @@
 // ones, own significance / visited / refined / sign), so that a context is one load; a coefficient that becomes significant
 // updates its neighbours' words.  The words of the blocks are interleaved (word k of the lane's block at k * n_lanes + lane),
 // so that lanes stepping through blocks of one size in lockstep touch neighbouring addresses.  Coefficients are written signed
-// into the frame's int32 plane as they are decoded.  The host orders the blocks by passes x area, longest first.
+// into the frame's int32 plane as they are decoded.  A block whose passes stop before the last bit-plane (a .91 stream with
+// rate- or quality-limited layers) gets one more sweep that moves every significant coefficient to the midpoint of its
+// undecoded planes, so that such streams reconstruct exactly as OpenJPEG reconstructs them; complete blocks skip it.
+// The host orders the blocks by passes x area, longest first.
 // k_j2k_idwt_h / k_j2k_idwt_v: inverse 5/3 lifting (Annex F.3.8, symmetric extension, all origins zero so that every level
 // starts at an even coordinate; a length-1 signal passes through) of one level of every frame, rows then columns (2D_SR);
 // the last column pass of a frame adds the DC level shift, clamps to the sample range (as OpenJPEG does) and writes the uint16
@@ -245,6 +248,22 @@ __global__ void __launch_bounds__(NT_T1) k_j2k_t1(const unsigned char* __restric
             }
         }
     }
+    if (passes == 3 * nbp - 2) return;
+    // A block that stops early (a rate- or quality-limited layer): as OpenJPEG does, a significant coefficient goes to the
+    // midpoint of what its undecoded planes leave open, |v| += 2^(b_last - 1) where b_last >= 1 is the lowest plane at which
+    // it was coded.  After a cleanup or refinement pass at plane bf that is bf for every significant coefficient; after a
+    // significance pass it is bf for those that pass made significant (bit bf of |v| set) and bf + 1 for the others, which
+    // wait for their refinement.  bf + 1 <= nbp - 1, so |v| stays below 2^30.
+    const int pl = passes - 1, kf = pl == 0 ? 2 : (pl - 1) % 3, bf = nbp - 1 - (pl + 2) / 3;
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) {
+            int* v = V + (size_t)y * cols + x;
+            const int t = *v;
+            if (t == 0) continue;
+            const int m = t < 0 ? -t : t;
+            const int bl = kf == 0 && !(m & (1 << bf)) ? bf + 1 : bf;
+            if (bl >= 1) *v = t < 0 ? t - (1 << (bl - 1)) : t + (1 << (bl - 1));
+        }
 }
 
 __device__ __forceinline__ unsigned short j2k_sample(int v, int P, int sgn) {

@@ -615,6 +615,8 @@ int boa_ljpeg_decode(boa_ctx* ctx, const uint8_t* dev_data, size_t data_bytes, i
  * Runs tier-1 of every block in one launch per chunk of frames (chunks keep the workspace below 1 GiB), then the inverse 5/3
  * with the DC level shift, into dev_out uint16 (the sample clamped to its P-bit range, modulo 2^16), and returns the per-frame
  * status (BOA_J2K_OK / _INVALID: a block with more passes than its bit-planes allow, or beyond 30 bit-planes) in host_status.
+ * A block with fewer than 3 x bit-planes - 2 passes (a stream truncated by its layers; none is valid too) is reconstructed as
+ * OpenJPEG does: a significant coefficient coded down to plane b >= 1 gets 2^(b - 1) added to its magnitude (the midpoint).
  * Every field is validated on the host first (BOA_EINVAL); malformed streams are reported per frame, never by a fault.
  * Synchronous. */
 #define BOA_J2K_FRAME_WORDS 12

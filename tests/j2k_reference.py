@@ -138,16 +138,21 @@ class MQ:
         return d
 
 
-def decode_block(data, start, length, w, h, orient, numbps, passes):
-    """One code block -> (int64 [h][w] signed coefficients, ok).  ok False: more passes than bit-planes, or beyond 30 bits."""
+def decode_block(data, start, length, w, h, orient, numbps, passes, with_last=False):
+    """One code block -> (int64 [h][w] signed coefficients, ok).  ok False: more passes than bit-planes, or beyond 30 bits.
+    A block that stops before its last pass (passes < 3 * numbps - 2: a rate- or quality-limited layer) is reconstructed as
+    OpenJPEG does: a significant coefficient whose lowest coded plane b_last (the plane where it became significant or was
+    last refined) is >= 1 lies at the midpoint of what is left open, |v| = m + 2^(b_last - 1); b_last = 0 leaves m.
+    with_last: (coefficients, b_last [h][w], -1 where not significant, ok)."""
     out = np.zeros((h, w), dtype=np.int64)
     if passes == 0:
-        return out, True
+        return (out, out - 1, True) if with_last else (out, True)
     if numbps < 1 or numbps > 30 or passes > 3 * numbps - 2:
-        return out, False
+        return (out, out - 1, False) if with_last else (out, False)
     W2 = w + 2
     F = [0] * (W2 * (h + 2))
     V = [0] * (W2 * (h + 2))
+    B = [-1] * (W2 * (h + 2))                          # lowest plane at which the coefficient was coded
     mq = MQ(data, start, start + length)
     zc = ZC[orient]
     nbr = ((-W2 - 1, 1 << 7, 0), (-W2, 1 << 6, 1 << 11), (-W2 + 1, 1 << 5, 0), (-1, 1 << 4, 1 << 10), (1, 1 << 3, 1 << 9),
@@ -164,7 +169,8 @@ def decode_block(data, start, length, w, h, orient, numbps, passes):
 
     for k in range(passes):
         kind = 2 if k == 0 else (k - 1) % 3            # 0 significance propagation, 1 refinement, 2 cleanup
-        bit = 1 << (numbps - 1 - (k + 2) // 3)
+        plane = numbps - 1 - (k + 2) // 3
+        bit = 1 << plane
         for y0 in range(0, h, 4):
             y1 = min(y0 + 4, h)
             for x in range(w):
@@ -180,6 +186,7 @@ def decode_block(data, start, length, w, h, orient, numbps, passes):
                         neg = sign(i)
                         set_sig(i, neg)
                         V[i] = -bit if neg else bit
+                        B[i] = plane
                         y = y0 + r + 1
                 for yy in range(y, y1):
                     i = (yy + 1) * W2 + x + 1
@@ -190,12 +197,14 @@ def decode_block(data, start, length, w, h, orient, numbps, passes):
                                 neg = sign(i)
                                 set_sig(i, neg)
                                 V[i] = -bit if neg else bit
+                                B[i] = plane
                             F[i] |= VIS
                     elif kind == 1:
                         if f & SIG and not f & VIS:
                             ctx = 16 if f & REF else (15 if f & 0xFF else 14)
                             if mq.decode(ctx):
                                 V[i] += -bit if V[i] < 0 else bit
+                            B[i] = plane
                             F[i] |= REF
                     else:
                         if not f & (SIG | VIS):
@@ -203,9 +212,14 @@ def decode_block(data, start, length, w, h, orient, numbps, passes):
                                 neg = sign(i)
                                 set_sig(i, neg)
                                 V[i] = -bit if neg else bit
+                                B[i] = plane
                         F[i] &= ~VIS
     out[:] = np.asarray(V, dtype=np.int64).reshape(h + 2, W2)[1:-1, 1:-1]
-    return out, True
+    last = np.asarray(B, dtype=np.int64).reshape(h + 2, W2)[1:-1, 1:-1]
+    if passes < 3 * numbps - 2:
+        half = np.where(last >= 1, 1 << np.maximum(last - 1, 0), 0)
+        out += np.sign(out) * half
+    return (out, last, True) if with_last else (out, True)
 
 
 def idwt53_1d(y, axis):
@@ -225,8 +239,8 @@ def idwt53_1d(y, axis):
     return np.moveaxis(X, 0, axis)
 
 
-def decode_frame(fr):
-    """A boa_hip.jpeg2000.Frame -> (uint16 [rows][cols], the sample modulo 2^16 after the clamp to its range; ok)."""
+def reconstruct(fr):
+    """A boa_hip.jpeg2000.Frame -> (int64 [rows][cols], the inverse transform's output before the DC shift and the clamp; ok)."""
     plane = np.zeros((fr.rows, fr.cols), dtype=np.int64)
     data = fr.data
     off, ok = 0, True
@@ -240,6 +254,12 @@ def decode_frame(fr):
         hr, wr = -(-fr.rows >> d), -(-fr.cols >> d)
         reg = idwt53_1d(plane[:hr, :wr], 1)
         plane[:hr, :wr] = idwt53_1d(reg, 0)
+    return plane, ok
+
+
+def decode_frame(fr):
+    """A boa_hip.jpeg2000.Frame -> (uint16 [rows][cols], the sample modulo 2^16 after the clamp to its range; ok)."""
+    plane, ok = reconstruct(fr)
     P = fr.precision
     if fr.signed:
         s = np.clip(plane, -(1 << (P - 1)), (1 << (P - 1)) - 1)

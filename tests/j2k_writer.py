@@ -1,4 +1,4 @@
-"""Test-only JPEG 2000 helpers: lossless codestreams from OpenJPEG through Pillow (where Pillow imports; the GPU tests never
+"""Test-only JPEG 2000 helpers: reversible codestreams (lossless, or truncated by their layers) from OpenJPEG through Pillow (where Pillow imports; the GPU tests never
 import it), signed streams built from unsigned ones, the committed fixtures of tests/golden/j2k, and DICOM slices / series that
 wrap a codestream (ljpeg_writer.write_compressed_slice with a JPEG 2000 transfer syntax)."""
 import glob
@@ -31,7 +31,8 @@ def _ssiz_pos(stream: bytes) -> int:
 
 
 def encode(x, *, jp2=False, **kw) -> bytes:
-    """OpenJPEG (through Pillow) lossless codestream of x: uint8 -> P = 8, uint16 -> P = 16; kw: Pillow's JPEG 2000 options."""
+    """OpenJPEG (through Pillow) reversible codestream of x: uint8 -> P = 8, uint16 -> P = 16; kw: Pillow's JPEG 2000 options
+    (lossless unless quality_layers ends in a layer other than 0)."""
     from PIL import Image
     x = np.ascontiguousarray(x)
     if x.dtype == np.uint8:
@@ -69,8 +70,10 @@ def openjpeg_decode(stream: bytes) -> np.ndarray:
 
 
 def load_fixtures():
-    """The committed fixtures -> list of dicts: name, stream (bytes), source (int64 [rows][cols]), bits, signed."""
+    """The committed fixtures -> list of dicts: name, stream (bytes), source (int64 [rows][cols]), bits, signed; and decoded
+    (int64, OpenJPEG's own decode) for the streams that are not lossless."""
     out = []
+    phantoms = {}
     for path in sorted(glob.glob(os.path.join(FIXTURES, "*.npz"))):
         g = np.load(path)
         for k, m in enumerate(json.loads(str(g["meta"]))):
@@ -79,17 +82,25 @@ def load_fixtures():
             elif "phantom" in m:
                 from boa_hip.synthetic import ct_phantom
                 p = m["phantom"]
-                hu = ct_phantom(tuple(p["shape"]), seed=p["seed"]).transpose(2, 1, 0)[p["z"]]
-                src = hu.astype(np.int64) + p["offset"]
+                key = (tuple(p["shape"]), p["seed"])
+                if key not in phantoms:
+                    phantoms[key] = ct_phantom(key[0], seed=key[1]).transpose(2, 1, 0)
+                src = phantoms[key][p["z"]].astype(np.int64) + p["offset"]
+                if "crop" in p:
+                    y0, x0 = p["crop"]
+                    src = src[y0:y0 + m["rows"], x0:x0 + m["cols"]]
             else:
                 src = g[f"source_{k}"].astype(np.int64)
             out.append(dict(m, stream=g[f"stream_{k}"].tobytes(), source=src, file=os.path.basename(path)))
+            if f"decoded_{k}" in g.files:
+                out[-1]["decoded"] = g[f"decoded_{k}"].astype(np.int64)
     return out
 
 
 def expected(fx):
-    """The uint16 output of the decoder for a fixture: the sample modulo 2^16."""
-    return (np.asarray(fx["source"]).astype(np.int64) & 0xFFFF).astype(np.uint16)
+    """The uint16 output of the decoder for a fixture: the sample modulo 2^16.  The sample is the source for a lossless stream
+    and what OpenJPEG decodes (`decoded`) for a truncated one."""
+    return (np.asarray(fx.get("decoded", fx["source"])).astype(np.int64) & 0xFFFF).astype(np.uint16)
 
 
 def write_slice(path, pixels, stream, *, transfer_syntax=J2K_LOSSLESS, **kw):

@@ -1,6 +1,6 @@
 """JPEG 2000 DICOM input, host side (no device): the codestream parser and tier-2 of boa_hip/jpeg2000.py proven through the
-numpy reference tier-1 / inverse 5/3 (tests/j2k_reference.py) on the committed OpenJPEG fixtures and fresh streams, tile-parts
-and COC / QCC, every refusal by name, malformed streams, and the transfer syntaxes read_file accepts."""
+numpy reference tier-1 / inverse 5/3 (tests/j2k_reference.py) on the committed OpenJPEG fixtures and fresh streams (lossless,
+and truncated reversible ones against OpenJPEG's own decode), the midpoint rule at every pass count, tile-parts and COC / QCC, every refusal by name, malformed streams, and the transfer syntaxes read_file accepts."""
 import struct
 
 import numpy as np
@@ -40,16 +40,25 @@ def _main_header_end(stream):
 
 @pytest.mark.parametrize("fx", FIXTURES, ids=[f["name"] for f in FIXTURES])
 def test_fixture_through_host_tier2_and_reference(fx):
-    fr = _roundtrip(fx["stream"], fx["source"], fx["name"])
+    fr = _roundtrip(fx["stream"], JW.expected(fx), fx["name"])
     assert (fr.precision, fr.signed) == (fx["bits"], fx["signed"])
     assert fr.blocks[:, 6].sum() > 0
+    nbp, passes = fr.blocks[:, 5], fr.blocks[:, 6]
+    early = (passes > 0) & (passes < 3 * nbp - 2)
+    assert early.any() == ("decoded" in fx), fx["name"]   # a truncated fixture stops blocks early, a lossless one never
+    if "decoded" in fx:
+        assert not np.array_equal(fx["decoded"], fx["source"]) and fx["openjpeg"]
+    if "30db" in fx["name"]:
+        assert (passes == 0).any()
 
 
 def test_fixture_coverage():
     names = " ".join(f["name"] for f in FIXTURES)
     for want in ("lrcp", "rlcp", "rpcl", "pcrl", "cprl", "2layers", "3layers", "1res", "8res", "cb4x4", "cb16x64", "cb32",
                  "precincts", "plt_com", "jp2", "1x1", "1x37", "41x1", "40x33", "129x97", "256x256", "512x512", "_s8", "_s16",
-                 "fullrange_noise"):
+                 "fullrange_noise", "ct_trunc_rate10", "ct_trunc_2layers_cb16", "u8_trunc_30db_3res", "s16_1res_trunc",
+                 "s8_random_trunc", "trunc_rpcl_cb4x4_3layers", "1x37_u16_trunc", "41x1_u8_trunc", "u8_saturated_trunc",
+                 "u16_saturated_trunc", "s16_saturated_trunc", "256x256_ct_phantom_crop_trunc_rate8"):
         assert want in names, want
 
 
@@ -67,6 +76,73 @@ def test_fresh_pillow_streams():
         s = JW.stream_of(x, bits, signed, **kw)
         np.testing.assert_array_equal(JW.openjpeg_decode(s), x)
         _roundtrip(s, x, f"fresh{k}")
+    # truncated reversible streams (rate- or quality-limited layers): bit-equal to OpenJPEG's own decode
+    yy, xx = np.meshgrid(np.arange(129), np.arange(129), indexing="ij")
+    layer_options = [dict(quality_layers=[10], quality_mode="rates"),
+                     dict(quality_layers=[40, 10], quality_mode="rates", codeblock_size=(16, 16)),
+                     dict(quality_layers=[30], quality_mode="dB", num_resolutions=3),
+                     dict(quality_layers=[20, 8, 4], quality_mode="rates", codeblock_size=(4, 4), progression="RPCL"),
+                     dict(quality_layers=[45, 35], quality_mode="dB", codeblock_size=(64, 64)),
+                     dict(quality_layers=[5], quality_mode="rates", progression="PCRL", num_resolutions=3)]
+    tried = refused = lossy = 0
+    for shape in ((5, 7), (23, 58), (40, 33), (97, 129)):
+        for bits in (8, 16):
+            full = (1 << bits) - 1
+            body = np.hypot(yy[:shape[0], :shape[1]] - shape[0] / 2, xx[:shape[0], :shape[1]] - shape[1] / 2) < 0.4 * max(shape)
+            contents = [np.clip(np.round(full / 64 + body * (full / 60 + rng.normal(0, full / 4000 + 1, shape))), 0, full),
+                        rng.integers(0, full + 1, shape), rng.integers(0, 2, shape) * full]      # CT-like, noise, saturated
+            for signed in (False, True):
+                for c, u in enumerate(contents):
+                    x = u.astype(np.int64) - ((1 << (bits - 1)) if signed else 0)
+                    for o, kw in enumerate(layer_options):
+                        name = f"trunc {shape} {bits} bits signed {signed} content {c} options {o}"
+                        tried += 1
+                        try:
+                            s = JW.stream_of(x, bits, signed, **kw)
+                        except OSError:                 # Pillow itself refuses some option sets on tiny images
+                            refused += 1
+                            continue
+                        want = JW.openjpeg_decode(s)
+                        lossy += not np.array_equal(want, x)
+                        _roundtrip(s, want, name)
+    print(f"truncated sweep: {tried} tried, {refused} refused by Pillow, {lossy} not lossless")
+    assert tried == 288 and refused * 8 <= tried, (tried, refused)
+    assert lossy * 8 >= 7 * (tried - refused), (lossy, tried, refused)     # the sweep is about truncation: most are lossy
+
+
+def test_every_pass_count_keeps_the_decoded_bits_and_holds_the_midpoint():
+    """No OpenJPEG here: every block of a lossless fixture decoded with its first P passes, P = 0 .. its own count.  Where a
+    coefficient was coded down to plane b_last, the bits at and above b_last are those of the full decode, and the bits below
+    are the midpoint 2^(b_last - 1) (nothing for b_last = 0); the full count gives the full decode."""
+    fx = _small("40x33_u8_lrcp_2layers")
+    fr = _parse(fx["stream"], *fx["source"].shape)
+    off = 0
+    seen = set()
+    for o, x0, y0, w, h, nbp, own, ln in fr.blocks.tolist():
+        assert own == 3 * nbp - 2 or own == 0
+        full, last_full, ok = R.decode_block(fr.data, off, ln, w, h, o, nbp, own, with_last=True)
+        assert ok and ((last_full == 0) == (full != 0)).all() and ((last_full == -1) == (full == 0)).all()
+        for P in range(own + 1):
+            v, last, ok = R.decode_block(fr.data, off, ln, w, h, o, nbp, P, with_last=True)
+            assert ok
+            if P == own:
+                np.testing.assert_array_equal(v, full)
+                continue
+            if P == 0:
+                assert not v.any()
+                continue
+            kind, bf = (2 if P == 1 else (P - 2) % 3), nbp - 1 - (P + 1) // 3
+            seen.add((kind, bf >= 1))
+            sig = last >= 0
+            assert not v[~sig].any()
+            assert sig[np.abs(full) >> (bf + 1) != 0].all()            # significant above plane bf: coded by now
+            assert ((last[sig] == bf) | ((last[sig] == bf + 1) & (kind == 0))).all()
+            b, m, mf = last[sig], np.abs(v[sig]), np.abs(full[sig])
+            np.testing.assert_array_equal(np.sign(v[sig]), np.sign(full[sig]))
+            np.testing.assert_array_equal(m >> b, mf >> b)
+            np.testing.assert_array_equal(m & ((1 << b) - 1), np.where(b >= 1, 1 << np.maximum(b - 1, 0), 0))
+        off += ln
+    assert seen == {(k, hi) for k in (0, 1, 2) for hi in (False, True)} - {(2, False)}
 
 
 def _split_tile_parts(stream, cut, last_psot_zero=False):

@@ -1,12 +1,15 @@
-"""JPEG 2000 lossless DICOM series decoded on the device (csrc/j2k.hip): the committed OpenJPEG fixtures (tests/golden/j2k)
-decoded bit-exactly, alone and in one mixed batch, per-frame errors, get_image_info on J2K series against the uncompressed
+"""JPEG 2000 DICOM series decoded on the device (csrc/j2k.hip): the committed OpenJPEG fixtures (tests/golden/j2k) decoded
+bit-exactly, alone and in one mixed batch (lossless ones to their sources, truncated reversible ones to OpenJPEG's own decode),
+blocks cut at every pass count against the numpy model, the clamp at both range ends, per-frame errors, get_image_info on J2K series against the uncompressed
 series of the same pixels, a series mixing JPEG Lossless and JPEG 2000 slices, and a 512 x 512 x 600 series.  No Pillow here:
 only the committed fixtures are read."""
+import dataclasses
 import os
 
 import numpy as np
 import pytest
 
+import j2k_reference as R
 import j2k_writer as JW
 import ljpeg_writer as LW
 from dicom_writer import write_series
@@ -44,8 +47,8 @@ def test_every_fixture_alone(ctx, fixtures):
 
 
 def test_all_geometries_in_one_call(ctx, fixtures):
-    """Every fixture (1x1 to 512x512, 8 and 16 bits, signed, 1-8 resolutions) in one boa_j2k_decode call, twice over in a
-    shuffled order."""
+    """Every fixture (1x1 to 512x512, 8 and 16 bits, signed, 1-8 resolutions, lossless and truncated) in one boa_j2k_decode
+    call, twice over in a shuffled order."""
     from boa_hip import jpeg2000 as J
     order = np.random.default_rng(0).permutation(2 * len(fixtures)) % len(fixtures)
     frames = [_frame(fixtures[i], name=f"{fixtures[i]['name']}#{k}") for k, i in enumerate(order)]
@@ -53,6 +56,43 @@ def test_all_geometries_in_one_call(ctx, fixtures):
     assert (st == 0).all(), st
     for i, got in zip(order, px):
         np.testing.assert_array_equal(got, JW.expected(fixtures[i]), err_msg=fixtures[i]["name"])
+
+
+@pytest.mark.parametrize("name", ["40x33_u8_lrcp_2layers", "40x33_s8_random"])
+def test_every_pass_count_equals_the_model(ctx, fixtures, name):
+    """One frame per P = 0 .. the most passes of a block, every block cut to its first min(P, own) passes, all in one call:
+    every kind of last pass at every plane.  The numpy model keeps each coefficient's lowest coded plane; the kernel infers it
+    from the last pass."""
+    from boa_hip import jpeg2000 as J
+    fr = _frame(_by_name(fixtures, name))
+    own = fr.blocks[:, 6]
+    assert (own[own > 0] == 3 * fr.blocks[own > 0, 5] - 2).all()         # a lossless fixture: every block complete
+    frames = []
+    for P in range(int(own.max()) + 1):
+        b = fr.blocks.copy()
+        b[:, 6] = np.minimum(P, own)
+        frames.append(dataclasses.replace(fr, blocks=b, name=f"{name}#P{P}"))
+    px, st = J.decode_frames(ctx, frames)
+    assert (st == 0).all(), st
+    want = [R.decode_frame(f) for f in frames]
+    assert all(ok for _, ok in want)
+    for P, (got, (w, _)) in enumerate(zip(px, want)):
+        np.testing.assert_array_equal(got, w, err_msg=f"{name}: {P} passes")
+    np.testing.assert_array_equal(px[-1], JW.expected(_by_name(fixtures, name)))
+    assert len({w.tobytes() for w, _ in want}) > len(want) // 2         # (the cut frames really differ from one another)
+
+
+def test_saturated_truncated_frames_clamp_at_both_ends(ctx, fixtures):
+    from boa_hip import jpeg2000 as J
+    sat = [f for f in fixtures if "saturated" in f["name"]]
+    assert sorted((f["bits"], f["signed"]) for f in sat) == [(8, False), (16, False), (16, True)]
+    px, st = J.decode_frames(ctx, [_frame(f) for f in sat])
+    assert (st == 0).all(), st
+    for fx, got in zip(sat, px):
+        P = fx["bits"]
+        lo, hi = (-(1 << (P - 1)), (1 << (P - 1)) - 1) if fx["signed"] else (0, (1 << P) - 1)
+        assert fx["decoded"].min() == lo and fx["decoded"].max() == hi, fx["name"]
+        np.testing.assert_array_equal(got, JW.expected(fx), err_msg=fx["name"])
 
 
 def test_malformed_frame_reports_and_next_batch_decodes(ctx, fixtures):
@@ -107,6 +147,31 @@ def test_get_image_info_j2k_equals_uncompressed(ctx, fixtures, tmp_path, name, s
     kw = dict(signed=signed_pr, intercept=0 if signed_pr else -1024)
     write_series(tmp_path / "raw", stored, **kw)
     JW.write_series(tmp_path / "j2k", stored, [fx["stream"]] * n, transfer_syntax=syntax, **kw)
+    p_raw, info_raw = get_image_info(tmp_path / "raw", tmp_path / "o_raw")
+    p_j2k, info_j2k = get_image_info(tmp_path / "j2k", tmp_path / "o_j2k")
+    d_raw, a_raw, _ = nifti.load(p_raw)
+    d_j2k, a_j2k, _ = nifti.load(p_j2k)
+    assert d_raw.dtype == d_j2k.dtype
+    np.testing.assert_array_equal(d_j2k, d_raw)
+    np.testing.assert_array_equal(a_j2k, a_raw)
+    np.testing.assert_array_equal(d_raw.transpose(2, 1, 0), stored + (0 if signed_pr else -1024))
+    assert info_raw == info_j2k
+
+
+@pytest.mark.parametrize("names,signed_pr", [(("129x97_u16_ct_trunc_rate10", "129x97_u16_ct_trunc_2layers_cb16"), False),
+                                             (("64x64_s16_1res_trunc",), True)])
+def test_get_image_info_truncated_j2k_equals_openjpeg_pixels(ctx, fixtures, tmp_path, names, signed_pr):
+    """A .91 series of truncated reversible streams reads as the uncompressed series that holds OpenJPEG's decoded pixels."""
+    from boa_hip import nifti
+    from boa_hip.compute.io import get_image_info
+    fxs = [_by_name(fixtures, n) for n in names]
+    assert all(f["signed"] == signed_pr and "decoded" in f for f in fxs)
+    n = 12
+    stored = np.stack([fxs[z % len(fxs)]["decoded"] for z in range(n)]).astype(np.int64)
+    assert any(not np.array_equal(f["decoded"], f["source"]) for f in fxs)
+    kw = dict(signed=signed_pr, intercept=0 if signed_pr else -1024)
+    write_series(tmp_path / "raw", stored, **kw)
+    JW.write_series(tmp_path / "j2k", stored, [fxs[z % len(fxs)]["stream"] for z in range(n)], transfer_syntax=JW.J2K, **kw)
     p_raw, info_raw = get_image_info(tmp_path / "raw", tmp_path / "o_raw")
     p_j2k, info_j2k = get_image_info(tmp_path / "j2k", tmp_path / "o_j2k")
     d_raw, a_raw, _ = nifti.load(p_raw)
