@@ -133,7 +133,7 @@ class DevArray:
         return a.buf.download(a.shape, a.dtype)
 
     def nonzero_bbox(self):
-        """[[lo, hi], ...] of data != 0 (contiguous int16 / int32 / float32 arrays)."""
+        """[[lo, hi], ...] of data != 0 (contiguous uint8 / int16 / int32 / float32 arrays; float64 is not supported)."""
         if not self.is_contiguous:
             raise ValueError("nonzero_bbox: contiguous array required")
         bb = (C.c_int * 6)()

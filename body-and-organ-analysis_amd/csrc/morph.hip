@@ -366,6 +366,7 @@ static int copy3_out(boa_ctx* c, const void* in, long long in_off, const long lo
                 default: boa_set_error("boa_copy3: out dtype %d", out_dtype); return BOA_EINVAL;
             }
 #undef LAUNCH_T
+            c->counters[BOA_CNT_COPY_T]++;
             return BOA_OK;
         }
     }
@@ -502,6 +503,7 @@ extern "C" int boa_nonzero_bbox(boa_ctx* c, const void* dev_in, int dtype, const
             case 3: hipLaunchKernelGGL(k_nonzero_bbox<float>, dim3(grid), dim3(256), 0, c->stream, (const float*)dev_in, dims[0], dims[1], dims[2], d_bb, vec); break;
             default: boa_free(c, d_bb); boa_set_error("boa_nonzero_bbox: dtype %d (0 uint8, 1 int16, 2 int32, 3 float32)", dtype); return BOA_EINVAL;
         }
+        if (vec) c->counters[BOA_CNT_BBOX_VEC]++;
     }
     int bb[6];
     hipError_t e = hipMemcpyAsync(bb, d_bb, sizeof(bb), hipMemcpyDeviceToHost, c->stream);
