@@ -13,6 +13,7 @@ BOA_OK, BOA_EINVAL, BOA_EHIP, BOA_ENOMEM, BOA_EINF = 0, -1, -2, -3, -4
 BOA_DEFLATE_DYNAMIC = 1     # flags of boa_deflate_members2
 BOA_INF_INFO_WORDS, BOA_INF_MS_WORDS = 8, 8     # boa_inflate_streams: host_info (chunks, candidates, rejected, rounds, live), host_ms
 BOA_INF_STATUS = ("ok", "truncated", "invalid", "far", "overrun", "size", "crc", "repair", "trailing")
+BOA_PLAN_WORDS = 32
 K_CONV_MFMA, K_CONV_FIRST, K_CONVT, K_NORM_FINALIZE, K_HEAD_ACCUM, K_ARGMAX, K_OTHER, K_AGG, K_MORPH, K_RESAMPLE, K_COPY, K_COUNT = range(12)
 K_NAMES = ["conv_mfma", "conv_first", "convT_mfma", "norm_finalize", "head_accum", "finalize_argmax", "other", "aggregation",
            "morphology", "resample", "copy_remap"]
@@ -85,6 +86,10 @@ _PROTOS = {
     "boa_net_predict_labels_fold": (i32, [vp, vp, ip, ip, ip, ip, i32, vp, vp, i32, i32, vp, i32, vp, ip, ip, vp]),
     "boa_conv_block_test": (i32, [vp, vp, i32, i32, ip, vp, vp, vp, vp, i32, ip, ip, i32, i32, vp]),
     "boa_convtranspose_test": (i32, [vp, vp, i32, i32, ip, vp, vp, i32, ip, vp]),
+    "boa_conv_plan": (i32, [i32, i32, ip, i32, ip, ip, i32, i32, ip, ip]),
+    "boa_convt_plan": (i32, [i32, ip, i32, ip, i32, i32, i32, ip]),
+    "boa_conv_layer_test": (i32, [vp, i32, i32, ip, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, ip, ip, ip, vp, vp, vp, vp, ip]),
+    "boa_convt_layer_test": (i32, [vp, i32, i32, ip, vp, i32, vp, vp, vp, vp, i32, ip, vp, ip]),
     "boa_tissue_aggregate": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
     "boa_slice_label_presence": (i32, [vp, vp, i32, i32, i32, vp]),
     "boa_tissue_projections": (i32, [vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, vp, vp]),

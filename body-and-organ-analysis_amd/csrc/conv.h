@@ -36,6 +36,8 @@ struct ConvTile {
 
 // ---- conv.hip: weight packers, tile selection, the variant-0 conv, InstanceNorm finalize (layout helpers: end of this file) ----------
 bool choose_conv_tile(const ConvGeom& g, int cu_count, ConvTile* out, bool x3 = false);
+// h, xs, tiles and lds_bytes of a candidate (variant 0 / 1, R, w, b); false where choose_conv_tile would skip it
+bool conv_tile_complete(const ConvGeom& g, bool x3, ConvTile* t, long long* hv_out = nullptr);
 
 // packed weight sizes / packers (host side)
 size_t conv_wpk_halves(int Cin_total, int Cout, const int k[3]);
@@ -74,6 +76,12 @@ int launch_norm_finalize(boa_ctx* ctx, float* partials, int nblk, int N, int C, 
 // k_convt_x3<MT>
 bool first_mfma_ok(int Cin, const int P[3], const int k[3], int Cout);
 bool conv_ws_row_reuse(int R, int k1, int s1, int w1, int b1, int b2);
+// k_conv_ws: the cout chunk as the fastest tile index (c_units: the input channels in the kernel's 2-byte units, both sources)
+bool conv_ws_cy_fast(int c_units, int Cout, int R);
+bool conv_ws_supported(const int k[3], int HV);
+bool conv_ws_resident(int HV, int taps, int ncc, int Cout);
+int conv_ws_vw(int tiles_per_sample, int cu_count);
+int conv_ns_wn(int Cout);
 int convt_mfma_form(int Cin, const int s[3], bool norm_src);
 int convt_x3_mt(size_t vin);
 
@@ -219,6 +227,7 @@ int launch_head_x3(boa_ctx* ctx, const float* act, const float* ss, int F0, cons
                    float slope, float* logits_out, const uint16_t* gauss, uint16_t* acc, uint16_t* nacc, const int PV[3], const int start[3],
                    size_t plane_stride);
 int launch_octet_to_nchw_f32(boa_ctx* ctx, const float* in, const float* ss, float slope, int C, size_t vox, float* out);
+int launch_nchw_to_octet_f32(boa_ctx* ctx, const float* in, int N, int C, size_t vox, float* out);
 
 int launch_ndhwc32_to_nchw_f32(boa_ctx* ctx, const float* in, const float* ss, float slope, int C, size_t vox, float* out);
 

@@ -127,6 +127,42 @@ size_t conv_ws_lds_bytes(int HV, int taps, int ncc, int Cout);
 bool conv_ws_supported(const int k[3], int HV);
 bool conv_ws_resident(int HV, int taps, int ncc, int Cout);
 
+// Completes a candidate (variant 0 / 1, R, w, b) for the geometry: halo h, padded plane stride xs, block tiles per axis and the LDS
+// bytes; *hv_out = the halo voxels the kernel stages (variant 1: the padded planes).  false: the kernel does not take the candidate
+// (conv_ws_supported, the LDS limit).  Shared by choose_conv_tile's search and the plan query / plan override of the test seams
+// (net_debug.hip), so that an overridden plan is completed and refused exactly as the search would.
+bool conv_tile_complete(const ConvGeom& g, bool x3, ConvTile* t, long long* hv_out) {
+    const int dims[3] = {g.Do, g.Ho, g.Wo};
+    const int taps = g.k[0] * g.k[1] * g.k[2];
+    const int ncc = x3 ? g.Cin / 8 : g.Cin / 16;
+    const int variant = t->variant;
+    const int* w = t->w;
+    int* h = t->h;
+    long long HV = 1;
+    for (int d = 0; d < 3; ++d) {
+        const int ext = t->b[d] * w[d];
+        h[d] = (ext - 1) * g.s[d] + g.k[d];
+        t->tiles[d] = ceil_div(dims[d], ext);
+        HV *= h[d];
+    }
+    // k_conv_ws, M-tiles that span several x-planes (w0 > 1, rows of w2 = 8 / 16 lanes: the 16^3 ... 4^3 layers):
+    // lane row lx sits xs voxels = xs * 16 bytes behind row lx - 1, and with xs = h1 * h2 (180 / 100 at the 16^3 / 8^3
+    // layers: = 64 bytes mod 256) the rows of a ds_read_b128 lane group overlapped on the banks -- 35 - 44 % of these
+    // launches' LDS cycles were conflicts (profiles/r05_pmc_lds.txt).  The planes are padded to xs = w2 (mod 16): the
+    // rows of every lane group then tile a 256-byte bank row.  HV below counts the padded planes.
+    int xs = h[1] * h[2];
+    if (variant == 1 && w[0] > 1 && w[1] == 1 && w[2] >= 8 && w[2] <= 16 && g.s[0] == 1 && g.s[2] == 1)
+        while (xs % 16 != w[2] % 16) ++xs;
+    if (variant == 1) HV = (long long)h[0] * xs;
+    if (variant == 1 && !conv_ws_supported(g.k, (int)HV)) return false;
+    const size_t lds = variant == 1 ? conv_ws_lds_bytes((int)HV, taps, ncc, g.Cout) : conv_lds_bytes((int)HV, taps);
+    if (lds > 160 * 1024 - 2048) return false;   // (2 KiB stay free for the split-precision kernel's bias table)
+    t->xs = xs;
+    t->lds_bytes = lds;
+    if (hv_out) *hv_out = HV;
+    return true;
+}
+
 // Pick the wave M-tile shape, the block tile and the kernel variant.  Cost model (cycles per 32-voxel M-tile):
 //   variant 1 (k_conv_ws): chunk time = max(MFMA time of the consumers, staging time of the producers) + barrier;
 //   variant 0 (k_conv_mfma): MFMA and staging serialised inside a block, partly hidden by the second block on the CU.
@@ -159,29 +195,23 @@ bool choose_conv_tile(const ConvGeom& g, int cu_count, ConvTile* out, bool x3) {
                             const int b2 = M / (b0 * b1);
                             if (b0 * b1 * b2 != M) continue;
                             const int b[3] = {b0, b1, b2};
-                            int h[3], tl[3];
-                            long long HV = 1, covered = 1, tiles = 1;
+                            ConvTile c;
+                            c.variant = variant;
+                            c.R = R;
                             for (int d = 0; d < 3; ++d) {
-                                const int ext = b[d] * w[d];
-                                h[d] = (ext - 1) * g.s[d] + g.k[d];
-                                tl[d] = ceil_div(dims[d], ext);
-                                HV *= h[d];
-                                covered *= (long long)tl[d] * ext;
+                                c.w[d] = w[d];
+                                c.b[d] = b[d];
+                            }
+                            long long HV;
+                            if (!conv_tile_complete(g, x3, &c, &HV)) continue;
+                            const int* h = c.h;
+                            const int* tl = c.tiles;
+                            const size_t lds = c.lds_bytes;
+                            long long covered = 1, tiles = 1;
+                            for (int d = 0; d < 3; ++d) {
+                                covered *= (long long)tl[d] * b[d] * w[d];
                                 tiles *= tl[d];
                             }
-                            // k_conv_ws, M-tiles that span several x-planes (w0 > 1, rows of w2 = 8 / 16 lanes: the 16^3 ... 4^3 layers):
-                            // lane row lx sits xs voxels = xs * 16 bytes behind row lx - 1, and with xs = h1 * h2 (180 / 100 at the 16^3 / 8^3
-                            // layers: = 64 bytes mod 256) the rows of a ds_read_b128 lane group overlapped on the banks -- 35 - 44 % of these
-                            // launches' LDS cycles were conflicts (profiles/r05_pmc_lds.txt).  The planes are padded to xs = w2 (mod 16): the
-                            // rows of every lane group then tile a 256-byte bank row.  HV below counts the padded planes.
-                            int xs = h[1] * h[2];
-                            if (variant == 1 && w0 > 1 && w1 == 1 && w2 >= 8 && w2 <= 16 && g.s[0] == 1 && g.s[2] == 1)
-                                while (xs % 16 != w2 % 16) ++xs;
-                            if (variant == 1) HV = (long long)h[0] * xs;
-                            if (variant == 1 && !conv_ws_supported(g.k, (int)HV)) continue;
-                            const size_t lds = variant == 1 ? conv_ws_lds_bytes((int)HV, taps, ncc, g.Cout)
-                                                            : conv_lds_bytes((int)HV, taps);
-                            if (lds > 160 * 1024 - 2048) continue;   // (2 KiB stay free for the split-precision kernel's bias table)
                             const long long nblocks = tiles * (g.Cout / 32) * g.N;
                             const double valid = (double)dims[0] * dims[1] * dims[2];
                             const double waste = (double)covered / valid;
@@ -211,16 +241,7 @@ bool choose_conv_tile(const ConvGeom& g, int cu_count, ConvTile* out, bool x3) {
                             if (cost < best_cost) {
                                 best_cost = cost;
                                 found = true;
-                                out->variant = variant;
-                                out->R = R;
-                                for (int d = 0; d < 3; ++d) {
-                                    out->w[d] = w[d];
-                                    out->b[d] = b[d];
-                                    out->h[d] = h[d];
-                                    out->tiles[d] = tl[d];
-                                }
-                                out->lds_bytes = lds;
-                                out->xs = xs;
+                                *out = c;
                             }
                         }
                 }

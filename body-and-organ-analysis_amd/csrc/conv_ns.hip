@@ -576,6 +576,7 @@ bool conv_ns_applicable(const ConvGeom& g) {
 
 // consumer waves along the cout axis: four when the layer has four or more cout chunks, else two (Cout = 64 / 96)
 static int ns_wn(int Cout) { return Cout >= 128 ? 4 : 2; }
+int conv_ns_wn(int Cout) { return ns_wn(Cout); }
 
 void conv_ns_tile(const ConvGeom& g, ConvTile* t) {
     t->variant = 2;

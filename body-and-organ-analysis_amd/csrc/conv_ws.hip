@@ -877,6 +877,9 @@ bool conv_ws_row_reuse(int R, int k1, int s1, int w1, int b1, int b2) {
     return R > 1 && k1 == 3 && s1 == 1 && w1 == 1 && b2 == 1 && b1 % R == 0;
 }
 
+// the 32 -> 64, R = 1 layer: two cout chunks of a spatial tile run back to back on one halo (2-chunk inputs)
+bool conv_ws_cy_fast(int c_units, int Cout, int R) { return c_units == 32 && Cout == 64 && R == 1; }
+
 template <int R, int K0, int K1, int K2, bool X3>
 static void launch_ws_t(boa_ctx* ctx, const ConvArgs& a, const ConvTile& t, int total, int grid, int resident, const int* desc, int desc_row) {
     // row reuse: the R M-tiles of a wave are consecutive output rows (m = cw * R + r, my = m & (b1 - 1) when b2 == 1),
@@ -1019,7 +1022,7 @@ int launch_conv_ws(boa_ctx* ctx, const ConvArgs& a_in, const ConvTile& t, double
     a.vstep_n = grid / vw;
     a.vstep_j = grid % vw;
     a.ncy = a.Cout / 32;
-    a.cy_fast = ((a.C0 + a.C1) == 32 && a.Cout == 64 && t.R == 1) ? 1 : 0;
+    a.cy_fast = conv_ws_cy_fast(a.C0 + a.C1, a.Cout, t.R) ? 1 : 0;
     a.runs = ws_run_table(ctx, a, total, vw);
     BOA_REQUIRE(a.runs != nullptr, "conv_ws: could not allocate the run table");
     const int* desc = nullptr;

@@ -301,3 +301,20 @@ int launch_octet_to_nchw_f32(boa_ctx* ctx, const float* in, const float* ss, flo
     BOA_HIP_TRY(hipGetLastError());
     return BOA_OK;
 }
+
+// PyTorch [N][C][vox] fp32 -> the split-precision mode's octet planes [N][C/8][vox][8] (test seams: the inverse of the above)
+static __global__ void k_nchw_to_octet_f32(const float* __restrict__ in, int C, size_t vox, float* __restrict__ out) {
+    const int n = blockIdx.y;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;  // over C * vox in the output order
+    if (i >= vox * C) return;
+    const int j = (int)(i % 8);
+    const size_t v = (i / 8) % vox;
+    const int c = (int)(i / (8 * vox)) * 8 + j;
+    out[(size_t)n * vox * C + i] = in[((size_t)n * C + c) * vox + v];
+}
+
+int launch_nchw_to_octet_f32(boa_ctx* ctx, const float* in, int N, int C, size_t vox, float* out) {
+    hipLaunchKernelGGL(k_nchw_to_octet_f32, dim3((unsigned)((vox * C + 255) / 256), N), dim3(256), 0, ctx->stream, in, C, vox, out);
+    BOA_HIP_TRY(hipGetLastError());
+    return BOA_OK;
+}

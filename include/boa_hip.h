@@ -314,6 +314,35 @@ int boa_head_tile(boa_ctx* ctx, const uint16_t* dev_act, const float* dev_ss, in
 int boa_convtranspose_test(boa_ctx* ctx, const float* dev_in, int N, int Cin, const int dims[3],
                            const float* host_w, const float* host_b, int Cout, const int stride[3], float* dev_out);
 
+/* Host-only plan query (no GPU touched, no context): everything that selects code for one conv / transposed conv of a network, from
+ * the functions the network set-up and the launchers call.  mode: 0 = fp16, 2 = split precision.  plan_override (may be NULL):
+ * {variant, R, w[3], b[3]} instead of the planner's choice, completed and checked as the planner's candidates are (BOA_EINVAL where
+ * the planner would skip it).  plan_out: int[BOA_PLAN_WORDS]
+ *   conv : 0 variant (0 k_conv_mfma, 1 k_conv_ws, 2 k_conv_ns), 1 R, 2-4 w, 5-7 b, 8-10 h, 11 xs, 12-14 tiles, 15 lds_bytes, 16 row reuse,
+ *          17 resident weights, 18 cy_fast, 19 vw, 20 nslots, 21 cout waves of k_conv_ns, 22 cout groups per spatial tile, 23 nblk (the
+ *          statistics slots per (n, cout): the partials table holds [N][Cout][2][nblk] floats), 24-26 output dims, 27 BOA_LK_*, 28 split
+ *   convT: 0 convt_mfma_form (-1: split precision), 1 MT of k_convt_x3, 2 BOA_LK_*, 3 stride of the last axis, 4 Cin / 16, 5-7 output dims */
+#define BOA_PLAN_WORDS 32
+int boa_conv_plan(int Cin0, int Cin1, const int dims[3], int Cout, const int kernel[3], const int stride[3], int cu_count, int mode,
+                  const int* plan_override, int* plan_out);
+int boa_convt_plan(int Cin, const int dims[3], int Cout, const int stride[3], int cu_count, int mode, int norm_src, int* plan_out);
+/* Unit-test seams: ONE layer launched as the network launches it (production packers, launch_conv_mfma / launch_conv_x3 +
+ * launch_norm_finalize, launch_convt_mfma / launch_convt_x3), with the plan of boa_conv_plan for the context's CU count.
+ *   sources   dev fp32 [N][C][D][H][W], converted to the mode's layout (fp16 chunk planes / fp32 octet planes); per source the
+ *             producer's tables or NULL (raw source): dev_ss fp32 [N][C][2], and for the fp16 mode dev_ss16 [N][C/2][2] packed words
+ *   dev_raw   the kernel's own output buffer in the mode's layout: fp16 [N][Cout/16][vox][16] / fp32 [N][Cout/8][vox][8]
+ *   dev_ss [N][Cout][2], dev_ss16 [N][Cout] words (fp16 mode, else NULL), dev_partials [N][Cout][2][nblk] floats, ZEROED by the caller
+ *   host_plan (may be NULL) int[BOA_PLAN_WORDS]: the plan that ran
+ * boa_convt_layer_test, fp16 mode: dev_ss without dev_ss16 runs k_convt_mfma's fp32-table transform (the network always passes both) */
+int boa_conv_layer_test(boa_ctx* ctx, int mode, int N, const int dims[3], const float* dev_src0, int C0, const float* dev_ss0,
+                        const uint32_t* dev_ss16_0, const float* dev_src1, int C1, const float* dev_ss1, const uint32_t* dev_ss16_1,
+                        const float* host_w, const float* host_b, const float* host_gamma, const float* host_beta, int Cout,
+                        const int kernel[3], const int stride[3], const int* plan_override, void* dev_raw, float* dev_ss,
+                        uint32_t* dev_ss16, float* dev_partials, int* host_plan);
+int boa_convt_layer_test(boa_ctx* ctx, int mode, int N, const int dims[3], const float* dev_src, int Cin, const float* dev_ss,
+                         const uint32_t* dev_ss16, const float* host_w, const float* host_b, int Cout, const int stride[3], void* dev_raw,
+                         int* host_plan);
+
 /* ------------------------------------------------------------------ body-composition / HU aggregation - */
 /* subclassify_tissues (BCA/tissue/subclassification.py:38-53, rules BCA/tissue/definition.py:6-30) fused with
  * the slice-wise voxel counts of Builder.prepare (BCA/report/builder.py:403-444) and the per-slice HU sums that

@@ -240,6 +240,31 @@ def norm_reference(raw: np.ndarray, gamma: np.ndarray, beta: np.ndarray, eps: fl
     return np.stack([scale, shift], 1), mean, var
 
 
+# InstanceNorm (scale, shift): the statistics are fp32 partial sums of (c, c^2) per conv-epilogue slot, reduced in fp64;
+# var = E[c^2] - mean^2 amplifies the relative error eps_s of E[c^2] by E[c^2] / var = 1 + mean^2 / var, and scale = gamma / sqrt(var
+# + eps) halves it: |d scale| / scale <= SS_EPS * (1 + mean^2 / var) / 2 + 2^-24 (its fp32 rounding).  SS_EPS = the relative error
+# of an fp32-accumulated sum of positive terms (measured on MI355X: see DESIGN section 3).  The fp16 mode's statistics are
+# those of the fp32 epilogue values, the stored raw output is their fp16 rounding: + 2^-11 / sqrt(n) of the rms for the mean.
+SS_EPS = 2.0 ** -20
+
+
+def ss_bars(raw: np.ndarray, ss: np.ndarray, ss64: np.ndarray, mean: np.ndarray, var: np.ndarray, fp16: bool):
+    """A conv's (scale, shift) table `ss` [C, 2] against norm_reference's (ss64, mean, var) of its own raw output [C, ...]: the largest
+    |d scale| / scale and |d shift| over their bars (<= 1 passes), and the largest |mean| / std."""
+    r2 = raw.reshape(raw.shape[0], -1).astype(np.float64)
+    n = r2.shape[1]
+    amp = 1.0 + mean ** 2 / np.maximum(var, 1e-300)          # E[c^2] / var
+    dmean = SS_EPS * np.abs(r2).mean(1)                        # fp32 sum of c: error relative to sum |c|
+    rel = SS_EPS * amp / 2 + 2.0 ** -24
+    if fp16:   # statistics of the fp32 epilogue values, not of their fp16 roundings: 4 sigma of the rounding noise
+        rel = rel + (2.0 ** -24 + 4 * 2.0 ** -11 / np.sqrt(n)) * amp
+        dmean = dmean + 4 * 2.0 ** -11 * np.sqrt((r2 ** 2).mean(1) / n)
+    ds = np.abs(ss[:, 0] - ss64[:, 0]) / np.abs(ss64[:, 0])
+    dt = np.abs(ss[:, 1] - ss64[:, 1])
+    tol_t = 2.0 ** -24 * np.abs(ss64[:, 1]) + np.abs(ss64[:, 0]) * dmean + np.abs(mean * ss64[:, 0]) * rel
+    return float((ds / rel).max()), float((dt / tol_t).max()), float((np.abs(mean) / np.sqrt(np.maximum(var, 1e-300))).max())
+
+
 # ---- numpy model of the split-precision product ------------------------------------------------------------------------------
 def x3_weight_scale(w: np.ndarray) -> float:
     """csrc/conv.hip x3_weight_scale: power of two that puts max |w| into [2^13, 2^14)."""

@@ -27,12 +27,7 @@ pytestmark = pytest.mark.gpu
 LK = {1: "first_valu", 2: "first_mfma", 3: "conv_ws", 4: "conv_ns", 5: "conv_mfma", 6: "conv_f32", 7: "convt_x3", 8: "convt_mfma",
       9: "convt_rw", 10: "convt_deep", 11: "convt_f32", 12: "head_x3", 13: "head_f32", 14: "head_mfma"}
 
-# InstanceNorm (scale, shift): the statistics are fp32 partial sums of (c, c^2) per conv-epilogue slot, reduced in fp64;
-# var = E[c^2] - mean^2 amplifies the relative error eps_s of E[c^2] by E[c^2] / var = 1 + mean^2 / var, and scale = gamma / sqrt(var
-# + eps) halves it: |d scale| / scale <= SS_EPS * (1 + mean^2 / var) / 2 + 2^-24 (its fp32 rounding).  SS_EPS = the relative error
-# of an fp32-accumulated sum of positive terms (measured on MI355X: see DESIGN section 3).  The fp16 mode's statistics are
-# those of the fp32 epilogue values, the stored raw output is their fp16 rounding: + 2^-11 / sqrt(n) of the rms for the mean.
-SS_EPS = 2.0 ** -20
+# the (scale, shift) bars and SS_EPS: layer_reference.ss_bars (shared with tests/test_gpu_conv_forms.py)
 
 
 @pytest.fixture(scope="module")
@@ -154,20 +149,7 @@ def _check(prec, geom, sd, tile_in, got, tag, rows, fails):
                "conv_ok": ok, "stats_ok": True, "at": tuple(int(v) for v in at)}
         if L.normkey:
             ss64, mean, var = lr.norm_reference(d["raw"], sd[L.normkey + ".weight"], sd[L.normkey + ".bias"])
-            r2 = d["raw"].reshape(d["raw"].shape[0], -1).astype(np.float64)
-            n = r2.shape[1]
-            amp = 1.0 + mean ** 2 / np.maximum(var, 1e-300)          # E[c^2] / var
-            dmean = SS_EPS * np.abs(r2).mean(1)                        # fp32 sum of c: error relative to sum |c|
-            rel = SS_EPS * amp / 2 + 2.0 ** -24
-            if prec == "fp16":   # statistics of the fp32 epilogue values, not of their fp16 roundings: 4 sigma of the rounding noise
-                rel = rel + (2.0 ** -24 + 4 * 2.0 ** -11 / np.sqrt(n)) * amp
-                dmean = dmean + 4 * 2.0 ** -11 * np.sqrt((r2 ** 2).mean(1) / n)
-            ds = np.abs(d["ss"][:, 0] - ss64[:, 0]) / np.abs(ss64[:, 0])
-            dt = np.abs(d["ss"][:, 1] - ss64[:, 1])
-            tol_t = 2.0 ** -24 * np.abs(ss64[:, 1]) + np.abs(ss64[:, 0]) * dmean + np.abs(mean * ss64[:, 0]) * rel
-            row["ss"] = float((ds / rel).max())
-            row["sh"] = float((dt / tol_t).max())
-            row["mean/std"] = float((np.abs(mean) / np.sqrt(np.maximum(var, 1e-300))).max())
+            row["ss"], row["sh"], row["mean/std"] = lr.ss_bars(d["raw"], d["ss"], ss64, mean, var, prec == "fp16")
             if row["ss"] > 1 or row["sh"] > 1:
                 row["ok"] = row["stats_ok"] = ok = False
             if prec == "fp16" and not np.array_equal(d["ss16"], lr.ss16_pack(d["ss"])):
