@@ -8,8 +8,8 @@ only -- PARITY UNPINNED vs GDCM / SimpleITK.
 Scope (everything else raises, nothing is guessed):
   * transfer syntaxes: implicit VR little endian (1.2.840.10008.1.2), explicit VR little endian (1.2.840.10008.1.2.1),
     JPEG Lossless Process 14 (1.2.840.10008.1.2.4.57, .70 -- boa_hip/jpeg_lossless.py), JPEG-LS lossless and near-lossless
-    (1.2.840.10008.1.2.4.80, .81 -- boa_hip/jpeg_ls.py), JPEG 2000 holding a reversible 5/3 stream (1.2.840.10008.1.2.4.90,
-    .91 -- boa_hip/jpeg2000.py) and RLE Lossless (1.2.840.10008.1.2.5 -- boa_hip/rle_lossless.py): encapsulated PixelData,
+    (1.2.840.10008.1.2.4.80, .81 -- boa_hip/jpeg_ls.py), JPEG 2000 holding a reversible 5/3 stream or an irreversible 9/7 one
+    with scalar quantisation, lossy then as OpenJPEG decodes it (1.2.840.10008.1.2.4.90, .91 -- boa_hip/jpeg2000.py) and RLE Lossless (1.2.840.10008.1.2.5 -- boa_hip/rle_lossless.py): encapsulated PixelData,
     one frame per file, the frames of a series decoded on the GPU in one call per codec; other compressed (lossy JPEG,
     MPEG), deflated and big-endian files raise NotImplementedError;
   * single-frame, MONOCHROME2, SamplesPerPixel 1, BitsAllocated 16 (8 and 32 are read too);
@@ -194,7 +194,7 @@ def read_file(path, stop_before_pixels: bool = False) -> Dict[str, Any]:
     if tsuid not in (IMPLICIT_LE, EXPLICIT_LE) and tsuid not in _CODECS:
         raise NotImplementedError(f"{path}: transfer syntax {tsuid} (compressed, deflated or big endian) is not supported; "
                                   "only implicit / explicit VR little endian (uncompressed), JPEG Lossless (Process 14), "
-                                  "JPEG-LS, JPEG 2000 (reversible) and RLE Lossless are read")
+                                  "JPEG-LS, JPEG 2000 and RLE Lossless are read")
     explicit = tsuid != IMPLICIT_LE
     encapsulated = tsuid in _CODECS
     out["TransferSyntaxUID"] = tsuid

@@ -1,8 +1,9 @@
-"""JPEG 2000 lossless (ITU T.800, reversible 5/3, one component, one tile) for DICOM CT: transfer syntaxes
-1.2.840.10008.1.2.4.90 (lossless only) and 1.2.840.10008.1.2.4.91 (holding a reversible stream).  A .91 stream may be lossy
-while reversible: its layers stop code blocks before their last coding pass.  Such blocks are reconstructed as OpenJPEG
-reconstructs them (every coefficient at the midpoint of what its undecoded bit-planes leave open), so the pixels equal the
-reference's.  The reference reads these
+"""JPEG 2000 (ITU T.800, one component, one tile) for DICOM CT: transfer syntaxes 1.2.840.10008.1.2.4.90 (lossless only) and
+1.2.840.10008.1.2.4.91, holding the reversible 5/3 transform or the irreversible 9/7 transform with scalar quantisation (derived
+or expounded); the stream decides, not the transfer syntax.  A reversible .91 stream may be lossy too: its layers stop code blocks
+before their last coding pass.  Such blocks are reconstructed as OpenJPEG reconstructs them (every coefficient at the midpoint of
+what its undecoded bit-planes leave open), and a 9/7 stream is dequantised, transformed and rounded in OpenJPEG's float32
+arithmetic (csrc/j2k_dwt97.h), so the pixels equal the reference's in every case.  The reference reads these
 series through GDCM / OpenJPEG (BOA/compute/io.py:254-259); here the host parses the codestream and runs tier-2, and tier-1 and
 the inverse wavelet transform of the whole series run in one batched HIP call (csrc/j2k.hip, `boa_j2k_decode`).
 
@@ -21,7 +22,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 J2K_LOSSLESS = "1.2.840.10008.1.2.4.90"     # JPEG 2000 Image Compression (Lossless Only)
-J2K = "1.2.840.10008.1.2.4.91"              # JPEG 2000 Image Compression (a reversible stream is read)
+J2K = "1.2.840.10008.1.2.4.91"              # JPEG 2000 Image Compression (reversible or irreversible)
 SYNTAXES = (J2K_LOSSLESS, J2K)
 
 # include/boa_hip.h: BOA_J2K_FRAME_WORDS, BOA_J2K_F_*, BOA_J2K_BLOCK_WORDS, BOA_J2K_B_*
@@ -52,6 +53,10 @@ class Frame:
     levels: int                    # decomposition levels NL
     blocks: np.ndarray             # int64 [n][8]: orientation, x0, y0 (Mallat position), w, h, bit-planes, passes, bytes
     data: bytes                    # the blocks' data, block after block, in table order
+    transform: int = 1             # 1 reversible 5/3, 0 irreversible 9/7 (the COD / COC field)
+    band: Optional[np.ndarray] = None       # int64 [n]: the block's subband, 0 LL, 1 + 3 (r - 1) + (0 HL, 1 LH, 2 HH) of resolution r
+    band_mb: Optional[np.ndarray] = None    # int64 [3 NL + 1]: magnitude bit-planes M_b = G + eps_b - 1 of every subband
+    steps: Optional[np.ndarray] = None      # float32 [3 NL + 1], 9/7 only: step_b = (1 + mu_b / 2048) 2^(P - eps_b)
 
 
 @dataclass
@@ -105,9 +110,7 @@ def _cod_params(r: _Reader, scod_precincts: bool, name: str) -> _Coding:
     levels, xcb, ycb, style, transform = r.take(">BBBBB")
     if levels > 32:
         raise _err(f"{name}: {levels} decomposition levels (at most 32)")
-    if transform == 0:
-        raise NotImplementedError(f"{name}: irreversible 9/7 wavelet transform: lossy JPEG 2000 is not read")
-    if transform != 1:
+    if transform not in (0, 1):
         raise _err(f"{name}: wavelet transform {transform} (0 = 9/7, 1 = 5/3)")
     if xcb > 8 or ycb > 8 or xcb + ycb > 8:
         raise _err(f"{name}: code-block size exponents {xcb + 2}, {ycb + 2} (each 2..10, sum at most 12)")
@@ -130,16 +133,51 @@ def _cod_params(r: _Reader, scod_precincts: bool, name: str) -> _Coding:
     return _Coding(levels, xcb + 2, ycb + 2, style, transform, pp)
 
 
-def _quant(r: _Reader, name: str) -> Tuple[int, List[int]]:
+def _quant(r: _Reader, name: str) -> Tuple[int, int, List[int]]:
+    """Sqcd / Sqcc and what follows -> (style, guard bits, values): style 0 an exponent per subband, style 1 (derived) the one
+    16-bit eps << 11 | mu of the LL band, style 2 (expounded) one such value per subband."""
     sq = r.take(">B")
     style, guard = sq & 31, sq >> 5
-    if style in (1, 2):
-        raise NotImplementedError(f"{name}: scalar quantisation ({'derived' if style == 1 else 'expounded'}): lossy JPEG 2000 "
-                                  "is not read")
-    if style != 0:
+    if style not in (0, 1, 2):
         raise _err(f"{name}: quantisation style {style}")
-    exps = [b >> 3 for b in r.b[r.p:]]
-    return guard, exps
+    if style == 0:
+        return style, guard, [b >> 3 for b in r.b[r.p:]]
+    if style == 1:
+        return style, guard, [r.take(">H")]
+    vals = []
+    while r.p < len(r.b):
+        vals.append(r.take(">H"))
+    return style, guard, vals
+
+
+def _check_pair(transform: int, style: int, name: str):
+    """The wavelet transform and the quantisation style that hold for the component have to belong together: 5/3 without
+    quantisation, 9/7 with scalar quantisation."""
+    if transform == 0 and style == 0:
+        raise NotImplementedError(f"{name}: irreversible 9/7 wavelet transform without scalar quantisation: lossy JPEG 2000 is not "
+                                  "read in this form")
+    if transform == 1 and style != 0:
+        raise NotImplementedError(f"{name}: scalar quantisation ({'derived' if style == 1 else 'expounded'}) with the reversible "
+                                  "5/3 transform is not read")
+
+
+def _band_table(levels: int, style: int, vals: List[int], precision: int, name: str):
+    """-> (eps_b per subband, step_b float32 per subband or None without quantisation); subbands LL, then HL LH HH of
+    resolutions 1 .. NL.  Derived quantisation (T.800 E-5): eps_b = eps_0 - (r - 1) from resolution 2 on (never below 0, as
+    OpenJPEG has it), mu_b = mu_0."""
+    nb = 3 * levels + 1
+    if style == 1:
+        e0, mu = vals[0] >> 11, vals[0] & 0x7FF
+        exps = [e0] + [max(0, e0 - (r - 1)) for r in range(1, levels + 1) for _ in range(3)]
+        mants = [mu] * nb
+    else:
+        if len(vals) < nb:
+            raise _err(f"{name}: QCD/QCC holds {len(vals)} {'exponents' if style == 0 else 'step sizes'}, {nb} subbands")
+        if style == 0:
+            return list(vals[:nb]), None
+        exps, mants = [v >> 11 for v in vals[:nb]], [v & 0x7FF for v in vals[:nb]]
+    steps = np.array([(1.0 + m / 2048.0) * 2.0 ** (precision - e) for e, m in zip(exps, mants)], dtype=np.float32)
+    return exps, steps
 
 
 def _tag_tree(w: int, h: int):
@@ -221,11 +259,9 @@ def _ceil_shift(v: int, s: int) -> int:
 
 
 def _tier2(tile: bytes, W: int, H: int, cod: _Coding, nlayers: int, prog: int, guard: int, exps: List[int],
-           name: str) -> Tuple[np.ndarray, bytes]:
+           name: str) -> Tuple[np.ndarray, bytes, np.ndarray]:
     NL = cod.levels
-    if len(exps) < 3 * NL + 1:
-        raise _err(f"{name}: QCD/QCC holds {len(exps)} exponents, {3 * NL + 1} subbands")
-    blocks: List[list] = []           # orient, x0, y0, w, h, Mb, then: included, zbp, passes, lblock, chunks
+    blocks: List[list] = []           # orient, x0, y0, w, h, Mb, then: included, zbp, passes, lblock, chunks, subband
     precincts: Dict[Tuple[int, int], list] = {}
     order = []                        # (y, x, r, p) sort keys of the precincts on the reference grid
     for r in range(NL + 1):
@@ -234,17 +270,17 @@ def _tier2(tile: bytes, W: int, H: int, cod: _Coding, nlayers: int, prog: int, g
         ppx, ppy = cod.precincts[r]
         if r == 0:
             xcb, ycb = min(cod.xcb, ppx), min(cod.ycb, ppy)
-            bands = [(0, 0, 0, wr, hr, exps[0], ppx, ppy)]
+            bands = [(0, 0, 0, wr, hr, 0, ppx, ppy)]
         else:
             wl, hl = _ceil_shift(W, d + 1), _ceil_shift(H, d + 1)
             xcb, ycb = min(cod.xcb, ppx - 1), min(cod.ycb, ppy - 1)
-            bands = [(o, x0, y0, bw, bh, exps[3 * (r - 1) + k], ppx - 1, ppy - 1) for k, (o, x0, y0, bw, bh) in enumerate(
+            bands = [(o, x0, y0, bw, bh, 3 * (r - 1) + k, ppx - 1, ppy - 1) for k, (o, x0, y0, bw, bh) in enumerate(
                 [(1, wl, 0, wr - wl, hl), (2, 0, hl, wl, hr - hl), (3, wl, hl, wr - wl, hr - hl)], start=1)]
         npx, npy = _ceil_shift(wr, ppx), _ceil_shift(hr, ppy)
         for py in range(npy):
             for px in range(npx):
                 entry = []
-                for o, bx, by, bw, bh, eps, pbx, pby in bands:
+                for o, bx, by, bw, bh, sb, pbx, pby in bands:
                     x0, x1 = min(px << pbx, bw), min((px + 1) << pbx, bw)
                     y0, y1 = min(py << pby, bh), min((py + 1) << pby, bh)
                     if x1 <= x0 or y1 <= y0:
@@ -257,7 +293,7 @@ def _tier2(tile: bytes, W: int, H: int, cod: _Coding, nlayers: int, prog: int, g
                             ax, ay = cx << xcb, cy << ycb
                             ids.append(len(blocks))
                             blocks.append([o, bx + ax, by + ay, min(ax + (1 << xcb), bw) - ax, min(ay + (1 << ycb), bh) - ay,
-                                           guard + eps - 1, False, 0, 0, 3, []])
+                                           guard + exps[sb] - 1, False, 0, 0, 3, [], sb])
                     entry.append((ids, _tag_tree(cx1 - cx0, cy1 - cy0), _tag_tree(cx1 - cx0, cy1 - cy0)))
                 precincts[(r, py * npx + px)] = entry
                 order.append(((py << (ppy + d)), (px << (ppx + d)), r, py * npx + px))
@@ -325,14 +361,15 @@ def _tier2(tile: bytes, W: int, H: int, cod: _Coding, nlayers: int, prog: int, g
             raise _err(f"{name}: {b[8]} coding passes in one code block")
         table[k] = (b[0], b[1], b[2], b[3], b[4], nbp, b[8], len(data))
         datas.append(data)
-    return table, b"".join(datas)
+    return table, b"".join(datas), np.array([b[11] for b in blocks], dtype=np.int64)
 
 
 def parse_frame(data: bytes, *, rows: int, cols: int, bits_allocated: int = 16, bits_stored: Optional[int] = None,
                 name: str = "") -> Frame:
     """One JPEG 2000 frame (a bare codestream, or a JP2 file whose 'jp2c' box is taken) -> its code-block table.  Raises
-    NotImplementedError for what this reader does not decode (named: lossy 9/7, several tiles / components, sub-sampling,
-    code-block styles, SOP / EPH, POC, PPM, PPT, RGN), DicomError for malformed or inconsistent data."""
+    NotImplementedError for what this reader does not decode (named: 9/7 without scalar quantisation and 5/3 with it, several
+    tiles / components, sub-sampling, code-block styles, SOP / EPH, POC, PPM, PPT, RGN), DicomError for malformed or
+    inconsistent data.  The stream decides between the reversible 5/3 and the irreversible 9/7, not the transfer syntax."""
     buf = unwrap_jp2(bytes(data), name)
     if buf[:2] != b"\xFF\x4F":
         raise _err(f"{name}: compressed frame does not start with a JPEG 2000 SOC marker")
@@ -428,6 +465,7 @@ def parse_frame(data: bytes, *, rows: int, cols: int, bits_allocated: int = 16, 
         pos = nxt
     if siz is None or cod is None or qcd is None:
         raise _err(f"{name}: main header without {'SIZ' if siz is None else 'COD' if cod is None else 'QCD'}")
+    _check_pair((coc or cod[2]).transform, (qcc or qcd)[0], name)      # the pair that holds once the whole main header is known
     parts = []
     first = True
     while True:                                          # tile-parts
@@ -467,9 +505,12 @@ def parse_frame(data: bytes, *, rows: int, cols: int, bits_allocated: int = 16, 
             raise _err(f"{name}: codestream ends without EOC")
     prog, nlayers, coding = cod
     coding = coc or coding
-    guard, exps = qcc or qcd
-    table, bdata = _tier2(b"".join(parts), cols, rows, coding, nlayers, prog, guard, exps, name)
-    return Frame(name, rows, cols, siz[0], siz[1], coding.levels, table, bdata)
+    style, guard, vals = qcc or qcd
+    _check_pair(coding.transform, style, name)                        # (a tile-part header may have replaced either)
+    exps, steps = _band_table(coding.levels, style, vals, siz[0], name)
+    table, bdata, band = _tier2(b"".join(parts), cols, rows, coding, nlayers, prog, guard, exps, name)
+    return Frame(name, rows, cols, siz[0], siz[1], coding.levels, table, bdata, coding.transform, band,
+                 guard + np.array(exps, dtype=np.int64) - 1, steps)
 
 
 def build_batch(frames: Sequence[Frame]):
@@ -480,8 +521,10 @@ def build_batch(frames: Sequence[Frame]):
     off = out = nb = 0
     for f, fr in enumerate(frames):
         n = len(fr.blocks)
-        ftab[f, :10] = [out & 0xFFFFFFFF, out >> 32, fr.rows, fr.cols, fr.levels, fr.precision, int(fr.signed), nb, n, 0]
+        ftab[f, :10] = [out & 0xFFFFFFFF, out >> 32, fr.rows, fr.cols, fr.levels, fr.precision, int(fr.signed), nb, n, fr.transform]
         b = np.zeros((n, BLOCK_WORDS), dtype=np.int64)
+        if fr.transform == 0:                            # BOA_J2K_B_STEP: the float32 bits of 0.5f * step_b
+            b[:, 11] = (np.float32(0.5) * fr.steps[fr.band]).astype(np.float32).view(np.uint32)
         lens = fr.blocks[:, 7]
         starts = off + np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64) if n else np.zeros(0, dtype=np.int64)
         b[:, 0] = f

@@ -1,9 +1,11 @@
-// JPEG 2000 with the reversible 5/3 transform (ITU T.800, one component, one tile; lossless, or stopped early by its layers):
+// JPEG 2000 with the reversible 5/3 transform (lossless, or stopped early by its layers) or the irreversible 9/7 transform with
+// scalar quantisation (ITU T.800, one component, one tile):
 // tier-1 and the inverse wavelet transform of a batch of frames (the compressed slices of a DICOM series, transfer syntaxes 1.2.840.10008.1.2.4.90 / .91) in one call.
 //
 // The host (boa_hip/jpeg2000.py) parses the codestream and runs tier-2, and hands over a flat table of code blocks: frame,
 // subband orientation, position and size in the frame's coefficient plane (Mallat layout), number of magnitude bit-planes,
-// number of coding passes, and the block's data (its contributions of all layers, one codeword segment: code-block style 0).
+// number of coding passes, and the block's data (its contributions of all layers, one codeword segment: code-block style 0);
+// for a 9/7 frame also half the quantisation step of the block's subband.  The frames of a batch may mix both transforms.
 //
 // k_j2k_t1: one lane per code block, all blocks of a chunk of frames in one launch (T.800 Annexes C and D).  The MQ decoder's
 // registers stay in the lane's registers, its 19 context states in LDS (a byte per context and lane).  Each coefficient has a
@@ -18,15 +20,25 @@
 // k_j2k_idwt_h / k_j2k_idwt_v: inverse 5/3 lifting (Annex F.3.8, symmetric extension, all origins zero so that every level
 // starts at an even coordinate; a length-1 signal passes through) of one level of every frame, rows then columns (2D_SR);
 // the last column pass of a frame adds the DC level shift, clamps to the sample range (as OpenJPEG does) and writes the uint16
-// output.  k_j2k_store does the same for frames without a decomposition.  Launches: 1 + 2 x (levels) per chunk.
+// output.  k_j2k_store does the same for frames without a decomposition.  Launches: 1 + 2 x (levels) per chunk and transform.
+// 9/7 frames (j2k_dwt97.h holds the arithmetic, which is OpenJPEG's, float32 operation by operation, so that the pixels are its
+// pixels): k_j2k_t1 ends a block with a sweep that turns every significant coefficient into float(+-(2 m + 2^b_last)) * step / 2,
+// whose bits take the coefficient's place in the plane (4 bytes per sample either way: workspace and chunks are the same);
+// k_j2k_idwt97_h / k_j2k_idwt97_v follow the step schedule of the 5/3 kernels, each kernel skipping the other transform's frames:
+// every thread recomputes the +-4 window of a pair of neighbouring samples (scaling, four lifting steps, whole-sample mirroring),
+// which gives each output the operations of the in-place sweeps in their order; the last column pass rounds (ties to even), adds
+// the DC level shift, clamps and writes the uint16 output.
 //
 // Malformed input never faults: the host entry validates every table field against the buffers before anything is copied,
 // the MQ decoder reads only inside [block start, block end) and feeds 0xFF past it (C.3.4), every loop is bounded by the
 // table, and a block with more passes than its bit-planes allow or magnitudes beyond 30 bits sets the frame's status.
 #include <algorithm>
+#include <cmath>
+#include <cstring>
 #include <vector>
 
 #include "common.h"
+#include "j2k_dwt97.h"
 
 namespace {
 
@@ -248,6 +260,19 @@ __global__ void __launch_bounds__(NT_T1) k_j2k_t1(const unsigned char* __restric
             }
         }
     }
+    if (F[BOA_J2K_F_TRANSFORM] == BOA_J2K_T_97) {
+        // A block of a 9/7 frame: every significant coefficient becomes float(+-(2 m + 2^b_last)) * step / 2 (j2k_dwt97.h), the
+        // bits of the float32 in the plane; b_last by the rule below, 0 throughout a complete block.
+        const int pl = passes - 1, kf = pl == 0 ? 2 : (pl - 1) % 3, bf = nbp - 1 - (pl + 2) / 3;
+        const float step_half = __int_as_float(B[BOA_J2K_B_STEP]);
+        for (int y = 0; y < h; ++y)
+            for (int x = 0; x < w; ++x) {
+                int* v = V + (size_t)y * cols + x;
+                const int t = *v;
+                if (t != 0) *v = __float_as_int(j2k97_dequant(t, j2k_b_last(t < 0 ? -t : t, kf, bf), step_half));
+            }
+        return;
+    }
     if (passes == 3 * nbp - 2) return;
     // A block that stops early (a rate- or quality-limited layer): as OpenJPEG does, a significant coefficient goes to the
     // midpoint of what its undecoded planes leave open, |v| += 2^(b_last - 1) where b_last >= 1 is the lowest plane at which
@@ -282,7 +307,7 @@ __global__ void __launch_bounds__(NT_DWT) k_j2k_idwt_h(const int* __restrict__ f
                                                       int max_levels, const int* __restrict__ A, int* __restrict__ Bp) {
     const int* F = frames + (size_t)(f0 + blockIdx.y) * BOA_J2K_FRAME_WORDS;
     const int r = frame_level(F, step, max_levels);
-    if (r < 1) return;
+    if (r < 1 || F[BOA_J2K_F_TRANSFORM] != BOA_J2K_T_53) return;
     const int rows = F[BOA_J2K_F_ROWS], cols = F[BOA_J2K_F_COLS], d = F[BOA_J2K_F_LEVELS] - r;
     const int wr = ceil_shift(cols, d), hr = ceil_shift(rows, d), wl = ceil_shift(cols, d + 1), nh = wr - wl;
     const int idx = blockIdx.x * NT_DWT + threadIdx.x;
@@ -308,7 +333,7 @@ __global__ void __launch_bounds__(NT_DWT) k_j2k_idwt_v(const int* __restrict__ f
                                                       unsigned short* __restrict__ out) {
     const int* F = frames + (size_t)(f0 + blockIdx.y) * BOA_J2K_FRAME_WORDS;
     const int r = frame_level(F, step, max_levels);
-    if (r < 1) return;
+    if (r < 1 || F[BOA_J2K_F_TRANSFORM] != BOA_J2K_T_53) return;
     const int rows = F[BOA_J2K_F_ROWS], cols = F[BOA_J2K_F_COLS], L = F[BOA_J2K_F_LEVELS], d = L - r;
     const int wr = ceil_shift(cols, d), hr = ceil_shift(rows, d), hl = ceil_shift(rows, d + 1), nh = hr - hl;
     const int idx = blockIdx.x * NT_DWT + threadIdx.x;
@@ -342,7 +367,58 @@ __global__ void __launch_bounds__(NT_DWT) k_j2k_idwt_v(const int* __restrict__ f
     }
 }
 
-// frames without a decomposition level: plane -> shifted, clamped uint16 samples
+// The 9/7 frames' row pass of resolution r (j2k_dwt97.h): one thread per pair of neighbouring samples, each from its own window
+// of the row's low half [0, wl) and high half [wl, w_r) of A (the float32 coefficients) -> interleaved in B.
+__global__ void __launch_bounds__(NT_DWT) k_j2k_idwt97_h(const int* __restrict__ frames, int f0, long long base, int step,
+                                                        int max_levels, const float* __restrict__ A, float* __restrict__ Bp) {
+    const int* F = frames + (size_t)(f0 + blockIdx.y) * BOA_J2K_FRAME_WORDS;
+    const int r = frame_level(F, step, max_levels);
+    if (r < 1 || F[BOA_J2K_F_TRANSFORM] != BOA_J2K_T_97) return;
+    const int rows = F[BOA_J2K_F_ROWS], cols = F[BOA_J2K_F_COLS], d = F[BOA_J2K_F_LEVELS] - r;
+    const int wr = ceil_shift(cols, d), hr = ceil_shift(rows, d), wl = ceil_shift(cols, d + 1);
+    const int idx = blockIdx.x * NT_DWT + threadIdx.x;
+    if (idx >= hr * wl) return;
+    const int y = idx / wl, k = idx - y * wl;
+    const size_t o = (size_t)(frame_out(F) - base) + (size_t)y * cols;
+    const float* row = A + o;
+    float v0, v1;
+    j2k97_pair([&](int i) { return row[(i & 1) ? wl + (i >> 1) : (i >> 1)]; }, k, wr, v0, v1);
+    Bp[o + 2 * k] = v0;
+    if (2 * k + 1 < wr) Bp[o + 2 * k + 1] = v1;
+}
+
+// The 9/7 frames' column pass: low rows [0, hl) and high rows [hl, h_r) of B -> interleaved in A, or (the frame's last level)
+// the rounded, shifted, clamped uint16 samples in out
+__global__ void __launch_bounds__(NT_DWT) k_j2k_idwt97_v(const int* __restrict__ frames, int f0, long long base, int step,
+                                                        int max_levels, const float* __restrict__ Bp, float* __restrict__ A,
+                                                        unsigned short* __restrict__ out) {
+    const int* F = frames + (size_t)(f0 + blockIdx.y) * BOA_J2K_FRAME_WORDS;
+    const int r = frame_level(F, step, max_levels);
+    if (r < 1 || F[BOA_J2K_F_TRANSFORM] != BOA_J2K_T_97) return;
+    const int rows = F[BOA_J2K_F_ROWS], cols = F[BOA_J2K_F_COLS], L = F[BOA_J2K_F_LEVELS], d = L - r;
+    const int wr = ceil_shift(cols, d), hr = ceil_shift(rows, d), hl = ceil_shift(rows, d + 1);
+    const int idx = blockIdx.x * NT_DWT + threadIdx.x;
+    if (idx >= wr * hl) return;
+    const int k = idx / wr, x = idx - k * wr;
+    const long long fo = frame_out(F);
+    const size_t o = (size_t)(fo - base) + x;
+    const float* col = Bp + o;
+    float v0, v1;
+    j2k97_pair([&](int i) { return col[(size_t)((i & 1) ? hl + (i >> 1) : (i >> 1)) * cols]; }, k, hr, v0, v1);
+    const bool two = 2 * k + 1 < hr;
+    if (r == L) {
+        const int P = F[BOA_J2K_F_P], sg = F[BOA_J2K_F_SIGNED];
+        unsigned short* po = out + fo + x;
+        po[(size_t)(2 * k) * cols] = j2k97_sample(v0, P, sg);
+        if (two) po[(size_t)(2 * k + 1) * cols] = j2k97_sample(v1, P, sg);
+    } else {
+        float* pa = A + o;
+        pa[(size_t)(2 * k) * cols] = v0;
+        if (two) pa[(size_t)(2 * k + 1) * cols] = v1;
+    }
+}
+
+// frames without a decomposition level: plane -> shifted, clamped uint16 samples (a 9/7 frame's plane holds float32: rounded first)
 __global__ void __launch_bounds__(NT_DWT) k_j2k_store(const int* __restrict__ frames, int f0, long long base,
                                                      const int* __restrict__ A, unsigned short* __restrict__ out) {
     const int* F = frames + (size_t)(f0 + blockIdx.y) * BOA_J2K_FRAME_WORDS;
@@ -350,7 +426,11 @@ __global__ void __launch_bounds__(NT_DWT) k_j2k_store(const int* __restrict__ fr
     const int n = F[BOA_J2K_F_ROWS] * F[BOA_J2K_F_COLS];
     const int P = F[BOA_J2K_F_P], sg = F[BOA_J2K_F_SIGNED];
     const long long fo = frame_out(F);
-    for (int i = blockIdx.x * NT_DWT + threadIdx.x; i < n; i += gridDim.x * NT_DWT) out[fo + i] = j2k_sample(A[fo - base + i], P, sg);
+    const bool irr = F[BOA_J2K_F_TRANSFORM] == BOA_J2K_T_97;
+    for (int i = blockIdx.x * NT_DWT + threadIdx.x; i < n; i += gridDim.x * NT_DWT) {
+        const int v = A[fo - base + i];
+        out[fo + i] = irr ? j2k97_sample(__int_as_float(v), P, sg) : j2k_sample(v, P, sg);
+    }
 }
 
 }  // namespace
@@ -368,6 +448,8 @@ extern "C" int boa_j2k_decode(boa_ctx* c, const uint8_t* dev_data, size_t data_b
         BOA_REQUIRE(rows >= 1 && rows <= 65535 && cols >= 1 && cols <= 65535, "boa_j2k_decode: frame %d: size %d x %d", f, rows, cols);
         BOA_REQUIRE(L >= 0 && L <= 32 && P >= 1 && P <= 16 && (F[BOA_J2K_F_SIGNED] & ~1) == 0,
                     "boa_j2k_decode: frame %d: %d levels, precision %d, signed %d", f, L, P, F[BOA_J2K_F_SIGNED]);
+        const int T = F[BOA_J2K_F_TRANSFORM];
+        BOA_REQUIRE(T == BOA_J2K_T_97 || T == BOA_J2K_T_53, "boa_j2k_decode: frame %d: wavelet transform %d (0 = 9/7, 1 = 5/3)", f, T);
         BOA_REQUIRE(fo == out_total, "boa_j2k_decode: frame %d: output offset %lld, %lld expected (frames packed in order)", f, fo, out_total);
         out_total += (long long)rows * cols;
         const int bf = F[BOA_J2K_F_BLOCK_FIRST], nb = F[BOA_J2K_F_N_BLOCKS];
@@ -385,6 +467,11 @@ extern "C" int boa_j2k_decode(boa_ctx* c, const uint8_t* dev_data, size_t data_b
                         "boa_j2k_decode: block %d: %d x %d at (%d, %d) outside its %d x %d frame", b, w, h, x0, y0, rows, cols);
             BOA_REQUIRE(B[BOA_J2K_B_PASSES] >= 0 && len >= 0 && off + (unsigned long long)len <= data_bytes,
                         "boa_j2k_decode: block %d: %d passes, bytes [%llu, +%lld) outside the %zu-byte buffer", b, B[BOA_J2K_B_PASSES], off, len, data_bytes);
+            if (T == BOA_J2K_T_97) {
+                float sh;
+                memcpy(&sh, B + BOA_J2K_B_STEP, 4);
+                BOA_REQUIRE(std::isfinite(sh) && sh > 0.0f, "boa_j2k_decode: block %d: half quantisation step %g (finite, positive)", b, (double)sh);
+            }
         }
     }
     BOA_REQUIRE((n_frames == 0 ? 0 : frames[(size_t)(n_frames - 1) * BOA_J2K_FRAME_WORDS + BOA_J2K_F_BLOCK_FIRST]
@@ -456,22 +543,34 @@ extern "C" int boa_j2k_decode(boa_ctx* c, const uint8_t* dev_data, size_t data_b
         if (k.nb)
             hipLaunchKernelGGL(k_j2k_t1, dim3((k.nb + NT_T1 - 1) / NT_T1), dim3(NT_T1), 0, c->stream, dev_data, d_frames, d_blocks,
                                d_perm + k.b0, k.nb, k.base, A, flags, d_status);
-        bool any_flat = false;
-        for (int f = k.f0; f < k.f0 + k.nf; ++f) any_flat |= frames[(size_t)f * BOA_J2K_FRAME_WORDS + BOA_J2K_F_LEVELS] == 0;
+        bool any_flat = false, any[2] = {false, false};       // any[T]: the chunk holds frames of transform T
+        for (int f = k.f0; f < k.f0 + k.nf; ++f) {
+            any_flat |= frames[(size_t)f * BOA_J2K_FRAME_WORDS + BOA_J2K_F_LEVELS] == 0;
+            any[frames[(size_t)f * BOA_J2K_FRAME_WORDS + BOA_J2K_F_TRANSFORM]] = true;
+        }
         for (int step = 1; step <= k.max_levels; ++step) {
-            long long nh = 1, nv = 1;                  // the largest row-pass / column-pass work of a frame at this step
+            long long nh[2] = {1, 1}, nv[2] = {1, 1};   // per transform: the largest row-pass / column-pass work of a frame at this step
             for (int f = k.f0; f < k.f0 + k.nf; ++f) {
                 const int* F = frames + (size_t)f * BOA_J2K_FRAME_WORDS;
-                const int r = step - (k.max_levels - F[BOA_J2K_F_LEVELS]);
+                const int r = step - (k.max_levels - F[BOA_J2K_F_LEVELS]), T = F[BOA_J2K_F_TRANSFORM];
                 if (r < 1) continue;
                 const int d = F[BOA_J2K_F_LEVELS] - r;
-                nh = std::max(nh, (long long)ceil_shift(F[BOA_J2K_F_ROWS], d) * ceil_shift(F[BOA_J2K_F_COLS], d + 1));
-                nv = std::max(nv, (long long)ceil_shift(F[BOA_J2K_F_COLS], d) * ceil_shift(F[BOA_J2K_F_ROWS], d + 1));
+                nh[T] = std::max(nh[T], (long long)ceil_shift(F[BOA_J2K_F_ROWS], d) * ceil_shift(F[BOA_J2K_F_COLS], d + 1));
+                nv[T] = std::max(nv[T], (long long)ceil_shift(F[BOA_J2K_F_COLS], d) * ceil_shift(F[BOA_J2K_F_ROWS], d + 1));
             }
-            hipLaunchKernelGGL(k_j2k_idwt_h, dim3((unsigned)((nh + NT_DWT - 1) / NT_DWT), k.nf), dim3(NT_DWT), 0, c->stream, d_frames,
-                               k.f0, k.base, step, k.max_levels, A, Bp);
-            hipLaunchKernelGGL(k_j2k_idwt_v, dim3((unsigned)((nv + NT_DWT - 1) / NT_DWT), k.nf), dim3(NT_DWT), 0, c->stream, d_frames,
-                               k.f0, k.base, step, k.max_levels, Bp, A, dev_out);
+            // both transforms follow one step schedule; a kernel leaves the other transform's frames alone
+            if (any[BOA_J2K_T_53]) {
+                hipLaunchKernelGGL(k_j2k_idwt_h, dim3((unsigned)((nh[BOA_J2K_T_53] + NT_DWT - 1) / NT_DWT), k.nf), dim3(NT_DWT), 0,
+                                   c->stream, d_frames, k.f0, k.base, step, k.max_levels, A, Bp);
+                hipLaunchKernelGGL(k_j2k_idwt_v, dim3((unsigned)((nv[BOA_J2K_T_53] + NT_DWT - 1) / NT_DWT), k.nf), dim3(NT_DWT), 0,
+                                   c->stream, d_frames, k.f0, k.base, step, k.max_levels, Bp, A, dev_out);
+            }
+            if (any[BOA_J2K_T_97]) {
+                hipLaunchKernelGGL(k_j2k_idwt97_h, dim3((unsigned)((nh[BOA_J2K_T_97] + NT_DWT - 1) / NT_DWT), k.nf), dim3(NT_DWT), 0,
+                                   c->stream, d_frames, k.f0, k.base, step, k.max_levels, (const float*)A, (float*)Bp);
+                hipLaunchKernelGGL(k_j2k_idwt97_v, dim3((unsigned)((nv[BOA_J2K_T_97] + NT_DWT - 1) / NT_DWT), k.nf), dim3(NT_DWT), 0,
+                                   c->stream, d_frames, k.f0, k.base, step, k.max_levels, (const float*)Bp, (float*)A, dev_out);
+            }
         }
         if (any_flat)
             hipLaunchKernelGGL(k_j2k_store, dim3(64, k.nf), dim3(NT_DWT), 0, c->stream, d_frames, k.f0, k.base, A, dev_out);

@@ -633,18 +633,21 @@ int boa_ljpeg_decode(boa_ctx* ctx, const uint8_t* dev_data, size_t data_bytes, i
                      const int* segs, int n_subs, const int* subs, int n_tables, const uint32_t* tables, uint16_t* dev_out,
                      int* host_status, int serial);
 
-/* ------------------------------------------------------------------ JPEG 2000 lossless decode (j2k.hip) --- */
-/* DICOM transfer syntaxes 1.2.840.10008.1.2.4.90 / .91 holding a reversible (5/3) stream, ITU T.800, one component, one tile,
- * code-block style 0.  The host parses the codestream and runs tier-2 (boa_hip/jpeg2000.py) and passes, as HOST arrays:
+/* ------------------------------------------------------------------ JPEG 2000 decode (j2k.hip) --- */
+/* DICOM transfer syntaxes 1.2.840.10008.1.2.4.90 / .91 holding a reversible (5/3) or an irreversible (9/7, scalar quantisation)
+ * stream, ITU T.800, one component, one tile, code-block style 0.  The host parses the codestream and runs tier-2 (boa_hip/jpeg2000.py) and passes, as HOST arrays:
  *   frames  int32 [n_frames][BOA_J2K_FRAME_WORDS]: fields BOA_J2K_F_* (sample offset of the frame's output in dev_out: frames
  *           packed in order, each rows x cols; decomposition levels; precision P 1..16; signed 0 / 1; its range of blocks:
- *           blocks grouped by frame, in frame order); frames of a batch may differ in size, levels and precision;
+ *           blocks grouped by frame, in frame order; the wavelet transform, BOA_J2K_T_97 or BOA_J2K_T_53: the value of the COD
+ *           field); frames of a batch may differ in size, levels, precision and transform;
  *   blocks  int32 [n_blocks][BOA_J2K_BLOCK_WORDS]: fields BOA_J2K_B_* (frame; orientation 0 LL, 1 HL, 2 LH, 3 HH; x0, y0, w, h:
  *           the block's place in the frame's coefficient plane, Mallat layout, w x h at most 4096; magnitude bit-planes
  *           Mb - zero bit-planes; coding passes, the first a cleanup pass on the most significant plane; byte offset and length
- *           of its data in dev_data, the contributions of all layers concatenated).
+ *           of its data in dev_data, the contributions of all layers concatenated; in a 9/7 frame BOA_J2K_B_STEP, the float32 bits of
+ *           half the subband's quantisation step, 0.5f * (1 + mu_b / 2048) 2^(P - eps_b), finite and positive).
  * Runs tier-1 of every block in one launch per chunk of frames (chunks keep the workspace below 1 GiB), then the inverse 5/3
- * with the DC level shift, into dev_out uint16 (the sample clamped to its P-bit range, modulo 2^16), and returns the per-frame
+ * or the inverse 9/7 (dequantisation, transform and rounding in OpenJPEG's float32 arithmetic, csrc/j2k_dwt97.h: the pixels
+ * are OpenJPEG's) with the DC level shift, into dev_out uint16 (the sample clamped to its P-bit range, modulo 2^16), and returns the per-frame
  * status (BOA_J2K_OK / _INVALID: a block with more passes than its bit-planes allow, or beyond 30 bit-planes) in host_status.
  * A block with fewer than 3 x bit-planes - 2 passes (a stream truncated by its layers; none is valid too) is reconstructed as
  * OpenJPEG does: a significant coefficient coded down to plane b >= 1 gets 2^(b - 1) added to its magnitude (the midpoint).
@@ -660,6 +663,9 @@ int boa_ljpeg_decode(boa_ctx* ctx, const uint8_t* dev_data, size_t data_bytes, i
 #define BOA_J2K_F_SIGNED 6
 #define BOA_J2K_F_BLOCK_FIRST 7
 #define BOA_J2K_F_N_BLOCKS 8
+#define BOA_J2K_F_TRANSFORM 9
+#define BOA_J2K_T_97 0
+#define BOA_J2K_T_53 1
 #define BOA_J2K_BLOCK_WORDS 12
 #define BOA_J2K_B_FRAME 0
 #define BOA_J2K_B_ORIENT 1
@@ -672,6 +678,7 @@ int boa_ljpeg_decode(boa_ctx* ctx, const uint8_t* dev_data, size_t data_bytes, i
 #define BOA_J2K_B_OFF_LO 8
 #define BOA_J2K_B_OFF_HI 9
 #define BOA_J2K_B_LEN 10
+#define BOA_J2K_B_STEP 11
 #define BOA_J2K_OK 0
 #define BOA_J2K_INVALID 1
 int boa_j2k_decode(boa_ctx* ctx, const uint8_t* dev_data, size_t data_bytes, int n_frames, const int* frames, int n_blocks,
