@@ -140,6 +140,8 @@ _PROTOS = {
     "boa_comm_stats": (i32, [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "boa_add_f16_planes": (i32, [vp, vp, vp, vp, i32, ip, i32, i32]),
     "boa_ljpeg_decode": (i32, [vp, vp, u64, i32, ip, i32, ip, i32, ip, i32, C.POINTER(C.c_uint32), vp, ip, i32]),
+    "boa_jdct_decode": (i32, [vp, vp, u64, i32, ip, i32, i32, i32, ip, i32, ip, i32, C.POINTER(C.c_uint32), i32,
+                        C.POINTER(C.c_uint16), vp, ip, i32]),
     "boa_j2k_decode": (i32, [vp, vp, u64, i32, ip, i32, ip, vp, ip]),
     "boa_rle_decode": (i32, [vp, vp, u64, i32, ip, i32, i32, i32, vp, ip, i32]),
     "boa_jls_decode": (i32, [vp, vp, u64, i32, ip, i32, i32, vp, ip, i32]),

@@ -9,9 +9,11 @@ Scope (everything else raises, nothing is guessed):
   * transfer syntaxes: implicit VR little endian (1.2.840.10008.1.2), explicit VR little endian (1.2.840.10008.1.2.1),
     JPEG Lossless Process 14 (1.2.840.10008.1.2.4.57, .70 -- boa_hip/jpeg_lossless.py), JPEG-LS lossless and near-lossless
     (1.2.840.10008.1.2.4.80, .81 -- boa_hip/jpeg_ls.py), JPEG 2000 holding a reversible 5/3 stream or an irreversible 9/7 one
-    with scalar quantisation, lossy then as OpenJPEG decodes it (1.2.840.10008.1.2.4.90, .91 -- boa_hip/jpeg2000.py) and RLE Lossless (1.2.840.10008.1.2.5 -- boa_hip/rle_lossless.py): encapsulated PixelData,
-    one frame per file, the frames of a series decoded on the GPU in one call per codec; other compressed (lossy JPEG,
-    MPEG), deflated and big-endian files raise NotImplementedError;
+    with scalar quantisation, lossy then as OpenJPEG decodes it (1.2.840.10008.1.2.4.90, .91 -- boa_hip/jpeg2000.py), RLE
+    Lossless (1.2.840.10008.1.2.5 -- boa_hip/rle_lossless.py) and lossy sequential DCT JPEG, baseline 8-bit and extended 8- or
+    12-bit, as libjpeg decodes it by default (1.2.840.10008.1.2.4.50, .51 -- boa_hip/jpeg_dct.py): encapsulated PixelData,
+    one frame per file, the frames of a series decoded on the GPU in one call per codec; other compressed (progressive or
+    arithmetic JPEG, HTJ2K, MPEG), deflated and big-endian files raise NotImplementedError;
   * single-frame, MONOCHROME2, SamplesPerPixel 1, BitsAllocated 16 (8 and 32 are read too);
   * one series per call: like `GetGDCMSeriesFileNames(dir)` without a series id, the FIRST series (smallest SeriesInstanceUID
     in sorted order) of the folder is taken, other series' files are ignored;
@@ -32,7 +34,7 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
 
-from . import jpeg2000, jpeg_lossless, jpeg_ls, rle_lossless
+from . import jpeg2000, jpeg_dct, jpeg_lossless, jpeg_ls, rle_lossless
 
 IMPLICIT_LE = "1.2.840.10008.1.2"
 EXPLICIT_LE = "1.2.840.10008.1.2.1"
@@ -84,7 +86,7 @@ _STRUCT = {"US": "<H", "SS": "<h", "UL": "<I", "SL": "<i", "FL": "<f", "FD": "<d
 
 
 # the codec of every encapsulated transfer syntax this reader decodes
-_CODECS = {ts: codec for codec in (jpeg_lossless, jpeg_ls, jpeg2000, rle_lossless) for ts in codec.SYNTAXES}
+_CODECS = {ts: codec for codec in (jpeg_lossless, jpeg_ls, jpeg2000, rle_lossless, jpeg_dct) for ts in codec.SYNTAXES}
 
 
 class DicomError(ValueError):
@@ -194,7 +196,7 @@ def read_file(path, stop_before_pixels: bool = False) -> Dict[str, Any]:
     if tsuid not in (IMPLICIT_LE, EXPLICIT_LE) and tsuid not in _CODECS:
         raise NotImplementedError(f"{path}: transfer syntax {tsuid} (compressed, deflated or big endian) is not supported; "
                                   "only implicit / explicit VR little endian (uncompressed), JPEG Lossless (Process 14), "
-                                  "JPEG-LS, JPEG 2000 and RLE Lossless are read")
+                                  "JPEG-LS, JPEG 2000, RLE Lossless and sequential DCT JPEG (baseline, extended) are read")
     explicit = tsuid != IMPLICIT_LE
     encapsulated = tsuid in _CODECS
     out["TransferSyntaxUID"] = tsuid
@@ -222,6 +224,10 @@ def read_file(path, stop_before_pixels: bool = False) -> Dict[str, Any]:
             if tsuid in jpeg_ls.SYNTAXES and not jpeg_ls.plausible_stream(frame):
                 raise NotImplementedError(f"{path}: transfer syntax {tsuid}: PixelData does not start like a JPEG-LS stream "
                                           "(SOI, then SOF55 before any other frame header)")
+            # And the DCT JPEG syntaxes: SOI, then SOF0 or SOF1 ahead of any other frame header.
+            if tsuid in jpeg_dct.SYNTAXES and not jpeg_dct.plausible_stream(frame):
+                raise NotImplementedError(f"{path}: transfer syntax {tsuid}: PixelData does not start like a sequential DCT JPEG "
+                                          "stream (SOI, then SOF0 or SOF1 before any other frame header)")
             out["PixelData"] = jpeg_lossless.CompressedFrame(frame)
             out["PixelData"].transfer_syntax = tsuid
             continue
@@ -358,8 +364,8 @@ def _slice_pixels(ds: Dict[str, Any], decoded: Optional[np.ndarray] = None) -> n
 def load_series(folder, ctx=None) -> Tuple[np.ndarray, Dict[str, Any], List[str]]:
     """Folder -> (volume [x, y, z] in the file axis order of the NIfTI that `sitk.WriteImage` would write, geometry, files).
     geometry: LPS `origin` (3), `spacing` (3), `direction` (3 x 3, columns = row-direction / column-direction / slice normal),
-    and the RAS `affine` (4 x 4) of the NIfTI file.  JPEG Lossless, JPEG-LS, JPEG 2000 and RLE Lossless slices are decoded on the device in one
-    batched call per codec (ctx: a device Context; default the process's `compute.inference.get_context()`, used only when
+    and the RAS `affine` (4 x 4) of the NIfTI file.  JPEG Lossless, JPEG-LS, JPEG 2000, RLE Lossless and DCT JPEG slices are decoded on the
+    device in one batched call per codec (ctx: a device Context; default the process's `compute.inference.get_context()`, used only when
     the series holds such a slice)."""
     files = series_file_names(folder)
     sl = [read_file(p) for p in files]

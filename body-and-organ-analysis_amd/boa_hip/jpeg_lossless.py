@@ -39,7 +39,7 @@ def _err(msg: str):
 class CompressedFrame(bytes):
     """The bytes of one compressed frame (the concatenated fragments of an encapsulated PixelData), tagged with the file's
     transfer syntax, which names the codec: what `dicom.read_file` returns as PixelData for a JPEG Lossless, JPEG-LS,
-    JPEG 2000 or RLE Lossless file."""
+    JPEG 2000, RLE Lossless or DCT JPEG file."""
     transfer_syntax: str = ""
 
 

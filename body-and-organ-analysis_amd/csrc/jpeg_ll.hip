@@ -30,12 +30,13 @@
 #include <algorithm>
 
 #include "common.h"
+#include "jpeg_huff.h"
 
 namespace {
 
-constexpr int LB = 9;                        // bits of the direct lookup (codes of up to LB bits: one LDS read)
+constexpr int LB = JH_LB;                    // bits of the direct lookup (codes of up to LB bits: one LDS read)
 constexpr int TW = BOA_LJ_TABLE_WORDS;
-constexpr int T_MAXCODE = 256, T_VALOFF = 274, T_HUFFVAL = 292;
+constexpr int T_MAXCODE = JH_T_MAXCODE, T_HUFFVAL = JH_T_HUFFVAL;
 constexpr unsigned BAD = 0xffffffffu;        // exit of a subsequence whose decode met an invalid code or ran past its segment
 constexpr int NT = 256;
 
@@ -46,60 +47,12 @@ __device__ __forceinline__ int lj_fail(int L, unsigned pos, unsigned seg_bits) {
     return (!L && pos + 16u <= seg_bits) ? BOA_LJ_INVALID_CODE : BOA_LJ_TRUNCATED;
 }
 
-// stream word k (bytes 4k .. 4k+3 of the frame, big-endian); bytes at or past `end` (the segment's end) read as 0xff, and the
-// load itself happens only when the word starts below `end` (the frame's bytes are padded to a multiple of 4 on the host)
-__device__ __forceinline__ unsigned lj_word(const unsigned* w, unsigned end, unsigned k) {
-    const unsigned b = 4u * k;
-    if (b >= end) return ~0u;
-    unsigned v = __builtin_bswap32(w[k]);
-    if (b + 4u > end) v |= ~0u >> (8u * (end - b));
-    return v;
-}
-
-// 64-bit window over the bit stream of one segment, refilled a word at a time
-struct BitReader {
-    const unsigned* w;
-    unsigned end;      // segment end (byte, relative to the frame)
-    unsigned wi;       // index of the word in the high half of `ab` (~0: nothing loaded)
-    unsigned long long ab;
-    __device__ __forceinline__ BitReader(const unsigned char* frame, unsigned end_byte)
-        : w((const unsigned*)frame), end(end_byte), wi(~0u), ab(0) {}
-    // 64 - (pos & 31) >= 33 valid bits starting at bit `pos` (a codeword is at most 16 + 15 = 31 bits)
-    __device__ __forceinline__ unsigned long long peek(unsigned pos) {
-        const unsigned k = pos >> 5;
-        if (k != wi) {
-            if (k == wi + 1u && wi != ~0u) ab = (ab << 32) | lj_word(w, end, k + 1u);
-            else ab = ((unsigned long long)lj_word(w, end, k) << 32) | lj_word(w, end, k + 1u);
-            wi = k;
-        }
-        return ab << (pos & 31u);
-    }
-};
-
 // One codeword at the head of `win`: returns its length in bits (0 = invalid code) and the difference (T.81 H.1.2.2, table
 // H.2: SSSS 16 carries no extra bits and means 32768).  T: table words (LDS or global).
 __device__ __forceinline__ int lj_decode(const unsigned* T, unsigned long long win, int& diff) {
-    const unsigned top = (unsigned)(win >> 32);
-    const unsigned li = top >> (32 - LB);
-    const unsigned e = (T[li >> 1] >> ((li & 1u) * 16u)) & 0xffffu;
-    int len, s;
-    if (e) {
-        len = (int)(e >> 8);
-        s = (int)(e & 0xffu);
-    } else {
-        len = 0;
-        s = 0;
-        for (int l = LB + 1; l <= 16; ++l) {       // canonical codes: the first length whose maxcode bounds the prefix
-            const int code = (int)(top >> (32 - l));
-            if (code <= (int)T[T_MAXCODE + l]) {
-                const unsigned vi = (unsigned)((int)T[T_VALOFF + l] + code) & 255u;
-                s = (int)((T[T_HUFFVAL + (vi >> 2)] >> ((vi & 3u) * 8u)) & 0xffu);
-                len = l;
-                break;
-            }
-        }
-        if (!len) return 0;
-    }
+    int s;
+    const int len = jh_symbol(T, (unsigned)(win >> 32), s);
+    if (!len) return 0;
     if (s == 0) {
         diff = 0;
         return len;

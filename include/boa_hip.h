@@ -633,6 +633,50 @@ int boa_ljpeg_decode(boa_ctx* ctx, const uint8_t* dev_data, size_t data_bytes, i
                      const int* segs, int n_subs, const int* subs, int n_tables, const uint32_t* tables, uint16_t* dev_out,
                      int* host_status, int serial);
 
+/* ------------------------------------------------------------------ DCT JPEG decode (jpeg_dct.hip) --- */
+/* DICOM transfer syntaxes 1.2.840.10008.1.2.4.50 / .51 = ITU T.81 sequential DCT (baseline Process 1, extended Process 2 / 4),
+ * Huffman, one component, P = 8 or 12, decoded to the pixels libjpeg gives by default (JDCT_ISLOW).  The host parses the markers,
+ * removes the byte stuffing and the RSTn markers (boa_hip/jpeg_dct.py) and passes, all as HOST arrays:
+ *   frames  int32 [n_frames][BOA_JD_FRAME_WORDS]: fields BOA_JD_F_* (byte offset of the frame's un-stuffed entropy-coded data
+ *           in dev_data: 4-aligned, its bytes padded to a multiple of 4 inside the buffer; restart interval in blocks, 0 = none;
+ *           indices of its DC and AC tables in `tables` and of its quantisation table in `qtables`); every frame is rows x cols,
+ *           = ceil(rows / 8) x ceil(cols / 8) blocks in raster order (one MCU is one 8 x 8 block);
+ *   segs    int32 [n_segs][4]: one per restart interval of each frame, in frame order: start byte, end byte (relative to the
+ *           frame), first block (= k x restart interval), index of its first subsequence;
+ *   subs    int32 [n_subs][2]: the split of every segment for the parallel decode, as for boa_ljpeg_decode;
+ *   tables  uint32 [n_tables][BOA_LJ_TABLE_WORDS]: DHT tables of either class expanded as for boa_ljpeg_decode (a value is the
+ *           DC table's SSSS or the AC table's RRRRSSSS byte);
+ *   qtables uint16 [n_qtables][64]: quantisation tables in natural (row-major) order.
+ * Decodes the batch (serial = 0: one workgroup per frame, parallel entropy decode; serial = 1: one lane per frame, the loop of
+ * T.81 F.2.2), then dequantises and inverse-transforms every block, into dev_out uint16 [n_frames][rows][cols], and returns the
+ * per-frame status (BOA_JD_OK / _TRUNCATED / _INVALID_CODE / _RUN_PAST_BLOCK / _BAD_SSSS / _TRAILING) in host_status; the
+ * blocks of a failed frame that were not reached decode as zero coefficients.  The coefficient workspace (2 B per padded sample)
+ * is capped at 1 GiB (BOA_JDCT_WS_KB KiB where that variable is set): longer series decode in chunks of frames inside the call.
+ * Every offset is validated on the host first (BOA_EINVAL); malformed streams are reported per frame, never by a fault.
+ * Synchronous. */
+#define BOA_JD_FRAME_WORDS 16
+#define BOA_JD_F_OFF_LO 0
+#define BOA_JD_F_OFF_HI 1
+#define BOA_JD_F_LEN 2
+#define BOA_JD_F_P 3
+#define BOA_JD_F_RESTART 4
+#define BOA_JD_F_DC_TABLE 5
+#define BOA_JD_F_AC_TABLE 6
+#define BOA_JD_F_QTABLE 7
+#define BOA_JD_F_SEG_FIRST 8
+#define BOA_JD_F_N_SEG 9
+#define BOA_JD_F_SUB_FIRST 10
+#define BOA_JD_F_N_SUB 11
+#define BOA_JD_OK 0
+#define BOA_JD_TRUNCATED 1
+#define BOA_JD_INVALID_CODE 2
+#define BOA_JD_RUN_PAST_BLOCK 3
+#define BOA_JD_BAD_SSSS 4
+#define BOA_JD_TRAILING 5
+int boa_jdct_decode(boa_ctx* ctx, const uint8_t* dev_data, size_t data_bytes, int n_frames, const int* frames, int rows, int cols,
+                    int n_segs, const int* segs, int n_subs, const int* subs, int n_tables, const uint32_t* tables, int n_qtables,
+                    const uint16_t* qtables, uint16_t* dev_out, int* host_status, int serial);
+
 /* ------------------------------------------------------------------ JPEG 2000 decode (j2k.hip) --- */
 /* DICOM transfer syntaxes 1.2.840.10008.1.2.4.90 / .91 holding a reversible (5/3) or an irreversible (9/7, scalar quantisation)
  * stream, ITU T.800, one component, one tile, code-block style 0.  The host parses the codestream and runs tier-2 (boa_hip/jpeg2000.py) and passes, as HOST arrays:
