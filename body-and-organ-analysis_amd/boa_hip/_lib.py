@@ -18,7 +18,7 @@ K_CONV_MFMA, K_CONV_FIRST, K_CONVT, K_NORM_FINALIZE, K_HEAD_ACCUM, K_ARGMAX, K_O
 K_NAMES = ["conv_mfma", "conv_first", "convT_mfma", "norm_finalize", "head_accum", "finalize_argmax", "other", "aggregation",
            "morphology", "resample", "copy_remap"]
 CNT_NAMES = ["head_mfma", "head_valu", "conv_ws", "conv_simple", "first_mfma", "first_valu", "f32", "conv_x3", "x3", "head_gather",
-             "copy_t", "bbox_vec"]
+             "copy_t", "bbox_vec", "finalize_vec8"]
 MAX_STAGES = 8
 
 
@@ -68,6 +68,7 @@ _PROTOS = {
     "boa_net_debug_activation": (i32, [vp, i32, i32, i32, i32, vp, ip, ip]),
     "boa_net_debug_layer": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, ip, ip, ip]),
     "boa_head_tile": (i32, [vp, vp, vp, i32, ip, i32, vp, vp, f32, vp, vp, vp, vp, ip, ip]),
+    "boa_head_tile_f32": (i32, [vp, i32, vp, u64, vp, i32, ip, i32, vp, vp, f32, vp, vp, vp, vp, ip, ip]),
     "boa_ct_normalize": (i32, [vp, vp, i32, vp, u64, f32, f32, f32, f32]),
     "boa_accumulate_tile": (i32, [vp, vp, vp, vp, vp, i32, ip, ip, ip]),
     "boa_finalize_labels": (i32, [vp, vp, vp, i32, ip, vp, i32, i32, i32, vp, i32, vp, ip, ip, vp]),

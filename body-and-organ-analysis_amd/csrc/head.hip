@@ -263,6 +263,11 @@ int launch_head(boa_ctx* ctx, const __half* act, const float* ss, int F0, const 
     }
     size_t pv = (size_t)P[0] * P[1] * P[2];
     size_t lds = ((size_t)C * F0 + C + 2 * F0) * 4;
+    // the VALU head keeps the weights of every class in LDS: more than the 64 KiB a kernel gets by default from 251 classes on at F0 = 64
+    // (k_head<64, 1>; boa_finalize_labels takes 255 at most, 33 KiB at F0 = 32), so that kernel's limit is raised for such a launch
+    BOA_REQUIRE(lds <= (F0 == 64 ? 160 : 64) * 1024, "head: features[0]=%d with %d classes needs %zu bytes of LDS", F0, C, lds);
+    if (lds > 64 * 1024)
+        BOA_HIP_TRY(hipFuncSetAttribute((const void*)k_head<64, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     double bytes = (double)pv * (2.0 * F0 + (logits_out ? 4.0 * C : (4.0 * (C + 1) + 2.0)));
     KernelTimer tm(ctx, BOA_K_HEAD_ACCUM, 2.0 * pv * F0 * C, bytes);
     const bool mfma_shape = F0 == 32 && C <= 31 && P[2] % 32 == 0 && ((uintptr_t)act) % 16 == 0;

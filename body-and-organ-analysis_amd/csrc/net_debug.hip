@@ -335,6 +335,19 @@ extern "C" int boa_head_tile(boa_ctx* ctx, const uint16_t* dev_act, const float*
                        dev_n, PV, start);
 }
 
+extern "C" int boa_head_tile_f32(boa_ctx* ctx, int kind, const float* dev_act_f32, size_t stride, const float* dev_ss, int F0,
+                                 const int P[3], int C, const float* dev_w, const float* dev_b, float slope, float* dev_logits_out,
+                                 const uint16_t* dev_gauss, uint16_t* dev_acc, uint16_t* dev_n, const int PV[3], const int start[3]) {
+    BOA_REQUIRE(ctx && dev_act_f32 && dev_ss && P && dev_w && dev_b, "boa_head_tile_f32: NULL argument");
+    BOA_REQUIRE(dev_logits_out || (dev_acc && dev_n && PV && start), "boa_head_tile_f32: neither logits_out nor accumulators given");
+    BOA_REQUIRE(kind == BOA_LK_HEAD_X3 || kind == BOA_LK_HEAD_F32, "boa_head_tile_f32: kind %d (12 = k_head_x3, 13 = k_head_f32)", kind);
+    if (kind == BOA_LK_HEAD_X3)
+        return launch_head_x3(ctx, dev_act_f32, dev_ss, F0, P, C, dev_w, dev_b, slope, dev_logits_out, dev_gauss, dev_acc, dev_n, PV, start,
+                              stride);
+    return launch_head_f32(ctx, dev_act_f32, dev_ss, F0, P, C, dev_w, dev_b, slope, dev_logits_out, dev_gauss, dev_acc, dev_n, PV, start,
+                           stride);
+}
+
 // fp32 NCDHW of one stored tile for the debug seams, with a transposed conv's output fold taken out again (x / fold is exact): through
 // the conversion's (scale, shift) path with scale 1 / fold, shift 0 and slope 1 (LeakyReLU with slope 1 is the identity)
 static int debug_to_nchw(boa_net* net, const ActLayout& lay, const void* tile, const float* ss, float fold, size_t vox, float* out) {

@@ -282,6 +282,7 @@ extern "C" int boa_finalize_labels_planes(boa_ctx* c, uint16_t* dev_acc, const u
         size_t nvec = vv / 8;
         hipLaunchKernelGGL(k_finalize_labels<8>, dim3((unsigned)((nvec + block - 1) / block)), dim3(block), 0,
                            c->stream, a);
+        c->counters[BOA_CNT_FINALIZE_VEC8]++;
     } else {
         hipLaunchKernelGGL(k_finalize_labels<1>, dim3((unsigned)((vv + block - 1) / block)), dim3(block), 0,
                            c->stream, a);

@@ -109,7 +109,8 @@ int boa_prof_get(boa_ctx* ctx, int kclass, double* total_ms, long long* launches
 #define BOA_CNT_HEAD_GATHER 9     /* k_gather_head* (fused head over all covering tiles; raw partial sums in the tile-sharded path) */
 #define BOA_CNT_COPY_T 10         /* k_copy3_t (LDS-tiled transposing form of boa_copy3; k_copy3 otherwise)             */
 #define BOA_CNT_BBOX_VEC 11       /* k_nonzero_bbox with its 16-byte vector loop (per-element loop otherwise)          */
-#define BOA_CNT_COUNT 12
+#define BOA_CNT_FINALIZE_VEC8 12 /* k_finalize_labels<8> (16-byte accesses; k_finalize_labels<1> otherwise)               */
+#define BOA_CNT_COUNT 13
 long long boa_debug_counter(boa_ctx* ctx, int which, int reset);
 
 /* ------------------------------------------------------------------ sliding-window arithmetic seams -- */
@@ -311,6 +312,12 @@ int boa_net_debug_layer(boa_net* net, int kind, int stage, int conv, int tile, f
 int boa_head_tile(boa_ctx* ctx, const uint16_t* dev_act, const float* dev_ss, int F0, const int P[3], int C,
                   const float* dev_w, const float* dev_b, float slope, float* dev_logits_out, const uint16_t* dev_gauss,
                   uint16_t* dev_acc, uint16_t* dev_n, const int PV[3], const int start[3]);
+/* The same seam for the fp32-input heads.  kind = BOA_LK_HEAD_X3 (k_head_x3: act = octet planes [4][stride voxels][8], F0 == 32, at most
+ * 32 classes) or BOA_LK_HEAD_F32 (k_head_f32: stride == 0: channels-last records [voxel][F0]; else octet planes [F0/8][stride voxels][8]).
+ * The remaining arguments are boa_head_tile's; the call forwards to the launcher the network driver uses and does nothing else. */
+int boa_head_tile_f32(boa_ctx* ctx, int kind, const float* dev_act_f32, size_t stride, const float* dev_ss, int F0, const int P[3], int C,
+                      const float* dev_w, const float* dev_b, float slope, float* dev_logits_out, const uint16_t* dev_gauss,
+                      uint16_t* dev_acc, uint16_t* dev_n, const int PV[3], const int start[3]);
 int boa_convtranspose_test(boa_ctx* ctx, const float* dev_in, int N, int Cin, const int dims[3],
                            const float* host_w, const float* host_b, int Cout, const int stride[3], float* dev_out);
 

@@ -42,7 +42,7 @@ def test_counter_names_keep_their_indices():
     from boa_hip import _lib
     assert _lib.CNT_NAMES[:10] == ["head_mfma", "head_valu", "conv_ws", "conv_simple", "first_mfma", "first_valu", "f32", "conv_x3", "x3",
                                    "head_gather"]
-    assert _lib.CNT_NAMES[10:] == ["copy_t", "bbox_vec"]
+    assert _lib.CNT_NAMES[10:] == ["copy_t", "bbox_vec", "finalize_vec8"]
 
 
 # ---- boa_copy3: the view cases ---------------------------------------------------------------------------------------------------
