@@ -164,7 +164,8 @@ class NumpyAggEngine:
         idx = np.arange(lab.size, dtype=np.int64).reshape(lab.shape)
         first = np.asarray(ndimage.minimum(idx, lab, index=np.arange(1, n + 1)), dtype=np.int64) if n else np.zeros(0, np.int64)
         sizes = np.bincount(lab.ravel(), minlength=n + 1)[1:]
-        roots = np.where(lab > 0, first[np.maximum(lab, 1) - 1], -1)
+        # (a slab without foreground has no `first` to index: all background)
+        roots = np.where(lab > 0, first[np.maximum(lab, 1) - 1], -1) if n else np.full(lab.shape, -1, dtype=np.int64)
         return {"roots": roots, "first": first, "sizes": sizes.astype(np.int64), "shape": lab.shape}
 
     def boundary_and_components(self, cc, z0):
