@@ -128,6 +128,7 @@ _PROTOS = {
     "boa_resample_nearest_u8": (i32, [vp, vp, ip, vp, ip]),
     "boa_resize_skimage_f32": (i32, [vp, vp, ip, vp, ip, i32, i32]),
     "boa_resize_logits_argmax": (i32, [vp, vp, i32, ip, ip, ip, ip, i32, vp, i32, vp]),
+    "boa_logits_to_probabilities": (i32, [vp, vp, i32, ip, ip, ip, ip, i32, ip, ip, ip, vp, vp, vp]),
     "boa_comm_available": (i32, []),
     "boa_comm_library": (C.c_char_p, []),
     "boa_comm_unique_id": (i32, [vp]),

@@ -328,7 +328,79 @@ class HipPredictor:
         job.begin(after_first_start)
         return job
 
-    def predict_segmentation(self, input_image: np.ndarray, lut: Optional[np.ndarray] = None) -> np.ndarray:
+    def predict_probabilities_device(self, dvol: DeviceBuffer, V, prob_out: DeviceBuffer, labels_out: Optional[DeviceBuffer] = None,
+                                     lut: Optional[np.ndarray] = None, work: Optional[dict] = None, resample_to=None,
+                                     bbox_lo=None, full_dims=None, perm=(0, 1, 2)):
+        """All folds -> class probabilities on device (convert_predicted_logits_to_segmentation_with_correct_shape with
+        return_probabilities=True, export_prediction.py:14-71).  dvol: fp32 [Cin,*V] resident.  The scatter form of the tile loop
+        and `boa_finalize_labels(write_logits=1)` per fold leave the normalised fp16 logits, their fold mean goes through
+        `boa_logits_to_probabilities`: pad reverted, `resample_to` = (out_dims, slice_axis) as in predict_segmentation_device,
+        the box inserted at `bbox_lo` of `full_dims` (default: the box is the grid) with background (1, 0, ..) around it, the
+        spatial axes permuted by `perm`.  prob_out: fp32 [C, *full_dims permuted]; labels_out (optional): uint8, the first maximum
+        of the PROBABILITIES through `lut`.  The gather form never materialises logits and is not used here."""
+        PV, below = sw.pad_amounts(V, self.geom.patch_size)
+        origins = sw.get_sliding_window_origins(PV, self.geom.patch_size, self.tile_step_size)
+        C_ = self.geom.num_classes
+        nvox = int(np.prod(PV))
+        nf = len(self.list_of_parameters)
+        own = work is None
+        work = work if work is not None else {}
+
+        def buf(name, nbytes):
+            b = work.get(name)
+            if b is None or b.nbytes < nbytes:
+                if b is not None:
+                    b.free()
+                b = self.ctx.alloc(nbytes)
+                work[name] = b
+            return b
+
+        ring = work.get("flag_ring")
+        if ring is not None:
+            flag = ring.next()
+        else:
+            flag = buf("flag", 4)
+            flag.zero()
+        lut_arr = None
+        if lut is not None:
+            lut_arr = np.zeros(256, dtype=np.uint8)
+            lut_arr[:len(lut)] = lut
+        lut_p = lut_arr.ctypes.data_as(C.c_void_p) if lut_arr is not None else None
+        acc = buf("acc", C_ * nvox * 2)
+        nacc = buf("n", nvox * 2)
+        fold = buf("fold", C_ * nvox * 2) if nf > 1 else None
+        for f in range(nf):
+            self._run_fold(dvol, V, PV, below, origins, acc, nacc, f)
+            last = f == nf - 1
+            check(self.lib.boa_finalize_labels(
+                self.ctx.h, acc.vp, nacc.vp, C_, int3(PV), fold.vp if fold else None, 0 if f == 0 else 1,
+                nf if (last and fold) else 0, 0 if fold else 1, None, 0, None, None, None, flag.vp), "boa_finalize_labels")
+        if ring is None and int(flag.download((1,), np.int32)[0]):
+            raise RuntimeError("Encountered inf in predicted array. Aborting...")
+        out_dims, slice_axis = resample_to if resample_to is not None else (None, -1)
+        box = list(out_dims) if out_dims is not None else list(V)
+        check(self.lib.boa_logits_to_probabilities(
+            self.ctx.h, (fold if fold else acc).vp, C_, int3(PV), int3(below), int3(V), int3(out_dims) if out_dims is not None else None,
+            int(slice_axis), int3(bbox_lo if bbox_lo is not None else (0, 0, 0)), int3(full_dims if full_dims is not None else box),
+            int3(perm), prob_out.vp, lut_p, labels_out.vp if labels_out is not None else None), "boa_logits_to_probabilities")
+        if own:
+            for b in work.values():
+                b.free()
+
+    def predict_segmentation(self, input_image: np.ndarray, lut: Optional[np.ndarray] = None, return_probabilities: bool = False):
+        """Labels uint8 [*V] of preprocessed data [Cin, *V].  return_probabilities=True: (labels, probabilities float32 [C, *V]),
+        the labels being the first maximum of the probabilities (label_handling.py:144-183); only the pad is reverted here."""
+        if return_probabilities:
+            V = list(input_image.shape[1:])
+            dvol = self.ctx.from_numpy(np.ascontiguousarray(input_image, dtype=np.float32))
+            lab = self.ctx.alloc(int(np.prod(V)))
+            prob = self.ctx.alloc(self.geom.num_classes * int(np.prod(V)) * 4)
+            try:
+                self.predict_probabilities_device(dvol, V, prob, lab, lut=lut)
+                return lab.download(tuple(V), np.uint8), prob.download((self.geom.num_classes, *V), np.float32)
+            finally:
+                for b in (dvol, lab, prob):
+                    b.free()
         V = list(input_image.shape[1:])
         dvol = self.ctx.from_numpy(np.ascontiguousarray(input_image, dtype=np.float32))
         lab = self.ctx.zeros(int(np.prod(V)))

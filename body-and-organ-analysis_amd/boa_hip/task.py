@@ -236,11 +236,14 @@ class SegmentationTask:
             check(ctx.lib.boa_label_overlay(ctx.h, part.vp, n, d_labels.vp), "boa_label_overlay")
 
     # ---- one (sub-)volume, device resident ----------------------------------------------------------------------
-    def _predict_part_device(self, part_xyz: DevArray, dst_xyz: DevArray, src_lo: int, src_hi: int, spacing_zyx=None):
+    def _predict_part_device(self, part_xyz: DevArray, dst_xyz: DevArray, src_lo: int, src_hi: int, spacing_zyx=None,
+                             save_probabilities=None):
         """`part_xyz`: (x,y,z) view of the (resampled) CT that TS would write to s0k_0000.nii.gz.  Its labels for the
         part-local z range [src_lo, src_hi) are written into `dst_xyz` (a zero-initialised (x,y,z) view of the same
         x/y extent and src_hi - src_lo slices).  nibabel reader view change, crop_to_nonzero and insert_crop_into_image
-        (export_prediction.py:44-47) are views + one device copy each way."""
+        (export_prediction.py:44-47) are views + one device copy each way.  `save_probabilities` (a path): every model's class
+        probabilities on this part's (z, y, x) grid are written there and the labels are taken from them
+        (`_predict_part_probabilities`)."""
         dt = part_xyz.dtype
         want = dt if dt in (np.dtype(np.int16), np.dtype(np.int32)) else np.dtype(np.float32)
         code = {np.dtype(np.int16): 0, np.dtype(np.float32): 1, np.dtype(np.int32): 2}[want]
@@ -254,6 +257,23 @@ class SegmentationTask:
         bbox_t = work.nonzero_bbox()
         full = all(b == [0, n] for b, n in zip(bbox_t, work.shape))
         crop = work if full else work.box(bbox_t).contiguous()
+        if save_probabilities is not None:
+            try:
+                lab_zyx = self._predict_part_probabilities(crop, work.shape, bbox_t, code, spacing_zyx, sp_t, save_probabilities)
+                try:
+                    k0, k1 = max(0, src_lo), min(lab_zyx.shape[0], src_hi)
+                    if k0 < k1:
+                        lab_zyx.slice(0, k0, k1).transpose((2, 1, 0)).copy_to(dst_xyz.slice(2, k0 - src_lo, k1 - src_lo))
+                finally:
+                    lab_zyx.free()
+            finally:
+                if crop is not work:
+                    crop.free()
+                if work is not zyx:
+                    work.free()
+                if zyx.buf is not part_xyz.buf:
+                    zyx.free()
+            return
         d_lab = DevArray.empty(self.ctx, crop.shape, np.uint8)
         try:
             self.predict_zyx_device(crop.buf, crop.shape, d_lab.buf, in_dtype=code, spacing_zyx=sp_t)
@@ -276,6 +296,73 @@ class SegmentationTask:
             if zyx.buf is not part_xyz.buf:
                 zyx.free()
 
+    def _predict_part_probabilities(self, crop: DevArray, full_shape, bbox_t, in_dtype: int, spacing_zyx, sp_t, path) -> DevArray:
+        """export_prediction_from_logits with save_probabilities (export_prediction.py:14-71, :99-102) for every model of the task
+        on one part: `crop` is the transposed, nonzero-cropped array, `full_shape` its shape before the crop, `bbox_t` the crop box.
+        Per model: the fold-mean logits -> `boa_logits_to_probabilities` (plan-spacing resampling reverted, the box put back into
+        `full_shape` with background (1, 0, ..) around it, transpose_backward applied), the float32 [C, z, y, x] array written to
+        `path` (np.savez_compressed, key `probabilities`) and the properties to `Path(path).with_suffix(".pkl")`; each model
+        overwrites the files of the one before (TS/nnunet.py:286-293).  Returns the task's labels on the part's (z, y, x) grid --
+        the first maximum of each model's probabilities, merged in part order for a multi-model task -- as a DevArray (caller frees)."""
+        from .device import FlagRing
+        ctx = self.ctx
+        shape = [int(v) for v in crop.shape]
+        full = [int(v) for v in full_shape]
+        n, n_full = int(np.prod(shape)), int(np.prod(full))
+        tb = [int(v) for v in self.parts[0][1].transpose_backward]
+        out_shape = [full[tb[i]] for i in range(3)]
+        lo = [int(b[0]) for b in bbox_t]
+        vol = self._work.get("vol")
+        if vol is None or vol.nbytes < n * 4:
+            if vol is not None:
+                vol.free()
+            vol = self._work["vol"] = ctx.alloc(n * 4)
+        ring = self._work.get("flag_ring")
+        if ring is None:
+            ring = self._work["flag_ring"] = FlagRing(ctx)
+        ring.reset()
+        labels = DevArray.zeros(ctx, out_shape, np.uint8)
+        part = DevArray.empty(ctx, out_shape, np.uint8) if self.multimodel else labels
+        # what this engine knows of nnU-Net's properties_dict (plain types only: no nibabel / SimpleITK objects)
+        props = {"spacing": None if spacing_zyx is None else [float(v) for v in spacing_zyx],
+                 "shape_before_cropping": tuple(full), "bbox_used_for_cropping": [[int(a), int(b)] for a, b in bbox_t],
+                 "shape_after_cropping_and_before_resampling": tuple(shape)}
+        try:
+            for task_id, cfg, p, lut in self.parts:
+                nc = p.geom.num_classes
+                prob = ctx.alloc(nc * n_full * 4)
+                vol_r = None
+                try:
+                    ip = cfg.intensity_properties["0"]
+                    check(ctx.lib.boa_ct_normalize(ctx.h, crop.buf.vp, in_dtype, vol.vp, n, ip["mean"], ip["std"], ip["percentile_00_5"],
+                                                   ip["percentile_99_5"]), "boa_ct_normalize")
+                    new_shape = shape if sp_t is None else nr.compute_new_shape(shape, sp_t, cfg.spacing)
+                    geo = dict(lut=lut, work=self._work, bbox_lo=lo, full_dims=full, perm=tb)
+                    if new_shape == shape:
+                        p.predict_probabilities_device(vol, shape, prob, part.buf, **geo)
+                    else:
+                        ax_in = nr.slice_axis_for(nr.checked_kwargs(cfg.extra, "data"), sp_t, cfg.spacing)
+                        ax_out = nr.slice_axis_for(nr.checked_kwargs(cfg.extra, "probabilities"), cfg.spacing, sp_t)
+                        vol_r = ctx.alloc(int(np.prod(new_shape)) * 4)
+                        check(ctx.lib.boa_resize_skimage_f32(ctx.h, vol.vp, int3(shape), vol_r.vp, int3(new_shape), 3, ax_in),
+                              "boa_resize_skimage_f32")
+                        p.predict_probabilities_device(vol_r, new_shape, prob, part.buf, resample_to=(shape, ax_out), **geo)
+                    if part is not labels:
+                        check(ctx.lib.boa_label_overlay(ctx.h, part.buf.vp, n_full, labels.buf.vp), "boa_label_overlay")
+                    ring.check()
+                    write_probabilities(path, prob.download((nc, *out_shape), np.float32), props)
+                finally:
+                    prob.free()
+                    if vol_r is not None:
+                        vol_r.free()
+        except BaseException:
+            labels.free()
+            raise
+        finally:
+            if part is not labels:
+                part.free()
+        return labels
+
     def predict_part_xyz(self, data_xyz: np.ndarray) -> np.ndarray:
         """One (sub-)volume as TS writes it to s0k_0000.nii.gz: (x,y,z) array -> uint8 labels (x,y,z)."""
         src = DevArray.from_numpy(self.ctx, self._supported(data_xyz))
@@ -297,11 +384,23 @@ class SegmentationTask:
     # ---- nnUNet_predict_image ------------------------------------------------------------------------------
     def predict_image(self, data, affine: np.ndarray, force_split: bool = False,
                       crop_mask: Optional[np.ndarray] = None, crop_addon=(3, 3, 3), axcodes: str = "RAS",
-                      return_device: bool = False):
+                      return_device: bool = False, save_probabilities=None):
         """CT array in file axis order + its affine -> uint8 label array on the same grid.  The volume is uploaded
         once; reorientation, crops, splits and restores are device views / copies, resampling and inference run on the
         device, only the final label volume comes back.  `data` may be a resident DevArray (not freed here);
-        `return_device=True` returns the labels as a contiguous DevArray (caller frees) instead of downloading."""
+        `return_device=True` returns the labels as a contiguous DevArray (caller frees) instead of downloading.
+
+        `save_probabilities` (a path; nnUNet_predict_image(save_probabilities=...), TS/nnunet.py:335,550,572): every model run
+        writes its softmax probabilities, float32 [C, z, y, x], with `np.savez_compressed(path, probabilities=...)` -- on the grid
+        of the image handed to nnU-Net (TS-resampled, canonical; crop-to-nonzero and plan-spacing resampling reverted,
+        transpose_backward applied) -- and a pickle next to it (`Path(path).with_suffix(".pkl")`) with the plain-dict subset of
+        nnU-Net's properties_dict this engine knows: `spacing`, `shape_before_cropping`, `bbox_used_for_cropping`,
+        `shape_after_cropping_and_before_resampling` (lists / tuples of numbers; no nibabel or SimpleITK objects).  As in the
+        reference (TS/nnunet.py:286-293) each model OVERWRITES the file, so a multi-model task ends with its last model's
+        array, and of a split image only part s01 is saved.  In this mode the labels are the first maximum of the saved
+        probabilities; the label merge of `total` is unchanged.  The sharded modes raise NotImplementedError."""
+        if save_probabilities is not None and (self.shard is not None or self.model_shard is not None):
+            raise NotImplementedError("save_probabilities with a tile- or model-sharded task")
         resident = isinstance(data, DevArray)
         if not resident:
             if data.ndim == 2:
@@ -386,11 +485,12 @@ class SegmentationTask:
             do_split = (np.prod(ss) > NR_VOXELS_THR and ss[2] > 200 and self.multimodel) or force_split
             if do_split:
                 parts, comb = split_bounds(ss[2])
-                for (lo, hi), (dst, srcsl) in zip(parts, comb):
+                for k, ((lo, hi), (dst, srcsl)) in enumerate(zip(parts, comb)):
                     a, b, _ = srcsl.indices(hi - lo)
-                    self._predict_part_device(img_rsp.slice(2, lo, hi), seg.slice(2, dst.start, dst.stop), a, b, sp_zyx)
+                    self._predict_part_device(img_rsp.slice(2, lo, hi), seg.slice(2, dst.start, dst.stop), a, b, sp_zyx,
+                                              save_probabilities=save_probabilities if k == 0 else None)
             else:
-                self._predict_part_device(img_rsp, seg, 0, ss[2], sp_zyx)
+                self._predict_part_device(img_rsp, seg, 0, ss[2], sp_zyx, save_probabilities=save_probabilities)
             if zoom is not None:                                         # back to the input grid (TS/nnunet.py:685-687)
                 if tuple(in_shape) != tuple(ss):
                     buf = rs.resample_nearest_device(ctx, seg.buf, ss, in_shape)
@@ -420,6 +520,21 @@ class SegmentationTask:
                     a.free()
 
 
+def write_probabilities(path, probabilities: np.ndarray, properties: dict) -> None:
+    """export_prediction_from_logits with save_probabilities (export_prediction.py:99-102): `<path>` gets
+    np.savez_compressed(probabilities=float32 [C, z, y, x]), `Path(path).with_suffix(".pkl")` the pickled properties.  Existing
+    files are overwritten (TS copies every model's pair over the last one's, TS/nnunet.py:286-293)."""
+    import pickle
+    from pathlib import Path
+    path = Path(path)
+    if probabilities.dtype != np.float32 or probabilities.ndim != 4:
+        raise ValueError("probabilities must be float32 [C, z, y, x]")
+    with open(path, "wb") as f:        # (a file object: numpy appends ".npz" to a path that lacks it)
+        np.savez_compressed(f, probabilities=probabilities)
+    with open(path.with_suffix(".pkl"), "wb") as f:
+        pickle.dump(dict(properties), f)
+
+
 def remove_outside_of_mask(ctx: Context, seg: np.ndarray, mask: np.ndarray, addon: int = 1) -> np.ndarray:
     """TS/postprocessing.py:101-131 on arrays of the same grid: dilate `mask != 0` `addon` times with the 6-neighbour cross
     (scipy.ndimage.binary_dilation(mask, iterations=addon)), clear `seg` outside.  Runs on the device."""
@@ -444,12 +559,14 @@ def remove_outside_of_mask(ctx: Context, seg: np.ndarray, mask: np.ndarray, addo
 def run_cascade_task(ctx: Context, task: str, data: np.ndarray, affine: np.ndarray, rough_models, task_models,
                      crop_names: Sequence[str], crop_addon=(3, 3, 3), max_batch: int = 16, rough_resample: float = 6.0,
                      remove_outside: Optional[Sequence[str]] = None, remove_outside_dilation: Optional[float] = None,
-                     precision: Optional[str] = None) -> np.ndarray:
+                     precision: Optional[str] = None, save_probabilities=None) -> np.ndarray:
     """Crop-cascade task of `--models all` (TS/python_api.py:670-757): a rough `total` segmentation at 6 mm (single model
     Dataset298; 3 mm / Dataset297 with robust_crop: `rough_resample`), labels = the `total` map -> crop mask = union of the
     `crop_names` structures -> the task's own model at native resolution on the cropped image -> labels on the input grid
     -> optionally cleared outside the dilated union of the `remove_outside` structures (TS/nnunet.py:711-716).
-    rough_models / task_models: [(task_id, ModelConfig, [weight blob per fold])] as `model_store.load_task_models` gives."""
+    rough_models / task_models: [(task_id, ModelConfig, [weight blob per fold])] as `model_store.load_task_models` gives.
+    `save_probabilities` (a path): passed to the TASK's model (`SegmentationTask.predict_image`: the probabilities of the cropped
+    image's grid); the rough model's are not kept -- in the reference every later model run overwrites the file."""
     rough = SegmentationTask(ctx, "total", rough_models, resample=rough_resample, multimodel=False, max_batch=max_batch, precision=precision)
     try:
         organ_seg = rough.predict_image(data, affine)
@@ -459,7 +576,7 @@ def run_cascade_task(ctx: Context, task: str, data: np.ndarray, affine: np.ndarr
     crop_mask = np.isin(organ_seg, [inv[n] for n in crop_names]).astype(np.uint8)
     t = SegmentationTask(ctx, task, task_models, resample=None, multimodel=False, max_batch=max_batch, precision=precision)
     try:
-        seg = t.predict_image(data, affine, crop_mask=crop_mask, crop_addon=crop_addon)
+        seg = t.predict_image(data, affine, crop_mask=crop_mask, crop_addon=crop_addon, save_probabilities=save_probabilities)
     finally:
         t.close()
     if remove_outside_dilation is not None:

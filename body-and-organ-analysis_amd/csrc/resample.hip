@@ -12,6 +12,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "resample_logits.h"
 
 #define NPAD 12
 
@@ -342,12 +343,6 @@ struct ResizeArgs {
     int gaxis;             // clip group axis (-1: whole volume)
 };
 
-// nearest source index along the slice axis: scipy map_coordinates(order=0, mode="nearest") at scale * (o + 0.5) - 0.5
-__device__ __forceinline__ int nearest_src(int o, double scale, int n_in) {
-    const double cc = scale * ((double)o + 0.5) - 0.5;
-    return min(max((int)floor(cc + 0.5), 0), n_in - 1);
-}
-
 __global__ __launch_bounds__(256) void k_resize_cubic_f32(const double* __restrict__ coef, ResizeArgs a, const unsigned* __restrict__ mm,
                                                           float* __restrict__ out) {
     const size_t n = (size_t)a.O[0] * a.O[1] * a.O[2];
@@ -386,65 +381,27 @@ __global__ __launch_bounds__(256) void k_resize_cubic_f32(const double* __restri
     out[i] = (float)t;
 }
 
-// double -> half with ONE rounding (numpy's npy_double_to_half): to float with round-to-odd, then RTNE to half
-__device__ __forceinline__ unsigned short d2h_rn(double d) {
-    float f = __double2float_rz(d);
-    if ((double)f != d) f = __uint_as_float(__float_as_uint(f) | 1u);
-    return f2us(f);
-}
-
 struct LogitsResizeArgs {
-    const unsigned short* logits;  // fp16 [C][L0][L1][L2]
-    int C, L[3], off[3], I[3], O[3];  // full grid, crop origin, crop dims (= resampled shape), output dims
-    int act[3];
-    double zf[3];
+    LogitsResizeGeom g;
     int merge;
     unsigned char lut[256];
 };
 
 // resampling_fn_probabilities (order 1) of every class at one output voxel + fp16 rounding + numpy argmax + lut / merge
+// (the taps and the rounded value: resample_logits.h, shared with prob.hip)
 __global__ __launch_bounds__(256) void k_resize_logits_argmax(LogitsResizeArgs a, unsigned char* __restrict__ labels) {
-    const size_t n = (size_t)a.O[0] * a.O[1] * a.O[2];
+    const size_t n = (size_t)a.g.O[0] * a.g.O[1] * a.g.O[2];
     size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     int o[3];
-    idx3(i, a.O[1], a.O[2], o[0], o[1], o[2]);
-    double w[3][2];
-    int i0[3], i1[3], nt[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        if (a.act[d]) {
-            const double cc = ((double)o[d] + 0.5) * a.zf[d] - 0.5;  // not clamped: the tap INDICES are (mode "nearest")
-            const double fl = floor(cc);
-            const double x = cc - fl;
-            w[d][0] = 1.0 - x;
-            w[d][1] = x;
-            i0[d] = min(max((int)fl, 0), a.I[d] - 1);
-            i1[d] = min(max((int)fl + 1, 0), a.I[d] - 1);
-            nt[d] = 2;
-        } else {
-            i0[d] = i1[d] = a.I[d] == a.O[d] ? o[d] : nearest_src(o[d], a.zf[d], a.I[d]);
-            nt[d] = 1;
-        }
-    }
-    const size_t lv = (size_t)a.L[0] * a.L[1] * a.L[2];
+    idx3(i, a.g.O[1], a.g.O[2], o[0], o[1], o[2]);
+    LogitsTaps t;
+    logits_taps(a.g, o, t);
     float best = 0.f;
     int bidx = 0;
     bool bnan = false;
-    for (int c = 0; c < a.C; ++c) {
-        const unsigned short* base = a.logits + (size_t)c * lv;
-        double t = 0.0;
-        for (int p = 0; p < nt[0]; ++p)
-            for (int q = 0; q < nt[1]; ++q)
-                for (int r = 0; r < nt[2]; ++r) {
-                    const int x = (p ? i1[0] : i0[0]) + a.off[0], y = (q ? i1[1] : i0[1]) + a.off[1], z = (r ? i1[2] : i0[2]) + a.off[2];
-                    double cf = (double)us2f(base[((size_t)x * a.L[1] + y) * a.L[2] + z]);
-                    if (a.act[0]) cf *= w[0][p];
-                    if (a.act[1]) cf *= w[1][q];
-                    if (a.act[2]) cf *= w[2][r];
-                    t += cf;
-                }
-        const float f = us2f(d2h_rn(t));  // `reshaped_final` has the logits' dtype: float16
+    for (int c = 0; c < a.g.C; ++c) {
+        const float f = us2f(logits_resampled(a.g, t, c));
         const bool isn = f != f;
         if (c == 0) {
             best = f;
@@ -535,18 +492,10 @@ extern "C" int boa_resize_logits_argmax(boa_ctx* c, const uint16_t* dev_logits, 
     BOA_REQUIRE(C >= 1 && C <= 255, "boa_resize_logits_argmax: C=%d out of range", C);
     BOA_REQUIRE(slice_axis >= -1 && slice_axis <= 2, "boa_resize_logits_argmax: slice_axis %d", slice_axis);
     LogitsResizeArgs a;
-    a.logits = dev_logits;
-    a.C = C;
     a.merge = merge;
-    for (int d = 0; d < 3; ++d) {
-        a.L[d] = grid_dims[d];
-        a.off[d] = crop_off ? crop_off[d] : 0;
-        a.I[d] = crop_dims ? crop_dims[d] : grid_dims[d];
-        a.O[d] = out_dims[d];
-        BOA_REQUIRE(a.off[d] >= 0 && a.I[d] >= 1 && a.off[d] + a.I[d] <= a.L[d] && a.O[d] >= 1, "boa_resize_logits_argmax: bad geometry on axis %d", d);
-        a.act[d] = d != slice_axis;
-        a.zf[d] = (double)a.I[d] / (double)a.O[d];
-    }
+    int bad = 0;
+    BOA_REQUIRE(logits_resize_geom(&a.g, dev_logits, C, grid_dims, crop_off, crop_dims, out_dims, slice_axis, &bad),
+                "boa_resize_logits_argmax: bad geometry on axis %d", bad);
     for (int i = 0; i < 256; ++i) a.lut[i] = host_lut ? host_lut[i] : (unsigned char)i;
     const size_t on = (size_t)out_dims[0] * out_dims[1] * out_dims[2];
     KernelTimer t(c, BOA_K_ARGMAX, 0, (double)on * (2.0 * C + 1.0));

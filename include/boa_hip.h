@@ -555,6 +555,33 @@ int boa_resize_logits_argmax(boa_ctx* ctx, const uint16_t* dev_logits, int C, co
                              const int* crop_dims, const int out_dims[3], int slice_axis, const uint8_t* host_lut, int merge,
                              uint8_t* dev_labels_out);
 
+/* convert_predicted_logits_to_segmentation_with_correct_shape(..., return_probabilities=True)
+ * (NN/inference/export_prediction.py:14-71) in one pass: the (fold-mean) fp16 logits [C][grid_dims] -- as boa_finalize_labels
+ * (write_logits = 1) or its fold mean leave them -- become fp32 class probabilities and, optionally, the labels taken from them.
+ *   crop_off / crop_dims   the network's output for the image (pad_nd_image reverted); NULL = the whole grid
+ *   out_dims, slice_axis   resampling_fn_probabilities (:25-33) of that box to out_dims: order 1, fp16-rounded, the arithmetic of
+ *                          boa_resize_logits_argmax; NULL or equal to the box: the logits are taken as they are
+ *   apply_inference_nonlin (NN/utilities/label_handling/label_handling.py:128-141): logits.float(), softmax over the classes in fp32:
+ *                          m = max, e_c = expf(x_c - m), s = sum in ascending class order, p_c = e_c / s (csrc/softmax_codes.h);
+ *                          |p - p64| <= (C + 110) 2^-24 p64 where p64 > 2^-100, else <= 2^-99
+ *   labels                 convert_probabilities_to_segmentation (:144-183): the first class whose p equals the maximum p (the argmax
+ *                          of the probabilities, not of the logits), through host_lut (uint8[256], NULL = identity)
+ *   bbox_lo / full_dims    revert_cropping_on_probabilities (:197-220): the box goes to bbox_lo of the pre-crop grid full_dims;
+ *                          outside it p_0 = 1, p_c = 0 for c > 0 and the label is lut[0]
+ *   perm                   transpose_backward on the spatial axes (export_prediction.py:56-58, numpy's transpose): output axis i is
+ *                          axis perm[i] of the pre-crop grid.  The identity (every shipped plan) without resampling is the fast
+ *                          path: one coalesced read per class plane, full-line stores; any other perm, and the resampled form, take a
+ *                          plain kernel of one thread per output voxel.
+ *   dev_prob               fp32 [C][full_dims permuted]; dev_labels: uint8 [full_dims permuted] or NULL
+ * A NaN logit gives NaN probabilities at that voxel and label lut[0]; +-65504, subnormals and equal columns are ordinary inputs (the
+ * caller has raised on inf).  BOA_EINVAL before anything is launched: C outside 1..255, a box that leaves its grid, perm not a
+ * permutation, slice_axis outside -1..2, an extent below 1 or a class plane of 2^31 voxels or more.  Asynchronous on the context's
+ * stream. */
+int boa_logits_to_probabilities(boa_ctx* ctx, const uint16_t* dev_logits, int C, const int grid_dims[3], const int* crop_off,
+                                const int* crop_dims, const int* out_dims, int slice_axis, const int bbox_lo[3],
+                                const int full_dims[3], const int perm[3], float* dev_prob, const uint8_t* host_lut,
+                                uint8_t* dev_labels);
+
 /* ------------------------------------------------------------------ several GPUs on one volume (RCCL) -- */
 /* The tile-sharded sliding window (boa_hip/tile_shard.py): ranks own blocks of tile rows of the sliding window
  * (NN/inference/predict_from_raw_data.py:523-558 orders the tiles axis 0 outermost; :611-614 adds them one after the other into
