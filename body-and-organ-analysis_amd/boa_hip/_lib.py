@@ -106,6 +106,8 @@ _PROTOS = {
     "boa_ccl_list_components": (i32, [vp, vp, u64, i32, vp, vp, ip]),
     "boa_scatter_u32": (i32, [vp, vp, vp, vp, i32]),
     "boa_ccl_fill_unmarked": (i32, [vp, vp, vp, u64, C.c_uint32, vp, i32]),
+    "boa_label_blobs6": (i32, [vp, vp, i32, i32, i32, vp, vp, ip]),
+    "boa_label_blobs_filter": (i32, [vp, vp, vp, u64, vp, C.c_uint32, C.c_uint32, vp]),
     "boa_label_select": (i32, [vp, vp, u64, i32, ip, vp]),
     "boa_fill_holes_2d": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
     "boa_binary_dilate_cross": (i32, [vp, vp, vp, vp, i32, i32, i32, i32]),

@@ -1,7 +1,8 @@
 """File-level mirror of BOA/compute/inference.py: `compute_all_models` (:50-144) with the reference's signature,
 outputs and folder contract, on the device engine.
 
-Supported models: `total`, `bca`, `body_parts`, `body_regions` and the crop-cascade models of `--models all`
+Supported models: `total` (with the TotalSegmentator parameters `remove_small_blobs` and `body_seg`), `body`, `bca`, `body_parts`,
+`body_regions` and the crop-cascade models of `--models all`
 (lung_vessels, cerebral_bleed, hip_implant, pleural_pericard_effusion, liver_vessels, and the licensed
 heartchambers_highres: rough 6 mm / robust 3 mm `total` -> crop -> native-resolution model [-> remove_outside_of_mask],
 TS/python_api.py:670-757).  Anything else raises NotImplementedError -- nothing is silently skipped.  Weights come from
@@ -19,7 +20,7 @@ import numpy as np
 from .. import label_maps, model_store, nifti, orientation
 from ..device import Context
 from ..pipeline import BcaPipelineHip
-from ..task import SegmentationTask, run_cascade_task
+from ..task import SegmentationTask, run_cascade_task, run_with_body_crop
 from .config import resolve_device
 from .constants import BASE_MODELS
 from .measurements import compute_measurements
@@ -94,7 +95,7 @@ def compute_all_models(
         "num_slices": int(shape[2]),
         "num_slices_resampled": convert_resampling_slices(slices=shape[-1], current_sampling=spacing[-1], target_resampling=1.5),
     }
-    unsupported = [m for m in measurement_models if m != "total" and m not in model_store.CASCADE_MODELS]
+    unsupported = [m for m in measurement_models if m not in ("total", "body") and m not in model_store.CASCADE_MODELS]
     if unsupported:
         raise NotImplementedError(f"models {unsupported} are not implemented on the device")
     segmentation_folder.mkdir(parents=True, exist_ok=True)
@@ -105,8 +106,9 @@ def compute_all_models(
     ct = _ct_array(data, hdr)
     fast = bool(totalsegmentator_params.get("fast", False))
     for name in measurement_models:
-        _segment_one(ctx, name, ct, affine, hdr, segmentation_folder, fast, recompute)
-    _write_total_measurements(ctx, ct_path, segmentation_folder, measurement_models, cnr_adjustment, recompute)
+        _segment_one(ctx, name, ct, affine, hdr, segmentation_folder, fast, recompute, totalsegmentator_params)
+    # (`body` is a mask of the patient, not an organ model: BOA has no measurement label table for it)
+    _write_total_measurements(ctx, ct_path, segmentation_folder, [m for m in measurement_models if m != "body"], cnr_adjustment, recompute)
     bca_slices = convert_resampling_slices(slices=shape[-1], current_sampling=spacing[-1], target_resampling=5.0)
     for name in sorted(BASE_MODELS & set(models_to_compute)):
         _run_bca_model(ctx, name, ct, affine, hdr, segmentation_folder, fast_bca, bca_params,
@@ -115,8 +117,11 @@ def compute_all_models(
     return stats
 
 
-def _segment_one(ctx, name, ct, affine, hdr, folder, fast, recompute):
-    """One TotalSegmentator-style model -> `<name>.nii.gz` with the label table in the header extension."""
+def _segment_one(ctx, name, ct, affine, hdr, folder, fast, recompute, totalsegmentator_params=None):
+    """One TotalSegmentator-style model -> `<name>.nii.gz` with the label table in the header extension.  Of the TotalSegmentator
+    parameters `remove_small_blobs` (`total`, `body`) and `body_seg` (`total`) are honoured; both default to off."""
+    params = totalsegmentator_params or {}
+    small_blobs = bool(params.get("remove_small_blobs", False))
     target = folder / f"{name}.nii.gz"
     logger.info("Computing model %s...", name)
     if target.is_file() and not recompute:
@@ -124,13 +129,25 @@ def _segment_one(ctx, name, ct, affine, hdr, folder, fast, recompute):
         return
     if name == "total":
         key = "total_fast" if fast else "total"
-        task = SegmentationTask(ctx, "total", model_store.load_task_models(key), resample=model_store.TASKS[key]["resample"],
-                                multimodel=not fast)
+        if params.get("body_seg", False):                       # TS/python_api.py:739-764
+            seg = run_with_body_crop(ctx, "total", ct, affine, model_store.load_task_models("body_fast"), model_store.load_task_models(key),
+                                     resample=model_store.TASKS[key]["resample"], multimodel=not fast, remove_small_blobs=small_blobs)
+        else:
+            task = SegmentationTask(ctx, "total", model_store.load_task_models(key), resample=model_store.TASKS[key]["resample"],
+                                    multimodel=not fast)
+            try:
+                seg = task.predict_image(ct, affine, remove_small_blobs=small_blobs)
+            finally:
+                task.close()
+        names = label_maps.CLASS_MAP_TOTAL
+    elif name == "body":                                        # TS/python_api.py:272-287
+        key = "body_fast" if fast else "body"
+        task = SegmentationTask(ctx, "body", model_store.load_task_models(key), resample=model_store.TASKS[key]["resample"], multimodel=False)
         try:
-            seg = task.predict_image(ct, affine)
+            seg = task.predict_image(ct, affine, remove_small_blobs=small_blobs)
         finally:
             task.close()
-        names = label_maps.CLASS_MAP_TOTAL
+        names = label_maps.class_map("body")
     else:
         if fast:
             raise ValueError(f"task {name} does not work with option --fast")   # TS/python_api.py:242 ff.

@@ -96,9 +96,17 @@ def measurement_label_map(model_name: str) -> dict:
     return {k: int(v) for k, v in _data()["label_maps"][model_name]}
 
 
+# TS/map_to_binary.py class_map["body"] (:358-361): the task of Dataset299 / Dataset300
+CLASS_MAP_BODY = {1: "body_trunc", 2: "body_extremities"}
+_BUILTIN_CLASS_MAPS = {"body": CLASS_MAP_BODY}
+
+
 def class_map(task: str) -> dict:
-    """{label id: structure name} of a task (TS/map_to_binary.py class_map)."""
-    return {int(k): v for k, v in _data()["class_maps"][task].items()}
+    """{label id: structure name} of a task (TS/map_to_binary.py class_map): from the data file, else the tables of this module."""
+    maps = _data()["class_maps"]
+    if task in maps:
+        return {int(k): v for k, v in maps[task].items()}
+    return dict(_BUILTIN_CLASS_MAPS[task])
 
 
 def output_name(model_name: str) -> str:

@@ -20,6 +20,10 @@ TASKS: Dict[str, dict] = {
                    "folds": [0, 1, 2, 3, 4], "resample_only_thickness": True},
     "body_regions": {"task_id": [542], "resample": 5.0, "trainer": "nnUNetTrainerNoMirroring", "folds": [0, 1, 2, 3, 4],
                      "resample_only_thickness": True},
+    # the body task (TS/python_api.py:272-287): its blob post-processing is part of SegmentationTask.predict_image; `body_fast` is
+    # also the rough mask of `body_seg` (TS/python_api.py:739-749)
+    "body": {"task_id": [299], "resample": 1.5, "trainer": "nnUNetTrainer", "folds": [0]},
+    "body_fast": {"task_id": [300], "resample": 6.0, "trainer": "nnUNetTrainer", "folds": [0]},
     # rough organ segmentation for the crop cascade (TS/python_api.py:685-707): single model, `total` label map
     "total_6mm": {"task_id": [298], "resample": 6.0, "trainer": "nnUNetTrainer_4000epochs_NoMirroring", "folds": [0]},
     # crop-cascade tasks of `--models all` (TS/python_api.py:236-259,311-329): native resolution (resample None), cropped

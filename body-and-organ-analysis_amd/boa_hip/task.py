@@ -381,10 +381,30 @@ class SegmentationTask:
             return data
         return data.astype(np.float64)   # what get_fdata() hands to the reference
 
+    def _postprocess_model_grid(self, seg: DevArray, zooms, remove_small: bool):
+        """TS/nnunet.py:595-617 in place on the model-grid labels `seg` (contiguous (x, y, z), z fastest: the array order the
+        reference's scipy.ndimage.label sees): ONE 6-connected labelling of all labels (boa_label_blobs6), then one filter call per
+        reference step.  The steps only ever remove whole blobs, so the sizes of the first labelling hold for the later steps.
+        Thresholds: mm^3 / voxel volume in float32 (`blobs.size_threshold_voxels`)."""
+        from . import blobs
+        cm = label_maps.class_map(self.task_name)
+        lab = blobs.BlobLabelling(self.ctx, seg)
+        try:
+            if self.task_name == "body":
+                lab.filter(blobs.modes_for(cm, ["body_trunc"], blobs.MODE_LARGEST))
+                lo, hi = blobs.interval_bounds([blobs.size_threshold_voxels(50000, zooms), 1e10])
+                lab.filter(blobs.modes_for(cm, ["body_extremities"], blobs.MODE_INTERVAL), lo, hi)
+            if remove_small:
+                lo, hi = blobs.interval_bounds([blobs.size_threshold_voxels(200, zooms), 1e10])
+                lab.filter(blobs.modes_for(cm, list(cm.values()), blobs.MODE_INTERVAL), lo, hi)
+        finally:
+            lab.free()
+
     # ---- nnUNet_predict_image ------------------------------------------------------------------------------
     def predict_image(self, data, affine: np.ndarray, force_split: bool = False,
                       crop_mask: Optional[np.ndarray] = None, crop_addon=(3, 3, 3), axcodes: str = "RAS",
-                      return_device: bool = False, save_probabilities=None):
+                      return_device: bool = False, save_probabilities=None, remove_small_blobs: bool = False,
+                      model_grid_out: Optional[dict] = None):
         """CT array in file axis order + its affine -> uint8 label array on the same grid.  The volume is uploaded
         once; reorientation, crops, splits and restores are device views / copies, resampling and inference run on the
         device, only the final label volume comes back.  `data` may be a resident DevArray (not freed here);
@@ -398,9 +418,18 @@ class SegmentationTask:
         `shape_after_cropping_and_before_resampling` (lists / tuples of numbers; no nibabel or SimpleITK objects).  As in the
         reference (TS/nnunet.py:286-293) each model OVERWRITES the file, so a multi-model task ends with its last model's
         array, and of a split image only part s01 is saved.  In this mode the labels are the first maximum of the saved
-        probabilities; the label merge of `total` is unchanged.  The sharded modes raise NotImplementedError."""
+        probabilities; the label merge of `total` is unchanged.  The sharded modes raise NotImplementedError.
+
+        Blob post-processing on the model grid (TS/nnunet.py:595-617), between the recombination of the parts and the nearest
+        resample back (`_postprocess_model_grid`): task `body` always keeps the largest blob of `body_trunc` and drops the blobs
+        of `body_extremities` of at most 50 000 mm^3; `remove_small_blobs=True` then drops, for every label of the task's class
+        map, the blobs of at most 200 mm^3.  Not implemented for the sharded modes.  `model_grid_out` (a dict; test seam): gets
+        `labels`, the model-grid label array (x, y, z) BEFORE that post-processing, and `zooms`, its float32 header zooms."""
         if save_probabilities is not None and (self.shard is not None or self.model_shard is not None):
             raise NotImplementedError("save_probabilities with a tile- or model-sharded task")
+        blob_pp = bool(remove_small_blobs) or self.task_name == "body"
+        if blob_pp and (self.shard is not None or self.model_shard is not None):
+            raise NotImplementedError("blob post-processing (remove_small_blobs, task body) with a tile- or model-sharded task")
         resident = isinstance(data, DevArray)
         if not resident:
             if data.ndim == 2:
@@ -491,6 +520,11 @@ class SegmentationTask:
                                               save_probabilities=save_probabilities if k == 0 else None)
             else:
                 self._predict_part_device(img_rsp, seg, 0, ss[2], sp_zyx, save_probabilities=save_probabilities)
+            zooms_rsp = np.asarray(sp_rsp, dtype=np.float32)            # header zooms of the model-grid image (float32 pixdim)
+            if model_grid_out is not None:
+                model_grid_out["labels"], model_grid_out["zooms"] = seg.download(), zooms_rsp
+            if blob_pp:
+                self._postprocess_model_grid(seg, zooms_rsp, bool(remove_small_blobs))
             if zoom is not None:                                         # back to the input grid (TS/nnunet.py:685-687)
                 if tuple(in_shape) != tuple(ss):
                     buf = rs.resample_nearest_device(ctx, seg.buf, ss, in_shape)
@@ -586,3 +620,30 @@ def run_cascade_task(ctx: Context, task: str, data: np.ndarray, affine: np.ndarr
         vx = int(remove_outside_dilation / np.mean(zooms))
         seg = remove_outside_of_mask(ctx, seg, remove_mask, addon=vx)
     return seg
+
+
+def body_crop_mask(ctx: Context, data, affine: np.ndarray, body_models, max_batch: int = 16, precision: Optional[str] = None) -> np.ndarray:
+    """The rough body segmentation of `body_seg` (TS/python_api.py:739-749): Dataset300 at 6 mm as task `body` with its blob
+    post-processing, binarised (`save_binary`, TS/nnunet.py:700-701) -> uint8 0 / 1 mask on the input grid."""
+    body = SegmentationTask(ctx, "body", body_models, resample=6.0, multimodel=False, max_batch=max_batch, precision=precision)
+    try:
+        seg = body.predict_image(data, affine)
+    finally:
+        body.close()
+    return (seg > 0).astype(np.uint8)
+
+
+def run_with_body_crop(ctx: Context, task: str, data, affine: np.ndarray, body_models, task_models, resample: Optional[float] = None,
+                       multimodel: Optional[bool] = None, crop_addon=(3, 3, 3), max_batch: int = 16, precision: Optional[str] = None,
+                       remove_small_blobs: bool = False, force_split: bool = False) -> np.ndarray:
+    """`body_seg=True` (TS/python_api.py:739-764), TotalSegmentator's speed-up for large images: the task runs on the image cropped
+    to the bounding box of the rough body mask (`body_crop_mask`) plus `crop_addon` mm (the API's default [3, 3, 3]); outside the
+    box the result is 0, and an empty body mask gives an all-zero result without running the task's models (the early return of
+    `predict_image`).  body_models / task_models: [(task_id, ModelConfig, [weight blob per fold])]."""
+    crop_mask = body_crop_mask(ctx, data, affine, body_models, max_batch=max_batch, precision=precision)
+    t = SegmentationTask(ctx, task, task_models, resample=resample, multimodel=multimodel, max_batch=max_batch, precision=precision)
+    try:
+        return t.predict_image(data, affine, force_split=force_split, crop_mask=crop_mask, crop_addon=crop_addon,
+                               remove_small_blobs=remove_small_blobs)
+    finally:
+        t.close()

@@ -1,5 +1,6 @@
-// Shared pieces of the connected-component kernels (ccl_bytes.hip, ccl_bits.hip) and of the background union-find of the byte fill
-// (morph.hip): the atomic union-find on global memory, its LDS form, and the labelling of one 32 x 16 x 16 tile in LDS.
+// Shared pieces of the connected-component kernels (ccl_bytes.hip, ccl_bits.hip, ccl_labels.hip) and of the background union-find of
+// the byte fill (morph.hip): the atomic union-find on global memory, its LDS form, the labelling of one 32 x 16 x 16 tile in LDS (the
+// binary form; ccl_labels.hip has its own run and row rules and shares the union-find, the counting and the last pass).
 // Forest invariant everywhere: parent index <= own index, root = smallest linear index of the component.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -152,6 +153,60 @@ __device__ __forceinline__ void ccl_tile_count_runs(unsigned int* cnt, int tid, 
             atomicAdd(&cnt[myroot[k]], (unsigned int)len);
         }
     }
+}
+
+// ---- the last pass of a labelling (boa_ccl26, boa_label_blobs6), one thread per voxel i of a 256-thread block -----------------
+// after the border unions: every voxel points at its global root; a tile-local root that is not the global root hands its count
+// over (one global atomic per tile-local component instead of one per voxel)
+__device__ __forceinline__ void ccl_resolve_voxel(size_t i, size_t n, int* L, unsigned int* sizes, int* n_comp) {
+    int is_root = 0;
+    unsigned int pend_c = 0u;
+    int pend_root = 0;
+    if (i < n) {
+        const int p0 = L[i];
+        if (p0 >= 0) {
+            int root = p0, p = L[root];
+            while (p != root) {
+                root = p;
+                p = L[root];
+            }
+            if (root != p0) L[i] = root;
+            if (root == (int)i) {
+                is_root = 1;
+            } else {
+                const unsigned int c = sizes[i];
+                if (c) {
+                    pend_c = c;
+                    pend_root = root;
+                    // (agent-scope store, not a plain one: the same line may hold a root's count that other XCDs are adding to)
+                    __hip_atomic_store(&sizes[i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
+        }
+    }
+    // hand the counts over: body-sized masks are ONE giant component, so nearly every tile-local root of the volume adds to the same
+    // word -- a device-scope atomic per tile-local component serialises at that address (resolve took 0.2 ms on a mask of scattered
+    // specks and 2 ms on a solid one).  Two rounds of wave-level aggregation on the most common root of the wave, then the rest one
+    // by one.
+    {
+        const int lane = threadIdx.x & 63;
+#pragma unroll 1
+        for (int round = 0; round < 2; ++round) {
+            const unsigned long long act = __ballot(pend_c != 0u);
+            if (!act) break;
+            const int leader = __ffsll((long long)act) - 1;
+            const int r0 = __shfl(pend_root, leader);
+            const bool mine = pend_c != 0u && pend_root == r0;
+            unsigned int sum = mine ? pend_c : 0u;
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) sum += __shfl_xor(sum, m);
+            if (lane == leader) atomicAdd(&sizes[r0], sum);
+            if (mine) pend_c = 0u;
+        }
+        if (pend_c) atomicAdd(&sizes[pend_root], pend_c);
+    }
+    const unsigned long long b = __ballot(is_root);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(n_comp, __popcll(b));
 }
 
 // ---- unions across tile faces (ccl_border_voxel on bytes, cb_border_voxel on mask words and component ids) -----------------------

@@ -452,6 +452,25 @@ int boa_ccl_list_components(boa_ctx* ctx, const uint32_t* dev_sizes, size_t n, i
 int boa_scatter_u32(boa_ctx* ctx, uint32_t* dev_dst, const int32_t* host_idx, const uint32_t* host_val, int m);
 int boa_ccl_fill_unmarked(boa_ctx* ctx, const int32_t* dev_roots, const uint32_t* dev_sizes, size_t n, uint32_t mark,
                           uint8_t* dev_seg, int fill_value);
+/* Blobs of a label volume, 6-connectivity (scipy.ndimage.label's default structure, as TS/postprocessing.py:13-98 calls it on
+ * `data == idx`, label by label): a component is a maximal face-connected set of voxels with the same non-zero value, so ONE
+ * labelling of the uint8 volume [D0][D1][D2] (D2 fastest) serves every label (csrc/ccl_labels.hip).
+ *   roots dev int32 [n]: linear index of the component's first voxel in raster order (= the order in which scipy numbers the
+ *         components of a label), -1 on background;
+ *   sizes dev uint32 [n]: component size stored at the root's index, 0 elsewhere;
+ *   host_n_components (optional): number of components of all labels; without it the call does not synchronise.
+ * D0, D1 <= 65535 and D0 * D1 * D2 < 2^31. */
+int boa_label_blobs6(boa_ctx* ctx, const uint8_t* dev_labels, int D0, int D1, int D2, int32_t* dev_roots, uint32_t* dev_sizes,
+                     int* host_n_components);
+/* The blob filters on boa_label_blobs6's result, in place on the volume that was labelled, per label value v by host_mode[v]:
+ *   0  leave label v alone;
+ *   1  size interval (remove_small_blobs): clear the components with size <= lo or size > hi;
+ *   2  keep largest (keep_largest_blob): clear every component of label v but the largest (tie: the smallest root, which is
+ *      np.argmax's first).
+ * host_mode[0] is ignored.  Voxels that an earlier call cleared stay cleared; the sizes of the remaining components still hold, so
+ * several calls may follow one labelling.  lo, hi do not matter without a mode 1. */
+int boa_label_blobs_filter(boa_ctx* ctx, const int32_t* dev_roots, const uint32_t* dev_sizes, size_t n, const uint8_t host_mode[256],
+                           uint32_t lo, uint32_t hi, uint8_t* dev_labels_inout);
 /* mask_out = (labels == value) [mode 0] | (lut-free) labels > 0 [mode 1] | labels in {a,b,c} [mode 2, vals[3]] */
 int boa_label_select(boa_ctx* ctx, const uint8_t* dev_labels, size_t n, int mode, const int vals[3],
                      uint8_t* dev_mask_out);
