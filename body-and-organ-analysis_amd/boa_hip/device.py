@@ -93,6 +93,16 @@ def _pinned_atexit():
     _SHUTDOWN[0] = True
 
 
+def _download(b, shape, dtype, skip_empty: bool = False) -> np.ndarray:
+    """The bytes at `b.ptr` (a DeviceBuffer or a BufferView) as a host array; page-locked from PINNED_MIN_BYTES on."""
+    nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
+    out = b.ctx.pinned_empty(shape, dtype) if nbytes >= PINNED_MIN_BYTES else np.empty(shape, dtype=dtype)
+    assert b.nbytes >= out.nbytes, (out.nbytes, b.nbytes)
+    if out.nbytes or not skip_empty:
+        check(b.ctx.lib.boa_d2h(b.ctx.h, out.ctypes.data_as(C.c_void_p), C.c_void_p(b.ptr), out.nbytes))
+    return out
+
+
 class DeviceBuffer:
     """A hipMalloc'ed buffer owned by a Context; freed explicitly or when garbage collected."""
 
@@ -119,20 +129,19 @@ class DeviceBuffer:
 
     def upload(self, arr: np.ndarray):
         a = np.ascontiguousarray(arr)
-        assert a.nbytes <= self.nbytes, (a.nbytes, self.nbytes)
+        assert self.nbytes >= a.nbytes, (a.nbytes, self.nbytes)
         check(self.ctx.lib.boa_h2d(self.ctx.h, C.c_void_p(self.ptr), a.ctypes.data_as(C.c_void_p), a.nbytes))
         return self
 
     def download(self, shape, dtype) -> np.ndarray:
-        nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
-        out = self.ctx.pinned_empty(shape, dtype) if nbytes >= PINNED_MIN_BYTES else np.empty(shape, dtype=dtype)
-        assert out.nbytes <= self.nbytes, (out.nbytes, self.nbytes)
-        check(self.ctx.lib.boa_d2h(self.ctx.h, out.ctypes.data_as(C.c_void_p), C.c_void_p(self.ptr), out.nbytes))
-        return out
+        return _download(self, shape, dtype)
 
     @property
     def vp(self):
         return C.c_void_p(self.ptr)
+
+
+INF_MESSAGE = "Encountered inf in predicted array. Aborting..."      # predict_from_raw_data.py:622-625
 
 
 class FlagRing:
@@ -168,7 +177,7 @@ class FlagRing:
         flags = self.buf.download((self.SLOTS,), np.int32)
         if flags[:used].any():
             self.buf.zero()
-            raise RuntimeError("Encountered inf in predicted array. Aborting...")
+            raise RuntimeError(INF_MESSAGE)
 
     def free(self):
         if self.buf is not None:
@@ -181,7 +190,7 @@ class BufferView:
     contiguous ranges of its buffer)."""
 
     def __init__(self, buf, byte_offset: int, nbytes: int):
-        assert 0 <= byte_offset and byte_offset + nbytes <= buf.nbytes, (byte_offset, nbytes, buf.nbytes)
+        assert 0 <= byte_offset and buf.nbytes >= byte_offset + nbytes, (byte_offset, nbytes, buf.nbytes)
         self._keep = buf
         self.ctx = buf.ctx
         self.ptr = buf.ptr + int(byte_offset)
@@ -199,12 +208,100 @@ class BufferView:
             check(self.ctx.lib.boa_memset(self.ctx.h, self.vp, 0, self.nbytes))
 
     def download(self, shape, dtype) -> np.ndarray:
-        nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
-        out = self.ctx.pinned_empty(shape, dtype) if nbytes >= PINNED_MIN_BYTES else np.empty(shape, dtype=dtype)
-        assert out.nbytes <= self.nbytes, (out.nbytes, self.nbytes)
-        if out.nbytes:
-            check(self.ctx.lib.boa_d2h(self.ctx.h, out.ctypes.data_as(C.c_void_p), self.vp, out.nbytes))
-        return out
+        return _download(self, shape, dtype, skip_empty=True)     # (an empty window may lie at the very end of its buffer)
+
+
+class Workspace:
+    """The persistent, named device scratch of one task: lives as long as its owner, is reused across volumes and models, and is
+    freed as a whole (`free()`, or leaving a `with` block).  `ring=True`: it also owns the task's FlagRing (`.ring`, allocated on
+    first use -- by the thread that drives the context); the task resets it before a volume's first model and checks it once
+    after the last, and the predictors handed this workspace take their inf flags from it (`flag()`)."""
+
+    def __init__(self, ctx, ring: bool = False):
+        self.ctx = ctx
+        self._bufs: dict = {}
+        self._turns: dict = {}
+        self._ring = None
+        self._has_ring = bool(ring)
+
+    @property
+    def ring(self):
+        if self._ring is None and self._has_ring:
+            self._ring = FlagRing(self.ctx)
+        return self._ring
+
+    def buf(self, name: str, nbytes: int, init=None):
+        """The buffer `name` with room for `nbytes`: grow-only -- reused when large enough, otherwise freed and allocated anew with
+        exactly `nbytes`.  `init(buffer)` fills a fresh allocation whose contents the caller relies on."""
+        b = self._bufs.get(name)
+        if b is None or b.nbytes < nbytes:
+            if b is not None:
+                b.free()
+            b = self._bufs[name] = self.ctx.alloc(nbytes)
+            if init is not None:
+                init(b)
+        return b
+
+    def turn(self, name: str) -> int:
+        """0, 1, 0, .. on successive calls, per name (which of two alternating buffer sets is next)."""
+        t = self._turns.get(name, 0)
+        self._turns[name] = t ^ 1
+        return t
+
+    def flag(self):
+        """A zeroed int32 inf flag for one predict call: the next slot of the ring (the ring's owner reads it), else this
+        workspace's own flag (the caller reads it)."""
+        if self.ring is not None:
+            return self.ring.next()
+        f = self.buf("flag", 4)
+        f.zero()
+        return f
+
+    def free(self):
+        for b in self._bufs.values():
+            b.free()
+        self._bufs = {}
+        if self._ring is not None:
+            self._ring.free()
+            self._ring = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+
+class Scope:
+    """Call-lifetime ownership of device arrays / buffers: `own(a)` records `a`, `release(a)` forgets everything that shares
+    `a`'s buffer (the array a function returns), and leaving the `with` block -- also by an exception -- frees each distinct
+    underlying buffer once (two views of one buffer are one free)."""
+
+    def __init__(self):
+        self._owned: list = []
+
+    @staticmethod
+    def _buffer(a):
+        return getattr(a, "buf", a)      # (DevArray views share `.buf`; a DeviceBuffer is its own)
+
+    def own(self, a):
+        self._owned.append(a)
+        return a
+
+    def release(self, a):
+        self._owned = [o for o in self._owned if self._buffer(o) is not self._buffer(a)]
+        return a
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        seen = set()
+        for a in self._owned:
+            if id(self._buffer(a)) not in seen:
+                seen.add(id(self._buffer(a)))
+                a.free()
+        self._owned = []
 
 
 class Context:

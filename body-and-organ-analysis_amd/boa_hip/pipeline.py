@@ -13,6 +13,7 @@ NIfTI files of the reference's folder contract are written by the caller (I/O is
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import time
 from typing import Dict, Optional, Sequence, Tuple
@@ -21,7 +22,7 @@ import numpy as np
 
 from . import bca, label_maps, orientation
 from .devarray import DevArray
-from .device import Context
+from .device import Context, Scope
 from .plans import ModelConfig
 from .task import SegmentationTask
 
@@ -148,15 +149,10 @@ class BcaPipelineHip:
     def inference(self, task_name: str, ct: np.ndarray, affine: np.ndarray, force_split: bool = False,
                   crop: Optional[np.ndarray] = None, raw: Optional[np.ndarray] = None) -> np.ndarray:
         """`inference()` for one BCA task on host arrays (file axis order) -> cleaned labels (file axis order)."""
-        d_ct = DevArray.from_numpy(self.tasks[task_name].ctx if task_name in self.tasks else self.ctx, SegmentationTask._supported(ct))
-        try:
-            out = self._inference_device(task_name, d_ct, np.asarray(affine, dtype=np.float64), force_split, crop, raw)
-            try:
-                return out.download()
-            finally:
-                out.free()
-        finally:
-            d_ct.free()
+        with Scope() as sc:
+            d_ct = sc.own(DevArray.from_numpy(self.tasks[task_name].ctx if task_name in self.tasks else self.ctx, SegmentationTask._supported(ct)))
+            out = sc.own(self._inference_device(task_name, d_ct, np.asarray(affine, dtype=np.float64), force_split, crop, raw))
+            return out.download()
 
     def _both_nets_two_streams(self, d_ct, affine, force_split, raw_regions, done_regions, keep, crop_body=False):
         """body_parts on `parts_ctx` (worker thread), body_regions on `ctx` (calling thread); hand-over by value: the CT is
@@ -209,6 +205,22 @@ class BcaPipelineHip:
             d_parts = parts_here()
         return d_parts, d_regions
 
+    @contextlib.contextmanager
+    def _shared_resample_cache(self, shared: bool):
+        """Both nets see the same CT at the same (sx, sy, 5 mm) grid: with `shared` the cubic resampling runs once (unless the
+        second net works on a body crop).  The cache lives for ONE resident volume: its buffers are released on the way out."""
+        rs_cache: dict = {}
+        if shared:
+            for t in self.tasks.values():
+                t.resample_cache = rs_cache
+        try:
+            yield
+        finally:
+            for t in self.tasks.values():
+                t.resample_cache = None
+            for b in rs_cache.values():
+                b.free()
+
     def _lps_zyx(self, d: DevArray, affine: np.ndarray, dtype=None) -> DevArray:
         """BCA/io.py:78-94 `process_image` as a device view: reorient to LPS, SimpleITK array order (z,y,x), contiguous."""
         cur = "".join(orientation.aff2axcodes(affine))
@@ -231,19 +243,16 @@ class BcaPipelineHip:
             ct_f64 = ct_for_stats(ct, "bca: CT")[1]
             if ct_f64 and np.asarray(ct).dtype not in (np.int16, np.float64):
                 ct = np.asarray(ct, dtype=np.float64)      # what get_fdata() hands to the reference
-        d_ct = DevArray.from_numpy(self.ctx, SegmentationTask._supported(ct))
-        d_tot = None if total_seg is None else DevArray.from_numpy(self.ctx, np.ascontiguousarray(total_seg, dtype=np.uint8))
-        res = None
-        try:
+        with Scope() as sc:
+            d_ct = sc.own(DevArray.from_numpy(self.ctx, SegmentationTask._supported(ct)))
+            d_tot = None if total_seg is None else sc.own(DevArray.from_numpy(self.ctx, np.ascontiguousarray(total_seg, dtype=np.uint8)))
             res = self.run_resident(d_ct, affine, d_tot, median_filtering, examined_body_region, crop_body, force_split, raw_parts,
                                     raw_regions, done_parts, done_regions, ct_f64=ct_f64)
+            for k in ("body_parts", "body_regions", "tissues"):
+                sc.own(res[k])
             return {"body_parts": res["body_parts"].download(), "body_regions": res["body_regions"].download(),
                     "tissues": res["tissues"].download(), "bca_measurements": res["bca_measurements"],
                     "vertebrae": res["vertebrae"], "examined_body_part": res["examined_body_part"]}
-        finally:
-            for a in [d_ct, d_tot] + ([res[k] for k in ("body_parts", "body_regions", "tissues")] if res else []):
-                if a is not None:
-                    a.free()
 
     def run_resident(self, d_ct: DevArray, affine: np.ndarray, d_total: Optional[DevArray] = None,
                      median_filtering: bool = False, examined_body_region: Optional[str] = None, crop_body: bool = False,
@@ -256,32 +265,26 @@ class BcaPipelineHip:
         `ct_f64`: the tissue stage reads the CT as float64 (a CT that is not int16-exact) instead of int16."""
         ctx = self.ctx
         affine = np.asarray(affine, dtype=np.float64)
-        live = []
-        keep = []
-        # both nets see the same CT at the same (sx, sy, 5 mm) grid: the cubic resampling runs once (unless the second net
-        # works on a body crop)
-        rs_cache: dict = {}
         two_streams = self.parts_ctx is not None and raw_parts is None and done_parts is None and "body_parts" in self.tasks
-        if not two_streams:
-            for t in self.tasks.values():
-                t.resample_cache = rs_cache
-        try:
+        with Scope() as sc, self._shared_resample_cache(not two_streams):
             if two_streams:
-                d_parts, d_regions = self._both_nets_two_streams(d_ct, affine, force_split, raw_regions, done_regions, keep, crop_body)
+                handed: list = []      # what the two lanes hand over, also when one of them fails afterwards
+                try:
+                    d_parts, d_regions = self._both_nets_two_streams(d_ct, affine, force_split, raw_regions, done_regions, handed, crop_body)
+                finally:
+                    for a in handed:
+                        sc.own(a)
             else:
-                d_parts = self._inference_device("body_parts", d_ct, affine, force_split, None, raw_parts, done_parts)
-                keep.append(d_parts)
+                d_parts = sc.own(self._inference_device("body_parts", d_ct, affine, force_split, None, raw_parts, done_parts))
                 crop = d_parts.download() if crop_body else None
-                d_regions = self._inference_device("body_regions", d_ct, affine, force_split, crop, raw_regions, done_regions)
-                keep.append(d_regions)
+                d_regions = sc.own(self._inference_device("body_regions", d_ct, affine, force_split, crop, raw_regions, done_regions))
             with _Stage(ctx, "LPS reload, body-part flags, vertebrae, tissues + tables, JSON"):
                 _, laff = orientation.with_axcodes(np.empty(d_ct.shape, dtype=np.uint8), affine, "LPS")
                 sp = np.sqrt(np.sum(np.asarray(laff, dtype=np.float64)[:3, :3] ** 2, axis=0))
                 spacing = (float(sp[0]), float(sp[1]), float(sp[2]))
-                ct_l = self._lps_zyx(d_ct, affine, np.float64 if ct_f64 else np.int16)
-                rg_l = self._lps_zyx(d_regions, affine)
-                pt_l = self._lps_zyx(d_parts, affine)
-                live += [ct_l, rg_l, pt_l]
+                ct_l = sc.own(self._lps_zyx(d_ct, affine, np.float64 if ct_f64 else np.int16))
+                rg_l = sc.own(self._lps_zyx(d_regions, affine))
+                pt_l = sc.own(self._lps_zyx(d_parts, affine))
                 present = bca.slice_label_presence(ctx, rg_l.buf, rg_l.shape)
                 if examined_body_region:
                     flags = dict(abdomen=False, neck=False, thorax=False)
@@ -296,8 +299,7 @@ class BcaPipelineHip:
                 if callable(d_total):
                     d_total = d_total()
                 if d_total is not None:
-                    tot_l = self._lps_zyx(d_total, affine)
-                    live.append(tot_l)
+                    tot_l = sc.own(self._lps_zyx(d_total, affine))
                     vertebrae = bca.create_vertebrae_info(ctx, None, label_maps.CLASS_MAP_TOTAL, flags, d_total=tot_l.buf,
                                                           shape=tot_l.shape)
                 if self.agg is not None and self.agg[0].world > 1 and not median_filtering:
@@ -309,23 +311,10 @@ class BcaPipelineHip:
                     js, d_tis = bca.bca_measurements_device(ctx, ct_l.buf, rg_l.buf, pt_l.buf, ct_l.shape, spacing, vertebrae or None,
                                                             True, median_filtering, "LPS", flags if examined_body_region else None,
                                                             ct_f64=ct_f64)
-                tis_l = DevArray(ctx, d_tis, ct_l.shape, np.uint8)
-                live.append(tis_l)
+                tis_l = sc.own(DevArray(ctx, d_tis, ct_l.shape, np.uint8))
                 # back to the file's axis order: (z,y,x) LPS -> (x,y,z) LPS -> file orientation
                 back = orientation.ornt_transform(orientation.axcodes2ornt("LPS"), orientation.io_orientation(affine))
                 tissues = tis_l.transpose((2, 1, 0)).apply_orientation(back).contiguous(force_copy=True)
-                keep.append(tissues)
-            out = {"body_parts": d_parts, "body_regions": d_regions, "tissues": tissues, "bca_measurements": js,
-                   "vertebrae": vertebrae, "examined_body_part": flags}
-            keep = []
-            return out
-        finally:
-            for t in self.tasks.values():
-                t.resample_cache = None
-            for b in rs_cache.values():
-                b.free()
-            seen = set()
-            for a in live + keep:
-                if id(a.buf) not in seen:
-                    seen.add(id(a.buf))
-                    a.free()
+            # (the three label volumes are the caller's from here on)
+            return {"body_parts": sc.release(d_parts), "body_regions": sc.release(d_regions), "tissues": tissues, "bca_measurements": js,
+                    "vertebrae": vertebrae, "examined_body_part": flags}

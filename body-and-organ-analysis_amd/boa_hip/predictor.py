@@ -13,6 +13,7 @@ accumulators do not fit (the reference would retry with host-side results, :663-
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import List, Optional, Sequence
 
@@ -20,8 +21,56 @@ import numpy as np
 
 from . import sliding_window as sw
 from ._lib import BOA_EINVAL, check, int3
-from .device import Context, DeviceBuffer
+from .device import INF_MESSAGE, Context, DeviceBuffer, Scope, Workspace
 from .plans import NetGeometry
+
+
+def _lut256(lut) -> Optional[np.ndarray]:
+    """A label lookup table as the 256-entry uint8 table the kernels index (entries past len(lut) map to 0)."""
+    if lut is None:
+        return None
+    arr = np.zeros(256, dtype=np.uint8)
+    arr[:len(lut)] = lut
+    return arr
+
+
+class _Window:
+    """The sliding-window geometry of one predict call, computed once: padded extent `PV`, pad `below`, tile `origins`, class / voxel
+    / fold counts, whether the pad has to be cropped away, and the 256-entry LUT.  The object owns the LUT array: `lut_p` points
+    into it and is handed to every launch of the call."""
+
+    def __init__(self, pred: "HipPredictor", V, lut=None):
+        self.V = list(V)
+        self.PV, self.below = sw.pad_amounts(self.V, pred.geom.patch_size)
+        self.origins = sw.get_sliding_window_origins(self.PV, pred.geom.patch_size, pred.tile_step_size)
+        self.C_, self.nvox, self.nv = pred.geom.num_classes, int(np.prod(self.PV)), int(np.prod(self.V))
+        self.nf = len(pred.list_of_parameters)
+        self.crop = any(b != 0 for b in self.below) or list(self.PV) != self.V
+        self.lut = _lut256(lut)
+        self.lut_p = self.lut.ctypes.data_as(C.c_void_p) if self.lut is not None else None
+
+
+def _checked(work) -> Optional[Workspace]:
+    if work is not None and not isinstance(work, Workspace):
+        raise TypeError(f"work must be a device.Workspace or None, not {type(work).__name__}")
+    return work
+
+
+@contextlib.contextmanager
+def _scratch(ctx: Context, work):
+    """The caller's Workspace, or (None) a private one for this call that is released on the way out, errors included."""
+    if _checked(work) is not None:
+        yield work
+    else:
+        with Workspace(ctx) as private:
+            yield private
+
+
+def _raise_if_inf(flag, ring=None, message: str = INF_MESSAGE):
+    """The reference's inf check (predict_from_raw_data.py:622-625): reads `flag` and raises when it is set.  `ring`: the flag is a
+    slot of that FlagRing, whose owner reads every slot once per volume -- nothing is read here."""
+    if ring is None and int(flag.download((1,), np.int32)[0]):
+        raise RuntimeError(message)
 
 
 class HipPredictor:
@@ -184,22 +233,18 @@ class HipPredictor:
         V, PV, below, origins = self._setup(input_image)
         C_ = self.geom.num_classes
         nvox = int(np.prod(PV))
-        dvol = self.ctx.from_numpy(np.ascontiguousarray(input_image, dtype=np.float32))
-        acc = self.ctx.alloc(C_ * nvox * 2)
-        nacc = self.ctx.alloc(nvox * 2)
-        flag = self.ctx.zeros(4)
-        try:
+        with Scope() as sc:
+            dvol = sc.own(self.ctx.from_numpy(np.ascontiguousarray(input_image, dtype=np.float32)))
+            acc = sc.own(self.ctx.alloc(C_ * nvox * 2))
+            nacc = sc.own(self.ctx.alloc(nvox * 2))
+            flag = sc.own(self.ctx.zeros(4))
             self._run_fold(dvol, V, PV, below, origins, acc, nacc, fold)
             check(self.lib.boa_finalize_labels(self.ctx.h, acc.vp, nacc.vp, C_, int3(PV), None, 0, 0, 1, None, 0, None,
                                                None, None, flag.vp), "boa_finalize_labels")
-            if int(flag.download((1,), np.int32)[0]):
-                raise RuntimeError("Encountered inf in predicted array. Aborting... If this problem persists, reduce "
-                                   "value_scaling_factor in compute_gaussian or increase the dtype of predicted_logits "
-                                   "to fp32")
+            _raise_if_inf(flag, message="Encountered inf in predicted array. Aborting... If this problem persists, reduce "
+                                        "value_scaling_factor in compute_gaussian or increase the dtype of predicted_logits "
+                                        "to fp32")
             logits = acc.download((C_, *PV), np.uint16).view(np.float16)
-        finally:
-            for b in (dvol, acc, nacc, flag):
-                b.free()
         sl = (slice(None),) + tuple(slice(b, b + v) for b, v in zip(below, V))
         return np.ascontiguousarray(logits[sl])
 
@@ -218,9 +263,10 @@ class HipPredictor:
         return pred
 
     def predict_segmentation_device(self, dvol: DeviceBuffer, V, labels_out: DeviceBuffer, lut: Optional[np.ndarray] = None,
-                                    merge: bool = False, work: Optional[dict] = None, shard=None, resample_to=None):
+                                    merge: bool = False, work: Optional[Workspace] = None, shard=None, resample_to=None):
         """All folds -> labels on device.  dvol: fp32 [Cin,*V] resident; labels_out: uint8 [*V] resident (updated in
-        place when merge=True).  `work` may carry preallocated acc / n / fold buffers to reuse across models.
+        place when merge=True).  `work` (device.Workspace): the caller's scratch, reused across models and volumes; None = a
+        private one, released before this returns or raises.
         `shard` (tile_shard.TileShard): this volume is shared by the ranks of shard.comm -- every rank holds the volume,
         runs its block of tile rows, exchanges the overlap slabs and ends with the same labels_out.
         `resample_to` = (out_dims, slice_axis): the volume is at the plans' spacing and the labels are wanted on another
@@ -228,87 +274,56 @@ class HipPredictor:
         `out_dims` and reduced to labels there (`boa_resize_logits_argmax`); labels_out is then uint8 [*out_dims]."""
         if shard is not None and shard.comm.world > 1:
             return self._predict_segmentation_sharded(dvol, V, labels_out, lut, merge, work, shard, resample_to)
-        PV, below = sw.pad_amounts(V, self.geom.patch_size)
-        origins = sw.get_sliding_window_origins(PV, self.geom.patch_size, self.tile_step_size)
-        C_ = self.geom.num_classes
-        nvox = int(np.prod(PV))
-        nf = len(self.list_of_parameters)
-        own = work is None
-        work = work if work is not None else {}
-
-        def buf(name, nbytes):
-            b = work.get(name)
-            if b is None or b.nbytes < nbytes:
-                if b is not None:
-                    b.free()
-                b = self.ctx.alloc(nbytes)
-                work[name] = b
-            return b
-
-        ring = work.get("flag_ring")   # (device.FlagRing of the calling task: the inf flag is read once per volume, not per model)
-        if ring is not None:
-            flag = ring.next()
-        else:
-            flag = buf("flag", 4)
-            flag.zero()
-        lut_arr = None
-        if lut is not None:
-            lut_arr = np.zeros(256, dtype=np.uint8)
-            lut_arr[:len(lut)] = lut
-        lut_p = lut_arr.ctypes.data_as(C.c_void_p) if lut_arr is not None else None
-        crop = any(b != 0 for b in below) or list(PV) != list(V)
+        w = _Window(self, V, lut)
         direct = resample_to is None
-        if direct and self.use_gather_head and self._predict_labels_fused(dvol, V, PV, below, origins, labels_out, lut_p, merge, crop, flag, buf):
-            if ring is None and int(flag.download((1,), np.int32)[0]):
-                raise RuntimeError("Encountered inf in predicted array. Aborting...")
-            if own:
-                for b in work.values():
-                    b.free()
-            return
-        acc = buf("acc", C_ * nvox * 2)
-        nacc = buf("n", nvox * 2)
-        fold = buf("fold", C_ * nvox * 2) if nf > 1 else None
-        for f in range(nf):
-            self._run_fold(dvol, V, PV, below, origins, acc, nacc, f, gather=True)
-            last = f == nf - 1
-            # resampled path: keep the normalised (fold-mean) logits -- in `acc` for one fold, in `fold` otherwise -- and
-            # take the argmax after the resampling
-            check(self.lib.boa_finalize_labels(
-                self.ctx.h, acc.vp, nacc.vp, C_, int3(PV), fold.vp if fold else None, 0 if f == 0 else 1,
-                nf if (last and fold) else 0, 0 if (direct or fold) else 1, lut_p,
-                1 if merge else 0, labels_out.vp if (last and direct) else None, int3(below) if crop else None,
-                int3(V) if crop else None, flag.vp), "boa_finalize_labels")
-        if ring is None and int(flag.download((1,), np.int32)[0]):
-            raise RuntimeError("Encountered inf in predicted array. Aborting...")
-        if not direct:
-            out_dims, slice_axis = resample_to
-            check(self.lib.boa_resize_logits_argmax(self.ctx.h, (fold if fold else acc).vp, C_, int3(PV), int3(below), int3(V),
-                                                    int3(out_dims), int(slice_axis), lut_p, 1 if merge else 0, labels_out.vp),
-                  "boa_resize_logits_argmax")
-        if own:
-            for b in work.values():
-                b.free()
+        with _scratch(self.ctx, work) as ws:
+            flag = ws.flag()       # (a slot of the calling task's ring: the inf flag is read once per volume, not per model)
+            if direct and self.use_gather_head and self._predict_labels_fused(dvol, w, labels_out, merge, flag, ws):
+                _raise_if_inf(flag, ws.ring)
+                return
+            acc, nacc, fold = self._planes(w, ws)
+            for f in range(w.nf):
+                self._run_fold(dvol, w.V, w.PV, w.below, w.origins, acc, nacc, f, gather=True)
+                last = f == w.nf - 1
+                # resampled path: keep the normalised (fold-mean) logits -- in `acc` for one fold, in `fold` otherwise -- and
+                # take the argmax after the resampling
+                check(self.lib.boa_finalize_labels(
+                    self.ctx.h, acc.vp, nacc.vp, w.C_, int3(w.PV), fold.vp if fold else None, 0 if f == 0 else 1,
+                    w.nf if (last and fold) else 0, 0 if (direct or fold) else 1, w.lut_p,
+                    1 if merge else 0, labels_out.vp if (last and direct) else None, int3(w.below) if w.crop else None,
+                    int3(w.V) if w.crop else None, flag.vp), "boa_finalize_labels")
+            _raise_if_inf(flag, ws.ring)
+            if not direct:
+                out_dims, slice_axis = resample_to
+                check(self.lib.boa_resize_logits_argmax(self.ctx.h, (fold if fold else acc).vp, w.C_, int3(w.PV), int3(w.below), int3(w.V),
+                                                        int3(out_dims), int(slice_axis), w.lut_p, 1 if merge else 0, labels_out.vp),
+                      "boa_resize_logits_argmax")
 
-    def _predict_labels_fused(self, dvol, V, PV, below, origins, labels_out, lut_p, merge, crop, flag, buf) -> bool:
+    @staticmethod
+    def _planes(w: _Window, ws: Workspace):
+        """The scatter form's fp16 planes from the workspace: accumulators, weight sums, and the fold sum of an ensemble (else None)."""
+        acc = ws.buf("acc", w.C_ * w.nvox * 2)
+        nacc = ws.buf("n", w.nvox * 2)
+        return acc, nacc, (ws.buf("fold", w.C_ * w.nvox * 2) if w.nf > 1 else None)
+
+    def _predict_labels_fused(self, dvol, w: _Window, labels_out, merge, flag, ws: Workspace) -> bool:
         """The gather form of the tile loop (boa_net_predict_labels_fold): every tile's last decoder activation goes to a stash,
         one pass per fold walks the volume with the fp16 running sums in registers and ends in the labels -- no accumulator
         planes.  Same arithmetic and rounding order as the scatter loop below (labels bit-identical).  False = not applicable
         (exact mode, mirroring, > 32 classes, features[0] != 32, irregular tile list, stash does not fit): the caller runs
         the scatter loop."""
-        nf = len(self.list_of_parameters)
         self._ensure_net(0)
-        op = origins.ctypes.data_as(C.POINTER(C.c_int))
-        if not self.lib.boa_net_labels_supported(self._net, op, origins.shape[0]):
+        op = w.origins.ctypes.data_as(C.POINTER(C.c_int))
+        if not self.lib.boa_net_labels_supported(self._net, op, w.origins.shape[0]):
             return False
-        C_, nvox = self.geom.num_classes, int(np.prod(PV))
-        fold = buf("fold", C_ * nvox * 2) if nf > 1 else None
+        fold = ws.buf("fold", w.C_ * w.nvox * 2) if w.nf > 1 else None      # (shared with the scatter form on purpose)
         g = self._gaussian()
-        for f in range(nf):
+        for f in range(w.nf):
             self._ensure_net(f)
             rc = self.lib.boa_net_predict_labels_fold(
-                self._net, dvol.vp, int3(V), int3(PV), int3(below), op, origins.shape[0], g.vp if g else None,
-                fold.vp if fold else None, f, nf, lut_p, 1 if merge else 0, labels_out.vp, int3(below) if crop else None,
-                int3(V) if crop else None, flag.vp)
+                self._net, dvol.vp, int3(w.V), int3(w.PV), int3(w.below), op, w.origins.shape[0], g.vp if g else None,
+                fold.vp if fold else None, f, w.nf, w.lut_p, 1 if merge else 0, labels_out.vp, int3(w.below) if w.crop else None,
+                int3(w.V) if w.crop else None, flag.vp)
             if rc == -3 and f == 0:      # BOA_ENOMEM: the stash does not fit -> scatter loop
                 return False
             check(rc, "boa_net_predict_labels_fold")
@@ -325,11 +340,15 @@ class HipPredictor:
         (`after_first_start`: called once this model's first fold is queued -- the previous model's finish), so that with the RCCL
         transport the exchange of model k runs under the tiles of model k + 1.  The accumulators alternate between two slots."""
         job = _ShardedJob(self, dvol, V, labels_out, lut, merge, work, shard, resample_to)
-        job.begin(after_first_start)
+        try:
+            job.begin(after_first_start)
+        except BaseException:
+            job.close()
+            raise
         return job
 
     def predict_probabilities_device(self, dvol: DeviceBuffer, V, prob_out: DeviceBuffer, labels_out: Optional[DeviceBuffer] = None,
-                                     lut: Optional[np.ndarray] = None, work: Optional[dict] = None, resample_to=None,
+                                     lut: Optional[np.ndarray] = None, work: Optional[Workspace] = None, resample_to=None,
                                      bbox_lo=None, full_dims=None, perm=(0, 1, 2)):
         """All folds -> class probabilities on device (convert_predicted_logits_to_segmentation_with_correct_shape with
         return_probabilities=True, export_prediction.py:14-71).  dvol: fp32 [Cin,*V] resident.  The scatter form of the tile loop
@@ -338,78 +357,38 @@ class HipPredictor:
         the box inserted at `bbox_lo` of `full_dims` (default: the box is the grid) with background (1, 0, ..) around it, the
         spatial axes permuted by `perm`.  prob_out: fp32 [C, *full_dims permuted]; labels_out (optional): uint8, the first maximum
         of the PROBABILITIES through `lut`.  The gather form never materialises logits and is not used here."""
-        PV, below = sw.pad_amounts(V, self.geom.patch_size)
-        origins = sw.get_sliding_window_origins(PV, self.geom.patch_size, self.tile_step_size)
-        C_ = self.geom.num_classes
-        nvox = int(np.prod(PV))
-        nf = len(self.list_of_parameters)
-        own = work is None
-        work = work if work is not None else {}
-
-        def buf(name, nbytes):
-            b = work.get(name)
-            if b is None or b.nbytes < nbytes:
-                if b is not None:
-                    b.free()
-                b = self.ctx.alloc(nbytes)
-                work[name] = b
-            return b
-
-        ring = work.get("flag_ring")
-        if ring is not None:
-            flag = ring.next()
-        else:
-            flag = buf("flag", 4)
-            flag.zero()
-        lut_arr = None
-        if lut is not None:
-            lut_arr = np.zeros(256, dtype=np.uint8)
-            lut_arr[:len(lut)] = lut
-        lut_p = lut_arr.ctypes.data_as(C.c_void_p) if lut_arr is not None else None
-        acc = buf("acc", C_ * nvox * 2)
-        nacc = buf("n", nvox * 2)
-        fold = buf("fold", C_ * nvox * 2) if nf > 1 else None
-        for f in range(nf):
-            self._run_fold(dvol, V, PV, below, origins, acc, nacc, f)
-            last = f == nf - 1
-            check(self.lib.boa_finalize_labels(
-                self.ctx.h, acc.vp, nacc.vp, C_, int3(PV), fold.vp if fold else None, 0 if f == 0 else 1,
-                nf if (last and fold) else 0, 0 if fold else 1, None, 0, None, None, None, flag.vp), "boa_finalize_labels")
-        if ring is None and int(flag.download((1,), np.int32)[0]):
-            raise RuntimeError("Encountered inf in predicted array. Aborting...")
-        out_dims, slice_axis = resample_to if resample_to is not None else (None, -1)
-        box = list(out_dims) if out_dims is not None else list(V)
-        check(self.lib.boa_logits_to_probabilities(
-            self.ctx.h, (fold if fold else acc).vp, C_, int3(PV), int3(below), int3(V), int3(out_dims) if out_dims is not None else None,
-            int(slice_axis), int3(bbox_lo if bbox_lo is not None else (0, 0, 0)), int3(full_dims if full_dims is not None else box),
-            int3(perm), prob_out.vp, lut_p, labels_out.vp if labels_out is not None else None), "boa_logits_to_probabilities")
-        if own:
-            for b in work.values():
-                b.free()
+        w = _Window(self, V, lut)
+        with _scratch(self.ctx, work) as ws:
+            flag = ws.flag()
+            acc, nacc, fold = self._planes(w, ws)
+            for f in range(w.nf):
+                self._run_fold(dvol, w.V, w.PV, w.below, w.origins, acc, nacc, f)
+                last = f == w.nf - 1
+                check(self.lib.boa_finalize_labels(
+                    self.ctx.h, acc.vp, nacc.vp, w.C_, int3(w.PV), fold.vp if fold else None, 0 if f == 0 else 1,
+                    w.nf if (last and fold) else 0, 0 if fold else 1, None, 0, None, None, None, flag.vp), "boa_finalize_labels")
+            _raise_if_inf(flag, ws.ring)
+            out_dims, slice_axis = resample_to if resample_to is not None else (None, -1)
+            box = list(out_dims) if out_dims is not None else w.V
+            check(self.lib.boa_logits_to_probabilities(
+                self.ctx.h, (fold if fold else acc).vp, w.C_, int3(w.PV), int3(w.below), int3(w.V), int3(out_dims) if out_dims is not None else None,
+                int(slice_axis), int3(bbox_lo if bbox_lo is not None else (0, 0, 0)), int3(full_dims if full_dims is not None else box),
+                int3(perm), prob_out.vp, w.lut_p, labels_out.vp if labels_out is not None else None), "boa_logits_to_probabilities")
 
     def predict_segmentation(self, input_image: np.ndarray, lut: Optional[np.ndarray] = None, return_probabilities: bool = False):
         """Labels uint8 [*V] of preprocessed data [Cin, *V].  return_probabilities=True: (labels, probabilities float32 [C, *V]),
         the labels being the first maximum of the probabilities (label_handling.py:144-183); only the pad is reverted here."""
-        if return_probabilities:
-            V = list(input_image.shape[1:])
-            dvol = self.ctx.from_numpy(np.ascontiguousarray(input_image, dtype=np.float32))
-            lab = self.ctx.alloc(int(np.prod(V)))
-            prob = self.ctx.alloc(self.geom.num_classes * int(np.prod(V)) * 4)
-            try:
+        V = list(input_image.shape[1:])
+        with Scope() as sc:
+            dvol = sc.own(self.ctx.from_numpy(np.ascontiguousarray(input_image, dtype=np.float32)))
+            if return_probabilities:
+                lab = sc.own(self.ctx.alloc(int(np.prod(V))))
+                prob = sc.own(self.ctx.alloc(self.geom.num_classes * int(np.prod(V)) * 4))
                 self.predict_probabilities_device(dvol, V, prob, lab, lut=lut)
                 return lab.download(tuple(V), np.uint8), prob.download((self.geom.num_classes, *V), np.float32)
-            finally:
-                for b in (dvol, lab, prob):
-                    b.free()
-        V = list(input_image.shape[1:])
-        dvol = self.ctx.from_numpy(np.ascontiguousarray(input_image, dtype=np.float32))
-        lab = self.ctx.zeros(int(np.prod(V)))
-        try:
+            lab = sc.own(self.ctx.zeros(int(np.prod(V))))
             self.predict_segmentation_device(dvol, V, lab, lut=lut, merge=False)
             return lab.download(tuple(V), np.uint8)
-        finally:
-            dvol.free()
-            lab.free()
 
 
 class _ShardedJob:
@@ -418,20 +397,12 @@ class _ShardedJob:
     def __init__(self, pred: HipPredictor, dvol, V, labels_out, lut, merge, work, shard, resample_to):
         from . import tile_shard as ts
         self.ts, self.p, self.ctx, self.lib = ts, pred, pred.ctx, pred.lib
-        self.dvol, self.V, self.labels_out, self.merge, self.shard, self.resample_to = dvol, list(V), labels_out, merge, shard, resample_to
-        self.own = work is None
-        self.work = work if work is not None else {}
-        self.PV, self.below = sw.pad_amounts(self.V, pred.geom.patch_size)
-        self.origins = sw.get_sliding_window_origins(self.PV, pred.geom.patch_size, pred.tile_step_size)
-        self.plan = ts.plan_rows(self.origins, pred.geom.patch_size[0], self.PV[0], shard.comm.world,
+        self.dvol, self.labels_out, self.merge, self.shard, self.resample_to = dvol, labels_out, merge, shard, resample_to
+        self.own = _checked(work) is None      # a private workspace lives until `finish` (or a failed `begin`): `close`
+        self.work = Workspace(self.ctx) if self.own else work
+        self.w = _Window(pred, V, lut)
+        self.plan = ts.plan_rows(self.w.origins, pred.geom.patch_size[0], self.w.PV[0], shard.comm.world,
                                  assignment=getattr(shard, "assignment", None))
-        self.C_, self.nvox, self.nv = pred.geom.num_classes, int(np.prod(self.PV)), int(np.prod(self.V))
-        self.nf = len(pred.list_of_parameters)
-        self.lut_arr = None
-        if lut is not None:
-            self.lut_arr = np.zeros(256, dtype=np.uint8)
-            self.lut_arr[:len(lut)] = lut
-        self.crop = any(b != 0 for b in self.below) or list(self.PV) != list(self.V)
         self.direct = resample_to is None
         self.pending = None
         self.lo = self.hi = 0
@@ -444,43 +415,35 @@ class _ShardedJob:
         # its share of the planes: the same fp16 operations in the same order as on one GPU -> bit-identical labels.
         import os as _os
         self.fold_plans = None
-        if (self.nf > 1 and self.direct and shard.mode == "exact" and getattr(shard, "assignment", None) is None
+        if (self.w.nf > 1 and self.direct and shard.mode == "exact" and getattr(shard, "assignment", None) is None
                 and shard.comm.world > self.plan.active and not _os.environ.get("BOA_NO_FOLD_UNITS")):
-            units = ts.plan_units([len(self.plan.rows)] * self.nf, shard.comm.world)
-            self.fold_plans = [ts.plan_rows(self.origins, pred.geom.patch_size[0], self.PV[0], shard.comm.world, assignment=units[f])
-                               for f in range(self.nf)]
+            units = ts.plan_units([len(self.plan.rows)] * self.w.nf, shard.comm.world)
+            self.fold_plans = [ts.plan_rows(self.w.origins, pred.geom.patch_size[0], self.w.PV[0], shard.comm.world, assignment=units[f])
+                               for f in range(self.w.nf)]
 
-    def _buf(self, name, nbytes):
-        b = self.work.get(name)
-        if b is None or b.nbytes < nbytes:
-            if b is not None:
-                b.free()
-            b = self.ctx.alloc(nbytes)
-            self.work[name] = b
-        return b
-
-    def _lut_p(self):
-        return self.lut_arr.ctypes.data_as(C.c_void_p) if self.lut_arr is not None else None
+    def close(self):
+        if self.own:
+            self.work.free()
 
     def _begin_fold_units(self, after_first_start):
         ts, comm, rank = self.ts, self.shard.comm, self.shard.comm.rank
-        self.part = self._buf("part", self.nv)
+        self.part = self.work.buf("shard_part", self.w.nv)
         self.flogits = []
         member = 0
         for f, plan_f in enumerate(self.fold_plans):
-            F = self._buf(f"flog{f}", self.C_ * self.nvox * 2)       # fold f's normalised logits, complete on every rank after the sum
+            F = self.work.buf(f"flog{f}", self.w.C_ * self.w.nvox * 2)       # fold f's normalised logits, complete on every rank after the sum
             lo = hi = 0
             if plan_f.index(rank) is not None:
                 self.p._ensure_net(f)
-                nacc = self._buf(f"fn{member}", self.nvox * 2)
+                nacc = self.work.buf(f"fn{member}", self.w.nvox * 2)
                 member += 1
-                eng = ts.HipShardEngine(self.p, comm, self.dvol, self.V, self.PV, self.below, self.origins, F, nacc)
+                eng = ts.HipShardEngine(self.p, comm, self.dvol, self.w.V, self.w.PV, self.w.below, self.w.origins, F, nacc)
                 try:
                     lo, hi = ts.finish_fold_sharded(ts.start_fold_sharded(eng, plan_f, comm, self.shard.mode))
                 finally:
                     eng.close()
                 # acc / n -> normalised fp16 logits in place on the planes this rank owns (inf check included)
-                check(self.lib.boa_finalize_labels_planes(self.ctx.h, F.vp, nacc.vp, self.C_, int3(self.PV), None, 0, 0, 1, None, 0, None,
+                check(self.lib.boa_finalize_labels_planes(self.ctx.h, F.vp, nacc.vp, self.w.C_, int3(self.w.PV), None, 0, 0, 1, None, 0, None,
                                                           None, None, self.flag.vp, lo, hi), "boa_finalize_labels_planes")
             self.flogits.append((F, lo, hi))
             if f == 0 and after_first_start is not None:
@@ -491,45 +454,38 @@ class _ShardedJob:
         import os as _os
         if _os.environ.get("BOA_FOLD_ALLREDUCE"):
             for F, lo, hi in self.flogits:
-                ts.all_reduce_logit_planes(self.ctx, comm, F, self.C_, self.PV, lo, hi)
+                ts.all_reduce_logit_planes(self.ctx, comm, F, self.w.C_, self.w.PV, lo, hi)
         else:
-            shares = ts.plane_shares(self.PV[0], comm.world)
+            shares = ts.plane_shares(self.w.PV[0], comm.world)
             for (F, _, _), plan_f in zip(self.flogits, self.fold_plans):
                 owned = [plan_f.owned_planes(q) for q in range(comm.world)]
-                ts.reduce_scatter_logit_planes(self.ctx, comm, F, self.C_, self.PV, owned, shares)
+                ts.reduce_scatter_logit_planes(self.ctx, comm, F, self.w.C_, self.w.PV, owned, shares)
 
     def _finish_fold_units(self):
         comm = self.shard.comm
-        P0, P1 = (self.PV[0] * comm.rank) // comm.world, (self.PV[0] * (comm.rank + 1)) // comm.world
-        ones = self.work.get("ones")
-        if ones is None or ones.nbytes < self.nvox * 2:
-            if ones is not None:
-                ones.free()
-            ones = self.ctx.from_numpy(np.full(self.nvox, 0x3C00, np.uint16))       # fp16 1.0: x / 1 == x, the fold logits are normalised already
-            self.work["ones"] = ones
-        fold = self._buf("fold", self.C_ * self.nvox * 2)
+        P0, P1 = (self.w.PV[0] * comm.rank) // comm.world, (self.w.PV[0] * (comm.rank + 1)) // comm.world
+        # fp16 1.0: x / 1 == x, the fold logits are normalised already
+        ones = self.work.buf("ones", self.w.nvox * 2, init=lambda b: b.upload(np.full(self.w.nvox, 0x3C00, np.uint16)))
+        fold = self.work.buf("fold", self.w.C_ * self.w.nvox * 2)
         for f, (F, _, _) in enumerate(self.flogits):
-            last = f == self.nf - 1
+            last = f == self.w.nf - 1
             check(self.lib.boa_finalize_labels_planes(
-                self.ctx.h, F.vp, ones.vp, self.C_, int3(self.PV), fold.vp, 0 if f == 0 else 1, self.nf if last else 0, 0, self._lut_p(), 0,
-                self.part.vp if last else None, int3(self.below) if self.crop else None, int3(self.V) if self.crop else None, self.flag.vp,
+                self.ctx.h, F.vp, ones.vp, self.w.C_, int3(self.w.PV), fold.vp, 0 if f == 0 else 1, self.w.nf if last else 0, 0, self.w.lut_p, 0,
+                self.part.vp if last else None, int3(self.w.below) if self.w.crop else None, int3(self.w.V) if self.w.crop else None, self.flag.vp,
                 P0, P1), "boa_finalize_labels_planes")
 
     def begin(self, after_first_start=None):
-        job_slot = self.work.get("_job", 0) & 1
-        self.work["_job"] = self.work.get("_job", 0) + 1
-        self.flag = self._buf(f"flag{job_slot}", 4)
+        self.flag = self.work.buf(f"flag{self.work.turn('job')}", 4)      # (its own alternating flags: read by all_reduce_flag in `finish`)
         self.flag.zero()
         if self.fold_plans is not None:
             return self._begin_fold_units(after_first_start)
-        self.fold = self._buf("fold", self.C_ * self.nvox * 2) if self.nf > 1 else None
-        self.part = self._buf("part", self.nv)
-        for f in range(self.nf):
+        self.fold = self.work.buf("fold", self.w.C_ * self.w.nvox * 2) if self.w.nf > 1 else None
+        self.part = self.work.buf("shard_part", self.w.nv)
+        for f in range(self.w.nf):
             self.p._ensure_net(f)
-            slot = self.work.get("_seq", 0) & 1            # two accumulator sets: the one whose exchange is in flight and the one being filled
-            self.work["_seq"] = self.work.get("_seq", 0) + 1
-            acc, nacc = self._buf(f"acc{slot}", self.C_ * self.nvox * 2), self._buf(f"n{slot}", self.nvox * 2)
-            eng = self.ts.HipShardEngine(self.p, self.shard.comm, self.dvol, self.V, self.PV, self.below, self.origins, acc, nacc)
+            slot = self.work.turn("seq")            # two accumulator sets: the one whose exchange is in flight and the one being filled
+            acc, nacc = self.work.buf(f"acc{slot}", self.w.C_ * self.w.nvox * 2), self.work.buf(f"n{slot}", self.w.nvox * 2)
+            eng = self.ts.HipShardEngine(self.p, self.shard.comm, self.dvol, self.w.V, self.w.PV, self.w.below, self.w.origins, acc, nacc)
             state = self.ts.start_fold_sharded(eng, self.plan, self.shard.comm, self.shard.mode)
             if f == 0 and after_first_start is not None:
                 after_first_start()
@@ -542,13 +498,13 @@ class _ShardedJob:
             self.lo, self.hi = self.ts.finish_fold_sharded(state)
         finally:
             eng.close()
-        last = f == self.nf - 1
+        last = f == self.w.nf - 1
         fold, direct = self.fold, self.direct
         # (resampled path: keep the normalised fold-mean logits of the owned planes -- in the accumulators for one fold, in `fold` otherwise)
         check(self.lib.boa_finalize_labels_planes(
-            self.ctx.h, eng.acc.vp, eng.nacc.vp, self.C_, int3(self.PV), fold.vp if fold else None, 0 if f == 0 else 1,
-            self.nf if (last and fold) else 0, 0 if (direct or fold) else 1, self._lut_p(), 0, self.part.vp if (last and direct) else None,
-            int3(self.below) if self.crop else None, int3(self.V) if self.crop else None, self.flag.vp, self.lo, self.hi),
+            self.ctx.h, eng.acc.vp, eng.nacc.vp, self.w.C_, int3(self.w.PV), fold.vp if fold else None, 0 if f == 0 else 1,
+            self.w.nf if (last and fold) else 0, 0 if (direct or fold) else 1, self.w.lut_p, 0, self.part.vp if (last and direct) else None,
+            int3(self.w.below) if self.w.crop else None, int3(self.w.V) if self.w.crop else None, self.flag.vp, self.lo, self.hi),
             "boa_finalize_labels_planes")
         self.logits = fold if fold else eng.acc
 
@@ -556,33 +512,31 @@ class _ShardedJob:
         if self.done:
             return
         self.done = True
-        ts, comm, nv = self.ts, self.shard.comm, self.nv
-        check(self.lib.boa_memset(self.ctx.h, self.part.vp, 0, nv), "boa_memset")
-        if self.fold_plans is not None:
-            self._finish_fold_units()
-        if self.pending is not None:
-            self._finish_fold(*self.pending)
-            self.pending = None
-        if self.direct:
-            ts.all_reduce_labels(self.ctx, comm, self.part, nv)
-        else:
-            # nnU-Net resamples the logits (order 1) before the argmax: every rank needs all planes -> sum the plane-disjoint logits
-            # over the ranks, then the same fused resize + argmax as on one GPU (identical labels on every rank)
-            out_dims, slice_axis = self.resample_to
-            ts.all_reduce_logit_planes(self.ctx, comm, self.logits, self.C_, self.PV, self.lo, self.hi)
-        if ts.all_reduce_flag(self.ctx, comm, self.flag):
-            raise RuntimeError("Encountered inf in predicted array. Aborting...")
-        if not self.direct:
-            check(self.lib.boa_resize_logits_argmax(self.ctx.h, self.logits.vp, self.C_, int3(self.PV), int3(self.below), int3(self.V), int3(out_dims),
-                                                    int(slice_axis), self._lut_p(), 1 if self.merge else 0, self.labels_out.vp),
-                  "boa_resize_logits_argmax")
-        elif self.merge:
-            check(self.lib.boa_label_overlay(self.ctx.h, self.part.vp, nv, self.labels_out.vp), "boa_label_overlay")
-        else:
-            one, st = (C.c_int * 3)(1, 1, nv), (C.c_longlong * 3)(0, 0, 1)
-            check(self.lib.boa_copy3(self.ctx.h, self.part.vp, 0, 0, st, one, self.labels_out.vp, 0, 0, st), "boa_copy3")
-        if self.own:
-            for b in self.work.values():
-                if hasattr(b, "free"):
-                    b.free()
-
+        try:
+            ts, comm, nv = self.ts, self.shard.comm, self.w.nv
+            check(self.lib.boa_memset(self.ctx.h, self.part.vp, 0, nv), "boa_memset")
+            if self.fold_plans is not None:
+                self._finish_fold_units()
+            if self.pending is not None:
+                self._finish_fold(*self.pending)
+                self.pending = None
+            if self.direct:
+                ts.all_reduce_labels(self.ctx, comm, self.part, nv)
+            else:
+                # nnU-Net resamples the logits (order 1) before the argmax: every rank needs all planes -> sum the plane-disjoint logits
+                # over the ranks, then the same fused resize + argmax as on one GPU (identical labels on every rank)
+                out_dims, slice_axis = self.resample_to
+                ts.all_reduce_logit_planes(self.ctx, comm, self.logits, self.w.C_, self.w.PV, self.lo, self.hi)
+            if ts.all_reduce_flag(self.ctx, comm, self.flag):
+                raise RuntimeError(INF_MESSAGE)
+            if not self.direct:
+                check(self.lib.boa_resize_logits_argmax(self.ctx.h, self.logits.vp, self.w.C_, int3(self.w.PV), int3(self.w.below), int3(self.w.V), int3(out_dims),
+                                                        int(slice_axis), self.w.lut_p, 1 if self.merge else 0, self.labels_out.vp),
+                      "boa_resize_logits_argmax")
+            elif self.merge:
+                check(self.lib.boa_label_overlay(self.ctx.h, self.part.vp, nv, self.labels_out.vp), "boa_label_overlay")
+            else:
+                one, st = (C.c_int * 3)(1, 1, nv), (C.c_longlong * 3)(0, 0, 1)
+                check(self.lib.boa_copy3(self.ctx.h, self.part.vp, 0, 0, st, one, self.labels_out.vp, 0, 0, st), "boa_copy3")
+        finally:
+            self.close()

@@ -18,6 +18,7 @@ model's plans (`boa_hip/nnunet_resample.py`); it is the identity at every BASELI
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -27,7 +28,7 @@ from . import nnunet_resample as nr
 from . import resample as rs
 from ._lib import check, int3
 from .devarray import DevArray
-from .device import Context
+from .device import Context, Scope, Workspace
 from .plans import ModelConfig
 from .predictor import HipPredictor
 
@@ -101,7 +102,8 @@ class SegmentationTask:
             else:
                 lut = None
             self.parts.append((task_id, cfg, p, lut))
-        self._work: Dict[str, object] = {}
+        # the task's persistent device scratch and its FlagRing: reused across volumes and models, handed to the predictors as `work=`
+        self._work = Workspace(ctx, ring=True)
         # tile_shard.TileShard: several ranks share every volume (tile rows split, overlap slabs exchanged); each rank
         # must be given the same input and ends with the same labels.  None = this process handles whole volumes.
         self.shard = None
@@ -113,9 +115,7 @@ class SegmentationTask:
     def close(self):
         for _, _, p, _ in self.parts:
             p.close()
-        for b in [v for v in self._work.values() if hasattr(v, "free")]:
-            b.free()
-        self._work = {}
+        self._work.free()
 
     # ---- device core: resident CT [z,y,x] -> resident uint8 labels -----------------------------------------
     def predict_zyx_device(self, d_ct, shape, d_labels, in_dtype: int = 0, spacing_zyx=None):
@@ -123,29 +123,21 @@ class SegmentationTask:
         `spacing_zyx`: voxel spacing of the array (nnU-Net axis order); when it differs from a model's plans spacing the
         normalised volume is resampled to the plans' grid and the logits back (nnU-Net's own resampling,
         default_preprocessor.py:82-93 / export_prediction.py:25-33) -- None = the array is at the plans' spacing."""
-        ctx = self.ctx
         n = int(np.prod(shape))
-        vol = self._work.get("vol")
-        if vol is None or vol.nbytes < n * 4:
-            if vol is not None:
-                vol.free()
-            vol = self._work["vol"] = ctx.alloc(n * 4)
+        self._work.buf("vol", n * 4)      # (every model normalises into it; allocated before the ring, once per task)
         d_labels.zero()
-        # The predictors of this task take their inf-flag slots from the ring in `self._work` (predictor.py discovers it there), so EVERY
+        # The predictors of this task take their inf-flag slots from the ring of `self._work` (Workspace.flag), so EVERY
         # path below owns it: reset before the first model, one read after the last (a path that skipped the check would drop the
         # reference's "Encountered inf in predicted array" error and let unchecked slots pile up -- ADVICE r5).
-        ring = self._work.get("flag_ring")
-        if ring is None:
-            from .device import FlagRing
-            ring = self._work["flag_ring"] = FlagRing(ctx)
+        ring = self._work.ring
         ring.reset()
         if self.model_shard is not None and self.model_shard.world > 1 and self.multimodel:
-            self._predict_zyx_model_sharded(d_ct, shape, d_labels, in_dtype, vol, n, spacing_zyx)
+            self._predict_zyx_model_sharded(d_ct, shape, d_labels, in_dtype, n, spacing_zyx)
         elif self.shard is not None and self.shard.comm.world > 1 and self.multimodel and len(self.parts) > 1 and self._units_applicable(shape, spacing_zyx):
             self._predict_zyx_unit_sharded(d_ct, shape, d_labels, in_dtype, n)
         else:
             for k in range(len(self.parts)):
-                self._run_model(k, d_ct, shape, d_labels, in_dtype, vol, n, spacing_zyx, merge=self.multimodel, shard=self.shard)
+                self._run_model(k, d_ct, shape, d_labels, in_dtype, n, spacing_zyx, merge=self.multimodel, shard=self.shard)
         ring.check()   # the models' inf flags of this rank, one read per volume
 
     # ---- (row x model) units: all ranks busy on one multi-model volume ---------------------------------------------------------
@@ -165,7 +157,7 @@ class SegmentationTask:
         the one-GPU run in `exact` mode: per model the accumulation order is the reference's, the merge order is the part order."""
         import dataclasses
         from . import sliding_window as sw
-        ctx, world = self.ctx, self.shard.comm.world
+        world = self.shard.comm.world
         rows, weights = [], []
         for _, cfg, p, _ in self.parts:
             PV, _b = sw.pad_amounts(list(shape), p.geom.patch_size)
@@ -178,14 +170,7 @@ class SegmentationTask:
         prev = None
         for k in range(len(self.parts)):
             task_id, cfg, p, lut = self.parts[k]
-            vol = self._work.get(f"vol{k & 1}")
-            if vol is None or vol.nbytes < n * 4:
-                if vol is not None:
-                    vol.free()
-                vol = self._work[f"vol{k & 1}"] = ctx.alloc(n * 4)
-            ip = cfg.intensity_properties["0"]
-            check(ctx.lib.boa_ct_normalize(ctx.h, d_ct.vp, in_dtype, vol.vp, n, ip["mean"], ip["std"], ip["percentile_00_5"],
-                                           ip["percentile_99_5"]), "boa_ct_normalize")
+            vol = self._normalized(cfg, d_ct, in_dtype, n, name=f"vol{k & 1}")
             shard_k = dataclasses.replace(self.shard, assignment=units[k])
             job = p.begin_segmentation_sharded(vol, list(shape), d_labels, lut, True, self._work, shard_k,
                                                after_first_start=(prev.finish if prev is not None else None))
@@ -193,43 +178,53 @@ class SegmentationTask:
         if prev is not None:
             prev.finish()
 
-    def _run_model(self, k, d_ct, shape, d_out, in_dtype, vol, n, spacing_zyx, merge, shard):
-        """One model of the task on the resident array: CTNormalization with the model's own intensity properties
-        (default_preprocessor.py:336-348), nnU-Net's resampling to the plans' spacing when it differs from the array's, sliding
-        window, labels written (merge=False) or merged (merge=True) into `d_out`."""
+    def _normalized(self, cfg, d_ct, in_dtype: int, n: int, name: str = "vol"):
+        """CTNormalization with the model's own intensity properties (default_preprocessor.py:336-348) of the `n` voxels at `d_ct`
+        into the workspace buffer `name` (fp32), which is returned."""
         ctx = self.ctx
-        task_id, cfg, p, lut = self.parts[k]
+        vol = self._work.buf(name, n * 4)
         ip = cfg.intensity_properties["0"]
         check(ctx.lib.boa_ct_normalize(ctx.h, d_ct.vp, in_dtype, vol.vp, n, ip["mean"], ip["std"],
                                        ip["percentile_00_5"], ip["percentile_99_5"]), "boa_ct_normalize")
-        new_shape = list(shape) if spacing_zyx is None else nr.compute_new_shape(shape, spacing_zyx, cfg.spacing)
-        if new_shape == list(shape):      # resample_data_or_seg returns its input unchanged (default_resampling.py:194-196)
-            p.predict_segmentation_device(vol, list(shape), d_out, lut=lut, merge=merge, work=self._work, shard=shard)
+        return vol
+
+    @contextlib.contextmanager
+    def _at_plan_spacing(self, cfg, vol, shape, spacing):
+        """nnU-Net's resampling to the plans' spacing (default_preprocessor.py:82-93) of the normalised `vol` (`spacing`: the array's,
+        None = the plans'): yields (volume, shape, resample_to) for the predictor -- `vol` itself and None when the shape does not
+        change, else a temporary at the plans' grid, freed on exit, and `resample_to` = (shape, slice axis) for the way back."""
+        ctx, shape = self.ctx, [int(v) for v in shape]
+        new_shape = shape if spacing is None else nr.compute_new_shape(shape, spacing, cfg.spacing)
+        if new_shape == shape:      # resample_data_or_seg returns its input unchanged (default_resampling.py:194-196)
+            yield vol, shape, None
             return
         # normalise BEFORE resampling (default_preprocessor.py:82-84), order 3 in; order 1 back, then argmax
-        ax_in = nr.slice_axis_for(nr.checked_kwargs(cfg.extra, "data"), spacing_zyx, cfg.spacing)
-        ax_out = nr.slice_axis_for(nr.checked_kwargs(cfg.extra, "probabilities"), cfg.spacing, spacing_zyx)
+        ax_in = nr.slice_axis_for(nr.checked_kwargs(cfg.extra, "data"), spacing, cfg.spacing)
+        ax_out = nr.slice_axis_for(nr.checked_kwargs(cfg.extra, "probabilities"), cfg.spacing, spacing)
         vol_r = ctx.alloc(int(np.prod(new_shape)) * 4)
         try:
             check(ctx.lib.boa_resize_skimage_f32(ctx.h, vol.vp, int3(shape), vol_r.vp, int3(new_shape), 3, ax_in),
                   "boa_resize_skimage_f32")
-            p.predict_segmentation_device(vol_r, new_shape, d_out, lut=lut, merge=merge, work=self._work,
-                                          shard=shard, resample_to=(list(shape), ax_out))
+            yield vol_r, new_shape, (shape, ax_out)
         finally:
             vol_r.free()
 
-    def _predict_zyx_model_sharded(self, d_ct, shape, d_labels, in_dtype, vol, n, spacing_zyx=None):
+    def _run_model(self, k, d_ct, shape, d_out, in_dtype, n, spacing_zyx, merge, shard):
+        """One model of the task on the resident array: CTNormalization, nnU-Net's resampling to the plans' spacing when it differs
+        from the array's, sliding window, labels written (merge=False) or merged (merge=True) into `d_out`."""
+        task_id, cfg, p, lut = self.parts[k]
+        vol = self._normalized(cfg, d_ct, in_dtype, n)
+        with self._at_plan_spacing(cfg, vol, shape, spacing_zyx) as (v, v_shape, resample_to):
+            p.predict_segmentation_device(v, v_shape, d_out, lut=lut, merge=merge, work=self._work, shard=shard, resample_to=resample_to)
+
+    def _predict_zyx_model_sharded(self, d_ct, shape, d_labels, in_dtype, n, spacing_zyx=None):
         from . import tile_shard as ts
         ctx, comm = self.ctx, self.model_shard
-        part = self._work.get("part")
-        if part is None or part.nbytes < n:
-            if part is not None:
-                part.free()
-            part = self._work["part"] = ctx.alloc(n)
+        part = self._work.buf("model_part", n)
         for k in range(len(self.parts)):
             check(ctx.lib.boa_memset(ctx.h, part.vp, 0, n), "boa_memset")
             if k % comm.world == comm.rank:   # exactly the one-GPU computation of this model (incl. its plan-spacing resampling)
-                self._run_model(k, d_ct, shape, part, in_dtype, vol, n, spacing_zyx, merge=False, shard=None)
+                self._run_model(k, d_ct, shape, part, in_dtype, n, spacing_zyx, merge=False, shard=None)
             # the owner's label volume reaches every rank (sum over disjoint supports), then the reference's merge in part
             # order: `seg_combined[seg == jdx] = class_map_inv[name]` (TS/nnunet.py:553-556)
             ts.all_reduce_labels(ctx, comm, part, n)
@@ -247,54 +242,36 @@ class SegmentationTask:
         dt = part_xyz.dtype
         want = dt if dt in (np.dtype(np.int16), np.dtype(np.int32)) else np.dtype(np.float32)
         code = {np.dtype(np.int16): 0, np.dtype(np.float32): 1, np.dtype(np.int32): 2}[want]
-        zyx = part_xyz.transpose((2, 1, 0)).contiguous(want, force_copy=False)
         # plans' transpose_forward (default_preprocessor.py:57-60: data.transpose([0, *[i + 1 for i in transpose_forward]]) before
         # cropping / resampling; export_prediction.py:56-58 transposes the segmentation back): a device view + one copy
         tf = [int(v) for v in self.parts[0][1].transpose_forward]
         ident = tf == [0, 1, 2]
-        work = zyx if ident else zyx.transpose(tuple(tf)).contiguous(want, force_copy=True)
         sp_t = None if spacing_zyx is None else [spacing_zyx[i] for i in tf]
-        bbox_t = work.nonzero_bbox()
-        full = all(b == [0, n] for b, n in zip(bbox_t, work.shape))
-        crop = work if full else work.box(bbox_t).contiguous()
-        if save_probabilities is not None:
-            try:
-                lab_zyx = self._predict_part_probabilities(crop, work.shape, bbox_t, code, spacing_zyx, sp_t, save_probabilities)
-                try:
-                    k0, k1 = max(0, src_lo), min(lab_zyx.shape[0], src_hi)
-                    if k0 < k1:
-                        lab_zyx.slice(0, k0, k1).transpose((2, 1, 0)).copy_to(dst_xyz.slice(2, k0 - src_lo, k1 - src_lo))
-                finally:
-                    lab_zyx.free()
-            finally:
-                if crop is not work:
-                    crop.free()
-                if work is not zyx:
-                    work.free()
-                if zyx.buf is not part_xyz.buf:
-                    zyx.free()
-            return
-        d_lab = DevArray.empty(self.ctx, crop.shape, np.uint8)
-        try:
-            self.predict_zyx_device(crop.buf, crop.shape, d_lab.buf, in_dtype=code, spacing_zyx=sp_t)
-            # back to (z, y, x): axis i of the transposed array is axis tf[i] of the original
-            bbox = [None, None, None]
-            for i in range(3):
-                bbox[tf[i]] = bbox_t[i]
-            lab_zyx = d_lab if ident else d_lab.transpose(tuple(int(v) for v in self.parts[0][1].transpose_backward))
+        with Scope() as sc:
+            def copy_of(a, src):      # a copy is released here; a view of `src` is its owner's
+                return a if a.buf is src.buf else sc.own(a)
+            zyx = copy_of(part_xyz.transpose((2, 1, 0)).contiguous(want, force_copy=False), part_xyz)
+            work = zyx if ident else sc.own(zyx.transpose(tuple(tf)).contiguous(want, force_copy=True))
+            bbox_t = work.nonzero_bbox()
+            full = all(b == [0, n] for b, n in zip(bbox_t, work.shape))
+            crop = work if full else copy_of(work.box(bbox_t).contiguous(), work)
+            if save_probabilities is not None:
+                # (the labels come back on the part's whole (z, y, x) grid: the crop box is already put back)
+                lab_zyx = sc.own(self._predict_part_probabilities(crop, work.shape, bbox_t, code, spacing_zyx, sp_t, save_probabilities))
+                bbox = [[0, int(v)] for v in lab_zyx.shape]
+            else:
+                d_lab = sc.own(DevArray.empty(self.ctx, crop.shape, np.uint8))
+                self.predict_zyx_device(crop.buf, crop.shape, d_lab.buf, in_dtype=code, spacing_zyx=sp_t)
+                # back to (z, y, x): axis i of the transposed array is axis tf[i] of the original
+                bbox = [None, None, None]
+                for i in range(3):
+                    bbox[tf[i]] = bbox_t[i]
+                lab_zyx = d_lab if ident else d_lab.transpose(tuple(int(v) for v in self.parts[0][1].transpose_backward))
             k0, k1 = max(bbox[0][0], src_lo), min(bbox[0][1], src_hi)
             if k0 < k1:
                 src = lab_zyx.slice(0, k0 - bbox[0][0], k1 - bbox[0][0]).transpose((2, 1, 0))
                 dst = dst_xyz.slice(2, k0 - src_lo, k1 - src_lo).slice(1, bbox[1][0], bbox[1][1]).slice(0, bbox[2][0], bbox[2][1])
                 src.copy_to(dst)
-        finally:
-            d_lab.free()
-            if crop is not work:
-                crop.free()
-            if work is not zyx:
-                work.free()
-            if zyx.buf is not part_xyz.buf:
-                zyx.free()
 
     def _predict_part_probabilities(self, crop: DevArray, full_shape, bbox_t, in_dtype: int, spacing_zyx, sp_t, path) -> DevArray:
         """export_prediction_from_logits with save_probabilities (export_prediction.py:14-71, :99-102) for every model of the task
@@ -304,7 +281,6 @@ class SegmentationTask:
         `path` (np.savez_compressed, key `probabilities`) and the properties to `Path(path).with_suffix(".pkl")`; each model
         overwrites the files of the one before (TS/nnunet.py:286-293).  Returns the task's labels on the part's (z, y, x) grid --
         the first maximum of each model's probabilities, merged in part order for a multi-model task -- as a DevArray (caller frees)."""
-        from .device import FlagRing
         ctx = self.ctx
         shape = [int(v) for v in crop.shape]
         full = [int(v) for v in full_shape]
@@ -312,67 +288,39 @@ class SegmentationTask:
         tb = [int(v) for v in self.parts[0][1].transpose_backward]
         out_shape = [full[tb[i]] for i in range(3)]
         lo = [int(b[0]) for b in bbox_t]
-        vol = self._work.get("vol")
-        if vol is None or vol.nbytes < n * 4:
-            if vol is not None:
-                vol.free()
-            vol = self._work["vol"] = ctx.alloc(n * 4)
-        ring = self._work.get("flag_ring")
-        if ring is None:
-            ring = self._work["flag_ring"] = FlagRing(ctx)
+        self._work.buf("vol", n * 4)
+        ring = self._work.ring      # (owned here as in predict_zyx_device: reset before the first model, checked before a file is written)
         ring.reset()
-        labels = DevArray.zeros(ctx, out_shape, np.uint8)
-        part = DevArray.empty(ctx, out_shape, np.uint8) if self.multimodel else labels
         # what this engine knows of nnU-Net's properties_dict (plain types only: no nibabel / SimpleITK objects)
         props = {"spacing": None if spacing_zyx is None else [float(v) for v in spacing_zyx],
                  "shape_before_cropping": tuple(full), "bbox_used_for_cropping": [[int(a), int(b)] for a, b in bbox_t],
                  "shape_after_cropping_and_before_resampling": tuple(shape)}
-        try:
+        with Scope() as sc:
+            labels = sc.own(DevArray.zeros(ctx, out_shape, np.uint8))
+            part = sc.own(DevArray.empty(ctx, out_shape, np.uint8)) if self.multimodel else labels
             for task_id, cfg, p, lut in self.parts:
                 nc = p.geom.num_classes
                 prob = ctx.alloc(nc * n_full * 4)
-                vol_r = None
                 try:
-                    ip = cfg.intensity_properties["0"]
-                    check(ctx.lib.boa_ct_normalize(ctx.h, crop.buf.vp, in_dtype, vol.vp, n, ip["mean"], ip["std"], ip["percentile_00_5"],
-                                                   ip["percentile_99_5"]), "boa_ct_normalize")
-                    new_shape = shape if sp_t is None else nr.compute_new_shape(shape, sp_t, cfg.spacing)
-                    geo = dict(lut=lut, work=self._work, bbox_lo=lo, full_dims=full, perm=tb)
-                    if new_shape == shape:
-                        p.predict_probabilities_device(vol, shape, prob, part.buf, **geo)
-                    else:
-                        ax_in = nr.slice_axis_for(nr.checked_kwargs(cfg.extra, "data"), sp_t, cfg.spacing)
-                        ax_out = nr.slice_axis_for(nr.checked_kwargs(cfg.extra, "probabilities"), cfg.spacing, sp_t)
-                        vol_r = ctx.alloc(int(np.prod(new_shape)) * 4)
-                        check(ctx.lib.boa_resize_skimage_f32(ctx.h, vol.vp, int3(shape), vol_r.vp, int3(new_shape), 3, ax_in),
-                              "boa_resize_skimage_f32")
-                        p.predict_probabilities_device(vol_r, new_shape, prob, part.buf, resample_to=(shape, ax_out), **geo)
+                    vol = self._normalized(cfg, crop.buf, in_dtype, n)
+                    with self._at_plan_spacing(cfg, vol, shape, sp_t) as (v, v_shape, resample_to):
+                        p.predict_probabilities_device(v, v_shape, prob, part.buf, lut=lut, work=self._work, resample_to=resample_to,
+                                                       bbox_lo=lo, full_dims=full, perm=tb)
                     if part is not labels:
                         check(ctx.lib.boa_label_overlay(ctx.h, part.buf.vp, n_full, labels.buf.vp), "boa_label_overlay")
                     ring.check()
                     write_probabilities(path, prob.download((nc, *out_shape), np.float32), props)
                 finally:
                     prob.free()
-                    if vol_r is not None:
-                        vol_r.free()
-        except BaseException:
-            labels.free()
-            raise
-        finally:
-            if part is not labels:
-                part.free()
-        return labels
+            return sc.release(labels)
 
     def predict_part_xyz(self, data_xyz: np.ndarray) -> np.ndarray:
         """One (sub-)volume as TS writes it to s0k_0000.nii.gz: (x,y,z) array -> uint8 labels (x,y,z)."""
-        src = DevArray.from_numpy(self.ctx, self._supported(data_xyz))
-        seg = DevArray.zeros(self.ctx, src.shape, np.uint8)
-        try:
+        with Scope() as sc:
+            src = sc.own(DevArray.from_numpy(self.ctx, self._supported(data_xyz)))
+            seg = sc.own(DevArray.zeros(self.ctx, src.shape, np.uint8))
             self._predict_part_device(src, seg, 0, src.shape[2])
             return seg.download()
-        finally:
-            src.free()
-            seg.free()
 
     @staticmethod
     def _supported(data: np.ndarray) -> np.ndarray:
@@ -445,12 +393,8 @@ class SegmentationTask:
         bbox = None
         if crop_mask is not None and crop_mask.sum() == 0:              # TS/nnunet.py:428-446
             return DevArray.zeros(ctx, orig_shape, np.uint8) if return_device else np.zeros(orig_shape, dtype=np.uint8)
-        owned = []                                                     # device arrays to release
-
-        def own(a):
-            owned.append(a)
-            return a
-        try:
+        with Scope() as sc:                                            # device arrays to release
+            own = sc.own
             view = data if resident else own(DevArray.from_numpy(ctx, self._supported(data)))
             cast = None
             if crop_mask is not None:
@@ -541,17 +485,8 @@ class SegmentationTask:
             if tuple(out.shape) != orig_shape[:3]:
                 raise ValueError(f"shape mismatch after restore: {out.shape} vs {orig_shape}")   # check_if_shape_and_affine_identical
             if return_device:
-                res = out.contiguous(force_copy=(resident and out.buf is data.buf))
-                keep = id(res.buf)
-                owned[:] = [a for a in owned if id(a.buf) != keep]
-                return res
+                return sc.release(out.contiguous(force_copy=(resident and out.buf is data.buf)))
             return out.download()
-        finally:
-            seen = set()
-            for a in owned:
-                if id(a.buf) not in seen:
-                    seen.add(id(a.buf))
-                    a.free()
 
 
 def write_probabilities(path, probabilities: np.ndarray, properties: dict) -> None:
@@ -578,16 +513,13 @@ def remove_outside_of_mask(ctx: Context, seg: np.ndarray, mask: np.ndarray, addo
         raise NotImplementedError("remove_outside_of_mask with addon < 1 (scipy dilates until convergence)")
     n = int(seg.size)
     Z, Y, X = (int(v) for v in seg.shape)
-    d_seg = ctx.from_numpy(np.ascontiguousarray(seg, dtype=np.uint8))
-    d_m = ctx.from_numpy(np.ascontiguousarray(mask != 0, dtype=np.uint8))
-    d_o, d_t = ctx.alloc(n), ctx.alloc(n)
-    try:
+    with Scope() as sc:
+        d_seg = sc.own(ctx.from_numpy(np.ascontiguousarray(seg, dtype=np.uint8)))
+        d_m = sc.own(ctx.from_numpy(np.ascontiguousarray(mask != 0, dtype=np.uint8)))
+        d_o, d_t = sc.own(ctx.alloc(n)), sc.own(ctx.alloc(n))
         check(ctx.lib.boa_binary_dilate_cross(ctx.h, d_m.vp, d_o.vp, d_t.vp, Z, Y, X, int(addon)), "boa_binary_dilate_cross")
         check(ctx.lib.boa_mask_assign(ctx.h, d_o.vp, n, 1, 0, d_seg.vp), "boa_mask_assign")          # seg[mask == 0] = 0
         return d_seg.download(seg.shape, np.uint8)
-    finally:
-        for b in (d_seg, d_m, d_o, d_t):
-            b.free()
 
 
 def run_cascade_task(ctx: Context, task: str, data: np.ndarray, affine: np.ndarray, rough_models, task_models,

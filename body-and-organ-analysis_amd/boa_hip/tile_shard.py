@@ -35,6 +35,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from ._lib import check, int3
+from .device import Workspace
 
 
 # ---------------------------------------------------------------------------------------------------- plan
@@ -305,7 +306,7 @@ class HipShardEngine:
         self.origins = np.ascontiguousarray(origins, dtype=np.int32).reshape(-1, 3)
         self.acc, self.nacc = acc, nacc
         self.C = predictor.geom.num_classes
-        self._stage = None
+        self._scratch = Workspace(self.ctx)      # host-staged transport: the packed slabs
 
     def begin(self):
         self.acc.zero()
@@ -349,11 +350,7 @@ class HipShardEngine:
                                          ll3(vv, plane, 1)), "boa_copy3")
 
     def _staging(self, nbytes):
-        if self._stage is None or self._stage.nbytes < nbytes:
-            if self._stage is not None:
-                self._stage.free()
-            self._stage = self.ctx.alloc(nbytes)
-        return self._stage
+        return self._scratch.buf("stage", nbytes)
 
     def empty(self, lo, hi):
         import torch
@@ -406,9 +403,7 @@ class HipShardEngine:
             stage.free()
 
     def close(self):
-        if self._stage is not None:
-            self._stage.free()
-            self._stage = None
+        self._scratch.free()
 
 
 def all_reduce_labels(ctx, comm, buf, n: int):

@@ -181,6 +181,7 @@ def test_total_512_is_reproducible(ctx):
     atomics-free statistics and a fixed tile schedule make the result a function of (input, weights, tile batch)."""
     from boa_hip import label_maps, synthetic
     from boa_hip._lib import check
+    from boa_hip.device import Workspace
     from boa_hip.predictor import HipPredictor
     shape = [512, 512, 512]
     nvox = 512 ** 3
@@ -193,7 +194,7 @@ def test_total_512_is_reproducible(ctx):
         p.set_parameters([blob])
         preds.append((tid, p))
     ip = models[0][1].intensity_properties["0"]
-    work = {}
+    work = Workspace(ctx)
     runs = []
     for _ in range(2):
         check(ctx.lib.boa_ct_normalize(ctx.h, d_ct.vp, 0, d_vol.vp, nvox, ip["mean"], ip["std"], ip["percentile_00_5"],
@@ -221,7 +222,8 @@ def test_total_512_is_reproducible(ctx):
         assert len(np.unique(forms[0])) > 10
     for _, p in preds:
         p.close()
-    for b in list(work.values()) + [d_ct, d_vol, d_lab]:
+    work.free()
+    for b in [d_ct, d_vol, d_lab]:
         b.free()
 
 
@@ -230,6 +232,7 @@ def test_bca_folds_gather_equals_scatter_full_size(ctx):
     the size the bench runs it -- 154 x 512 x 512 at 5 mm slices, patch 128^3, step 0.5, 98 tiles per fold, 3 folds -- against
     the scatter form (accumulator planes + boa_finalize_labels)."""
     from boa_hip import plans
+    from boa_hip.device import Workspace
     from boa_hip.predictor import HipPredictor
     shape = [154, 512, 512]
     nvox = int(np.prod(shape))
@@ -240,7 +243,7 @@ def test_bca_folds_gather_equals_scatter_full_size(ctx):
     d_vol, d_lab = ctx.from_numpy(vol), ctx.alloc(nvox)
     p = HipPredictor(ctx, cfg.geometry, tile_step_size=0.5, max_batch=25)
     p.set_parameters(blobs)
-    work = {}
+    work = Workspace(ctx)
     forms = []
     try:
         for fused in (True, False):
@@ -254,7 +257,8 @@ def test_bca_folds_gather_equals_scatter_full_size(ctx):
         assert len(np.unique(forms[0])) >= 5
     finally:
         p.close()
-        for b in list(work.values()) + [d_vol, d_lab]:
+        work.free()
+        for b in [d_vol, d_lab]:
             b.free()
 
 

@@ -197,6 +197,53 @@ def test_task_reads_the_inf_flags_once_per_volume_and_still_raises(ctx):
     ts.close()
 
 
+@pytest.mark.parametrize("gather", [True, False])
+def test_two_predictors_share_one_workspace(ctx, gather):
+    """A 9-class and then a 5-class predictor (2 folds each, 8 tiles) run on one device.Workspace, so the second finds `fold` (and
+    in the scatter form `acc`) larger than it needs: each one's labels must equal those it produces with a private workspace
+    (work=None).  A dict is refused with TypeError, and after Workspace.free() a fresh workspace still runs."""
+    from boa_hip.device import Workspace
+    shape = (40, 44, 48)
+    nvox = int(np.prod(shape))
+    x = np.random.default_rng(9).standard_normal((1, *shape)).astype(np.float32)
+    preds = [_pred(ctx, (32, 32, 32), nc, 2, 0.5) for nc in (9, 5)]
+    dvol, lab = ctx.from_numpy(x), ctx.alloc(nvox)
+
+    def run(p, work):
+        lab.zero()
+        p.predict_segmentation_device(dvol, list(shape), lab, work=work)
+        return lab.download(shape, np.uint8)
+
+    ws = Workspace(ctx)
+    try:
+        for p in preds:
+            p.use_gather_head = gather
+        ctx.counters(reset=True)
+        want = [run(p, None) for p in preds]
+        heads = ctx.counters()
+        assert (heads["head_mfma"] + heads["head_valu"] == 0) == gather      # the form asked for is the form that ran
+        assert all(len(np.unique(w)) > 2 for w in want)
+        with pytest.raises(TypeError):
+            preds[0].predict_segmentation_device(dvol, list(shape), lab, work={})
+        got = [run(p, ws) for p in preds]
+        for name in ("fold",) if gather else ("fold", "acc"):
+            assert ws.buf(name, 1).nbytes == 9 * nvox * 2, name              # the first model's planes: grown once, never shrunk
+        for w, g in zip(want, got):
+            np.testing.assert_array_equal(g, w)
+        ws.free()
+        fresh = Workspace(ctx)
+        try:
+            np.testing.assert_array_equal(run(preds[1], fresh), want[1])
+        finally:
+            fresh.free()
+    finally:
+        ws.free()
+        for p in preds:
+            p.close()
+        dvol.free()
+        lab.free()
+
+
 @pytest.mark.parametrize("precision", ["fp16", "fp32"])
 @pytest.mark.parametrize("nc", [2, 4, 5, 13])
 def test_gather_ties_and_small_class_counts(ctx, nc, precision):

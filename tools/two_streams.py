@@ -11,7 +11,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "body-and-organ-analysis_amd")]
 import numpy as np  # noqa: E402
 from boa_hip import label_maps, synthetic  # noqa: E402
 from boa_hip._lib import check  # noqa: E402
-from boa_hip.device import Context  # noqa: E402
+from boa_hip.device import Context, Workspace  # noqa: E402
 from boa_hip.predictor import HipPredictor  # noqa: E402
 
 size = int(sys.argv[1]) if len(sys.argv) > 1 else 512
@@ -32,7 +32,7 @@ class Lane:
             self.preds.append((tid, p))
         self.d_ct = self.ctx.from_numpy(synthetic.ct_phantom(shape, seed=seed))
         self.d_vol, self.d_lab = self.ctx.alloc(nvox * 4), self.ctx.alloc(nvox)
-        self.work = {}
+        self.work = Workspace(self.ctx)
         self.ip = models[0][1].intensity_properties["0"]
 
     def step(self):
