@@ -42,46 +42,139 @@ __host__ __device__ constexpr int ns_sw_zp(int z) { return (z & 1) * NS_SW_ZODD 
 __host__ __device__ constexpr int ns_sw_slots() { return 9 * 9 * NS_SW_ROW; }            // slots of one k-half plane (+ 8 of padding: the dummy slot)
 __host__ __device__ constexpr int ns_sw_plane_bytes() { return (ns_sw_slots() + 8) * 16 + 64; }   // = 64 mod 128: the k-half planes' stores interleave
 
-// prod_commit / prod_commit_x3 (conv_ws_dev.h) with a per-item LDS offset instead of the linear voxel index
+// The block tile is 4 x 4 x 8 output voxels at stride 2 (conv_ns_tile): a 9 x 9 x 17 halo, NS_ITEMS rounds of WS_PROD / 2 voxels
+#define NS_HV (9 * 9 * 17)
+#define NS_ITEMS ((NS_HV + WS_PROD / 2 - 1) / (WS_PROD / 2))
+static_assert(NS_ITEMS <= WS_MAXV, "k_conv_ns: halo items per producer lane");
+
+// prod_setup_desc / prod_setup (conv_ws_dev.h) for the NS_ITEMS items of this halo: the input voxel indices of the tile's items; returns
+// the mask of the items inside the input tensor.  (Own copy: a ProdItems stays partly in scratch -- hipcc merges the classes' stores of
+// its last members into one store to a selected address -- and a scratch load among the halo loads is waited for with a vmcnt(0).)
+__device__ __forceinline__ unsigned ns_setup_desc(const ConvArgs& p, const TileDesc& d, const ProdConst& k, int (&gi)[NS_ITEMS]) {
+    const int cls = (d.flags >> 4) & 3;
+    const int base = d.ibase;
+    unsigned okm;
+    if (cls == 0) {
+        okm = k.in_halo;
+#pragma unroll
+        for (int j = 0; j < NS_ITEMS; ++j) gi[j] = base + k.rel[j];
+    } else if (cls == 1) {
+        unsigned out = 0;
+#pragma unroll
+        for (int f = 0; f < 6; ++f) out |= (d.flags >> (8 + f)) & 1 ? k.face[f] : 0u;
+        okm = k.in_halo & ~out;
+#pragma unroll
+        for (int j = 0; j < NS_ITEMS; ++j) gi[j] = ((okm >> j) & 1u) ? base + k.rel[j] : 0;
+    } else {   // the halo sticks out further (a volume smaller than a tile): per-item range checks as in prod_setup
+        const int ix0 = d.tc.ox0 * p.s0 - p.p0, iy0 = d.tc.oy0 * p.s1 - p.p1, iz0 = d.tc.oz0 * p.s2 - p.p2;
+        okm = 0;
+#pragma unroll
+        for (int j = 0; j < NS_ITEMS; ++j) {
+            const unsigned ix = (unsigned)(ix0 + (k.hc[j] & 1023)), iy = (unsigned)(iy0 + ((k.hc[j] >> 10) & 1023)),
+                           iz = (unsigned)(iz0 + (k.hc[j] >> 20));
+            const unsigned ok = (unsigned)(ix < (unsigned)p.Di) & (unsigned)(iy < (unsigned)p.Hi) & (unsigned)(iz < (unsigned)p.Wi) &
+                                ((k.in_halo >> j) & 1u);
+            gi[j] = ok ? base + k.rel[j] : 0;
+            okm |= ok << j;
+        }
+    }
+    return okm;
+}
+
+// A producer lane's registers.  d: its octet of its halo voxels, ONE set: an item of the chunk being committed until it is stored, then
+// the same item of the chunk after it.  s0 / s1, ok, live, has_ss: the (scale, shift) words (4 channel pairs x {scales, shifts}), the
+// masks (bit j: voxel j is inside the input tensor / belongs to the halo) and the transform flag of the chunk whose loads are in
+// flight; ns_roll_sw copies them when that chunk's commit begins.  (u32x4_t: a loop-carried uint4 is four scalars to hipcc, see touch128.)
+struct NsRegs {
+    u32x4_t d[NS_ITEMS];
+    u32x4_t s0, s1;
+    unsigned ok, live;
+    int has_ss;
+};
+
+// item j of prod_commit / prod_commit_x3 (conv_ws_dev.h) with a per-item LDS offset instead of the linear voxel index
 template <bool X3, bool SS, bool EDGE>
-__device__ __forceinline__ void ns_commit_items_sw(const ConvArgs& p, const ChunkRegs& rg, unsigned char* d0, const int (&off)[WS_MAXV], int plane,
-                                                   int nv, unsigned slope2) {
-    if (EDGE)
-        asm volatile("; commit sw: edge tile");
-    else
-        asm volatile("; commit sw: interior tile");
+__device__ __forceinline__ void ns_commit_item_sw(const ConvArgs& p, const u32x4_t& d, const unsigned (&w)[8], bool ok, unsigned char* d0, int off,
+                                                  int plane, unsigned slope2) {
+    if constexpr (X3) {
+        float y[4] = {__uint_as_float(d.x), __uint_as_float(d.y), __uint_as_float(d.z), __uint_as_float(d.w)};
+        if (SS) {
 #pragma unroll
-    for (int j = 0; j < WS_MAXV; ++j) {
-        if (j < nv) {
-            if constexpr (X3) {
-                float y[4] = {__uint_as_float(rg.d[j].x), __uint_as_float(rg.d[j].y), __uint_as_float(rg.d[j].z), __uint_as_float(rg.d[j].w)};
-                if (SS) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const float f = __builtin_fmaf(y[i], __uint_as_float(rg.ssw[2 * i]), __uint_as_float(rg.ssw[2 * i + 1]));
-                        y[i] = f > 0.f ? f : f * p.slope;
-                    }
-                }
-                uint2 hi, lo;
-                x3_split4(y, hi, lo);
-                if (EDGE && !((rg.ok >> j) & 1u)) hi = lo = make_uint2(0, 0);
-                *(uint2*)(d0 + off[j]) = hi;
-                *(uint2*)(d0 + plane + off[j]) = lo;
-            } else {
-                uint4 o = rg.d[j];
-                if (SS) o = norm_act8_pk(o, rg.ssw, slope2);
-                if (EDGE && !((rg.ok >> j) & 1u)) o = make_uint4(0, 0, 0, 0);
-                *(uint4*)(d0 + off[j]) = o;
+            for (int i = 0; i < 4; ++i) {
+                const float f = __builtin_fmaf(y[i], __uint_as_float(w[2 * i]), __uint_as_float(w[2 * i + 1]));
+                y[i] = f > 0.f ? f : f * p.slope;
             }
         }
+        uint2 hi, lo;
+        x3_split4(y, hi, lo);
+        if (EDGE && !ok) hi = lo = make_uint2(0, 0);
+        *(uint2*)(d0 + off) = hi;
+        *(uint2*)(d0 + plane + off) = lo;
+    } else {
+        uint4 o = make_uint4(d.x, d.y, d.z, d.w);
+        if (SS) o = norm_act8_pk(o, w, slope2);
+        if (EDGE && !ok) o = make_uint4(0, 0, 0, 0);
+        *(uint4*)(d0 + off) = o;
     }
 }
 
-template <bool X3>
-__device__ __forceinline__ void ns_commit_sw(const ConvArgs& p, ChunkRegs& rg, unsigned char* dst_in, const int (&off)[WS_MAXV], int q, int HV,
-                                             int plane, int dbg) {
-    const int nv = (dbg & 32) ? 0 : (HV + WS_PROD / 2 - 1) / (WS_PROD / 2);
-    if (rg.skip_halo) return;
+// One producer interval, rolling: item j of the chunk in rg.d is normalised and stored, and the register it leaves takes item j of
+// the following chunk (ISSUE; its source `nbase`, its voxel indices `gi`) -- the loads of a chunk go out while the one before it is
+// committed, with one register set and one chunk's bytes in flight.  The waits are hipcc's: loads return in order, behind item j are
+// NS_ITEMS - 1 - j items of its chunk, the two (scale, shift) loads and j items of the next chunk, and the compiled loop waits with
+// s_waitcnt vmcnt(10) in front of every item (profiles/r12_ns_rolling_isa_waits.txt; 12 would do).
+template <bool X3, bool SS, bool EDGE, bool ISSUE>
+__device__ __forceinline__ void ns_roll_items_sw(const ConvArgs& p, NsRegs& rg, const unsigned (&w_in)[8], unsigned ok, unsigned char* d0,
+                                                 const int (&off)[WS_MAXV], int plane, unsigned slope2, const unsigned char* nbase,
+                                                 const int (&gi)[NS_ITEMS], int q, int dbg) {
+    // The copies differ in their marker, and the (scale, shift) words pass through it: hipcc otherwise merges the copies back into one
+    // path with per-item masks, or hoists the transform of ALL items in front of the branch that picks the copy -- behind a vmcnt(0).
+    unsigned w[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) w[i] = w_in[i];
+#define NS_ROLL_MARK(text) \
+    asm volatile(text : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]), "+v"(w[4]), "+v"(w[5]), "+v"(w[6]), "+v"(w[7]), "+v"(slope2))
+    if (EDGE)
+        NS_ROLL_MARK("; roll sw: edge tile");
+    else
+        NS_ROLL_MARK("; roll sw: interior tile");
+#undef NS_ROLL_MARK
+#pragma unroll
+    for (int j = 0; j < NS_ITEMS; ++j) {
+        if (!(dbg & 32)) ns_commit_item_sw<X3, SS, EDGE>(p, rg.d[j], w, (ok >> j) & 1u, d0, off[j], plane, slope2);
+        // (the load stays behind the store of the item whose register it takes: scheduled ahead of it, it gets a register of its own)
+        __builtin_amdgcn_sched_barrier(0);
+        if (ISSUE && !(dbg & 128)) rg.d[j] = prod_load_item<u32x4_t>(nbase, gi[j], q);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// the head of an issue: the chunk's masks and its (scale, shift) loads, in front of its items
+__device__ __forceinline__ void ns_issue_head(const ChunkSrc& src, unsigned ok, unsigned live, int q, NsRegs& rg) {
+    rg.ok = ok;
+    rg.live = live;
+    rg.has_ss = src.ss != nullptr;
+    if (src.ss) prod_load_ss(src.ss, q, rg.s0, rg.s1);
+    __builtin_amdgcn_sched_barrier(0);   // (the items behind them, in every chunk: the waits of the interval loop count on one order)
+}
+
+// The chunk in `rg` (issued one interval ago) is committed; ISSUE: the chunk after it (source `src`, items `gi`, `iok`) takes its place
+template <bool X3, bool ISSUE>
+__device__ __forceinline__ void ns_roll_sw(const ConvArgs& p, NsRegs& rg, unsigned char* dst_in, const int (&off)[WS_MAXV], int q, int plane,
+                                           const ChunkSrc& src, const int (&gi)[NS_ITEMS], unsigned iok, unsigned live, int dbg) {
+    // this chunk's words and masks leave their registers HERE (the "+v"), in front of the loads that replace them.  hipcc waits with
+    // vmcnt(0) for the copy (it counts the path on which none of the four ifs below is taken): what was issued one interval ago has
+    // landed before the first item is committed, as it had before the loop rolled; the rolling overlaps the commit with the ISSUE of
+    // the next chunk, which the trace of the old loop showed to cost as much as the commit (profiles/NOTES_r12.md).
+    unsigned w[8] = {rg.s0.x, rg.s0.y, rg.s0.z, rg.s0.w, rg.s1.x, rg.s1.y, rg.s1.z, rg.s1.w};
+    asm volatile("" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]), "+v"(w[4]), "+v"(w[5]), "+v"(w[6]), "+v"(w[7]));
+    const unsigned ok = rg.ok;
+    const bool has_ss = rg.has_ss != 0;
+    // padding voxels must read as zero AFTER the transform; the four (transform, edge) combinations are separate straight-line
+    // copies (see prod_commit), chosen per chunk
+    const bool edge = __builtin_amdgcn_ballot_w64(rg.ok != rg.live) != 0;
+    int form = __builtin_amdgcn_readfirstlane((has_ss ? 2 : 0) | (edge ? 1 : 0));
+    if (ISSUE) ns_issue_head(src, iok, live, q, rg);
     union {
         unsigned u;
         h2_t v;
@@ -89,18 +182,16 @@ __device__ __forceinline__ void ns_commit_sw(const ConvArgs& p, ChunkRegs& rg, u
     sl2.v = h2_t{(_Float16)p.slope, (_Float16)p.slope};
     // fp16: lane q & 1 owns k-half plane q & 1 of its voxels; split precision: hi -> plane 0, lo -> plane 1, lane q & 1 the 8-byte half
     unsigned char* d0 = X3 ? dst_in + (q & 1) * 8 : dst_in + (q & 1) * plane;
-    const bool edge = __builtin_amdgcn_ballot_w64(rg.ok != rg.live) != 0;
-    if (rg.has_ss) {
-        if (edge)
-            ns_commit_items_sw<X3, true, true>(p, rg, d0, off, plane, nv, sl2.u);
-        else
-            ns_commit_items_sw<X3, true, false>(p, rg, d0, off, plane, nv, sl2.u);
-    } else {
-        if (edge)
-            ns_commit_items_sw<X3, false, true>(p, rg, d0, off, plane, nv, sl2.u);
-        else
-            ns_commit_items_sw<X3, false, false>(p, rg, d0, off, plane, nv, sl2.u);
-    }
+    // Four ifs in a row, not an if / else tree: hipcc chains the arms of a tree through flow blocks in which the registers one arm has
+    // re-loaded stay live beside those the next arm reads -- a second register set, moved back behind a vmcnt(0) at the end of the
+    // interval.  Here every arm takes the set and leaves it in place (the empty asm: or the ifs become one switch, a tree again).
+    if (form == 3) ns_roll_items_sw<X3, true, true, ISSUE>(p, rg, w, ok, d0, off, plane, sl2.u, src.base, gi, q, dbg);
+    asm volatile("" : "+s"(form));
+    if (form == 2) ns_roll_items_sw<X3, true, false, ISSUE>(p, rg, w, ok, d0, off, plane, sl2.u, src.base, gi, q, dbg);
+    asm volatile("" : "+s"(form));
+    if (form == 1) ns_roll_items_sw<X3, false, true, ISSUE>(p, rg, w, ok, d0, off, plane, sl2.u, src.base, gi, q, dbg);
+    asm volatile("" : "+s"(form));
+    if (form == 0) ns_roll_items_sw<X3, false, false, ISSUE>(p, rg, w, ok, d0, off, plane, sl2.u, src.base, gi, q, dbg);
 }
 
 // One 16-channel chunk: acc[r] += sum over the 27 taps.  b0p: LDS address of this lane's voxel in plane 0 of the wave's
@@ -206,7 +297,7 @@ __global__ __launch_bounds__(WS_THREADS) void k_conv_ns(ConvArgs p, int dbg_arg,
         // ---- producer waves: as in k_conv_ws without the weight staging (chunk g + 1 committed while the consumers work on
         // chunk g, its global loads issued one barrier interval earlier)
         const int q = tid - 256;
-        const ProdConst pc = prod_const(p, q, HV);
+        ProdConst pc = prod_const(p, q, HV);
         // SW layout: this lane's LDS byte offset of its halo voxels (kernel constants, like pc.rel)
         int ldso[WS_MAXV];
 #pragma unroll
@@ -221,36 +312,28 @@ __global__ __launch_bounds__(WS_THREADS) void k_conv_ns(ConvArgs p, int dbg_arg,
         TileCoord& ptc = pd.tc;
         int pk = 0;
         ptc.n = ptc.cy = ptc.ox0 = ptc.oy0 = ptc.oz0 = ptc.sp = 0;
-        ProdItems items;
+        int gi[NS_ITEMS];   // input voxel indices of the items of the tile being issued, and the mask of those inside the input tensor
+        unsigned iok = 0;
 #pragma unroll
-        for (int j = 0; j < WS_MAXV; ++j) items.gi[j] = 0;
-        items.ok = 0;
-        // Two register sets (PF2): the loads of chunk g + 2 are issued at the HEAD of the interval, before chunk g + 1 is committed, so
-        // they have a whole barrier interval to land.  The stride-2 layers stage 8 input voxels per output voxel and are bound by
-        // the producers' HBM / L2 round trips (trace of an interior workgroup, 32 -> 64 @128^3: 330 + 1 220 cycles per tile waiting for
-        // loads that were issued behind the previous commit); k_conv_ns has no weight DMA whose vmcnt(0) would also wait for
-        // them (what made the same change a loss in k_conv_ws).  The interval loop is unrolled by two so that the sets alternate
-        // without copies.  A/B on one box (tools/ab_layers.sh, batch 8): 64 -> 128 @64^3 -5 %, 128 -> 256 @32^3 -8 %, 256 -> 320 @16^3
-        // -8 %; the 32 -> 64 layer at 128^3 (RM = 2: HBM-cold input, 3.6 TB/s of halo traffic) +16 % -- twice the loads in flight per
-        // CU there only deepen the queue in front of the memory side -- so that instantiation keeps one set.
-        constexpr bool PF2 = RM == 4;
-        ChunkRegs rgA, rgB;
-        auto clear_regs = [&](ChunkRegs& rg) {
+        for (int j = 0; j < NS_ITEMS; ++j) gi[j] = 0;
+        // Rolling commit / issue (ns_roll_items_sw): the loads of chunk g + 2 go out item by item while chunk g + 1 is committed, each
+        // into the register its item has just left.  "Commit all, then issue all" spent 2 200 cycles of a 4 700-cycle interval on the
+        // commit and 1 900 on the issue of 11 loads per lane (trace of an interior workgroup, 32 -> 64 @128^3, batch 25: the memory pipe
+        // takes the loads at the rate it serves them) with the memory pipe idle during the first and the LDS idle during the second.
+        // A/B on one box (tools/ab_layers.sh, batch 25 / 8): 32 -> 64 @128^3 -19 / -18 %, 64 -> 128 @64^3 -8 / -11 %, 128 -> 256 @32^3
+        // -12 / -7 %, 256 -> 320 @16^3 -20 / -12 %.  The second register set the RM = 4 instantiations had (loads of chunk g + 2 at the
+        // head of the interval: twice the bytes in flight, +16 % on the 32 -> 64 layer) lost to this loop on every layer and is gone.
+        NsRegs rg;
 #pragma unroll
-            for (int j = 0; j < WS_MAXV; ++j) rg.d[j] = make_uint4(0, 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) rg.ssw[j] = 0;
-            rg.ok = rg.live = 0;
-            rg.has_ss = 0;
-            rg.skip_halo = 0;
-            rg.cc = rg.cy = 0;
-        };
-        clear_regs(rgA);
-        clear_regs(rgB);
+        for (int j = 0; j < NS_ITEMS; ++j) rg.d[j] = u32x4_t{0, 0, 0, 0};
+        rg.s0 = rg.s1 = u32x4_t{0, 0, 0, 0};
+        rg.ok = rg.live = 0;
+        rg.has_ss = 0;
         int pcc = 0;
         int ptr_n = 0;
         // debug timeline of producer wave 4 of the traced block (second half of the trace buffer): 1 barrier passed, 8 next tile set up,
-        // 7 loads landed, 2 chunk committed, 3 next loads issued
+        // 2 chunk committed and the next one issued.  (The stamp is a global store: while it is pending hipcc waits with vmcnt(0) for every
+        // item, so the traced build's producers run item by item at the memory latency -- its timeline shows the roles, not the rates.)
 #define NS_PSTAMP(code)                                                                                                          \
     do {                                                                                                                         \
         if (WS_TRACING && (int)blockIdx.x == tr_blk && wave == 4 && lane == 0 && ptr_n < WS_TRACE_SLOTS / 2 - 8) {                                  \
@@ -259,58 +342,48 @@ __global__ __launch_bounds__(WS_THREADS) void k_conv_ns(ConvArgs p, int dbg_arg,
         }                                                                                                                        \
     } while (0)
         const bool live = !(dbg & 2);
-        auto setup_next = [&]() {   // descriptor + halo addresses of the next tile (before its first chunk is issued)
-            pd = load_desc(drow, ++pk);
-            prod_setup_desc(p, pd, pc, items);
-            NS_PSTAMP(8);
-        };
-        auto issue = [&](ChunkRegs& rg) {
-            prod_issue(p, ptc, items, pc.in_halo, pcc, false, q, dbg, rg);
-            if (++pcc == ncc) pcc = 0;
-            NS_PSTAMP(3);
-        };
-        auto commit = [&](ChunkRegs& rg, unsigned char* dst) {
-            if (WS_TRACING) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                NS_PSTAMP(7);
-            }
-            ns_commit_sw<X3>(p, rg, dst, ldso, q, HV, plane, dbg);
-            NS_PSTAMP(2);
-        };
-        if (live && my_chunks > 0) {
+        if (live && my_chunks > 0) {   // chunk 0: all of it
             pd = load_desc(drow, 0);
-            prod_setup_desc(p, pd, pc, items);
-            prod_issue(p, ptc, items, pc.in_halo, 0, false, q, dbg, rgA);
+            iok = ns_setup_desc(p, pd, pc, gi);
+            const ChunkSrc src = prod_chunk_src(p, ptc.n, 0, dbg);
+            ns_issue_head(src, iok, pc.in_halo, q, rg);
+#pragma unroll
+            for (int j = 0; j < NS_ITEMS; ++j)
+                if (!(dbg & 128)) rg.d[j] = prod_load_item<u32x4_t>(src.base, gi[j], q);
             if (++pcc == ncc) pcc = 0;
         }
-        if constexpr (PF2) {
-            auto interval = [&](int g, ChunkRegs& cur, ChunkRegs& nxt) {
-                if (live && g + 1 < my_chunks) {
-                    NS_PSTAMP(1);
-                    if (g + 2 < my_chunks) {
-                        if (pcc == 0) setup_next();
-                        issue(nxt);
-                    }
-                    commit(cur, bufs + ((g + 1) & 1) * buf_bytes);
-                }
-                __syncthreads();
-            };
-            for (int g = -1; g < my_chunks; g += 2) {
-                interval(g, rgA, rgB);
-                if (g + 1 < my_chunks) interval(g + 1, rgB, rgA);
+        // interval g: chunk g + 1 is committed while the consumers work on chunk g, and chunk g + 2 is issued; behind the workgroup's
+        // last chunk nothing is issued
+        for (int g = -1; live && g + 2 < my_chunks; ++g) {
+            NS_PSTAMP(1);
+            if (pcc == 0) {   // descriptor + halo addresses of the next tile, before its first chunk is issued
+                pd = load_desc(drow, ++pk);
+                // (the general halo class unpacks pc.hc and pc.in_halo per item: hipcc hoists the ~50 unpacked words out of
+                //  the interval loop and spills them unless they vary with it)
+#pragma unroll
+                for (int j = 0; j < WS_MAXV; ++j) asm volatile("" : "+v"(pc.hc[j]));
+                asm volatile("" : "+v"(pc.in_halo));
+                iok = ns_setup_desc(p, pd, pc, gi);
+                NS_PSTAMP(8);
             }
-        } else {
-            for (int g = -1; g < my_chunks; ++g) {
-                if (live && g + 1 < my_chunks) {
-                    NS_PSTAMP(1);
-                    const bool do_issue = g + 2 < my_chunks;
-                    if (do_issue && pcc == 0) setup_next();   // (before the commit: the loads go out right behind it, see k_conv_ws)
-                    commit(rgA, bufs + ((g + 1) & 1) * buf_bytes);
-                    if (do_issue) issue(rgA);
-                }
-                __syncthreads();
-            }
+            const ChunkSrc src = prod_chunk_src(p, ptc.n, pcc, dbg);
+            if (++pcc == ncc) pcc = 0;
+            ns_roll_sw<X3, true>(p, rg, bufs + ((g + 1) & 1) * buf_bytes, ldso, q, plane, src, gi, iok, pc.in_halo, dbg);
+            NS_PSTAMP(2);
+            __syncthreads();
         }
+        if (live && my_chunks > 0) {
+            NS_PSTAMP(1);
+            ChunkSrc none;
+            none.base = nullptr;
+            none.ss = nullptr;
+            ns_roll_sw<X3, false>(p, rg, bufs + ((my_chunks - 1) & 1) * buf_bytes, ldso, q, plane, none, gi, iok, pc.in_halo, dbg);
+            NS_PSTAMP(2);
+            __syncthreads();
+        }
+        if (!live)   // (ablation without the producers: the barriers alone)
+            for (int g = -1; g + 1 < my_chunks; ++g) __syncthreads();
+        __syncthreads();   // the consumers' last chunk
         return;
     }
 
@@ -613,7 +686,8 @@ int launch_conv_ns(boa_ctx* ctx, const ConvArgs& a_in, const ConvTile& t, double
     BOA_REQUIRE((double)a.Di * a.Hi * a.Wi <= 16777216.0, "conv_ns: more than 2^24 input voxels per sample (24-bit offset multiply)");
     BOA_REQUIRE((double)a.Di * a.Hi * a.Wi * std::max(a.C0, a.C1) * 2.0 < 4294967296.0,
                 "conv_ns: one sample of the input exceeds 4 GiB (32-bit voxel offsets)");
-    BOA_REQUIRE(2 * t.h[0] * t.h[1] * t.h[2] <= WS_PROD * WS_MAXV, "conv_ns: halo too large");
+    BOA_REQUIRE(t.h[0] == 9 && t.h[1] == 9 && t.h[2] == 17 && a.h0 * a.h1 * a.h2 == NS_HV && a.xs == a.h1 * a.h2,
+                "conv_ns: the producers are unrolled for the 9 x 9 x 17 halo");
 #ifdef WS_WITH_TRACE
     static const bool want_trace = getenv("BOA_WS_TRACE") != nullptr;
 #else

@@ -388,6 +388,45 @@ struct ChunkRegs {
     int cc, cy;           // k_conv_ws: (chunk, cout chunk) the set was issued for -- the weights follow by DMA at commit time
 };
 
+// prod_issue in pieces, for a producer that re-issues a chunk item by item (k_conv_ns).  The source of one chunk of sample n: its plane
+// of the chunk-planar activations and its 16 (scale, shift) words (null: raw input); both are wave-uniform.
+struct ChunkSrc {
+    const unsigned char* base;
+    const unsigned* ss;
+};
+
+__device__ __forceinline__ ChunkSrc prod_chunk_src(const ConvArgs& p, int n, int cc, int dbg) {
+    int cg = cc * 16;
+    const size_t in_vox = (size_t)p.Di * p.Hi * p.Wi;
+    ChunkSrc s;
+    if (cg < p.C0) {
+        s.base = (const unsigned char*)(p.src0 + ((size_t)n * p.C0 + cg) * in_vox);
+        s.ss = p.ss16_0 ? p.ss16_0 + ((size_t)n * p.C0 + cg) : nullptr;
+    } else {
+        cg -= p.C0;
+        s.base = (const unsigned char*)(p.src1 + ((size_t)n * p.C1 + cg) * in_vox);
+        s.ss = p.ss16_1 ? p.ss16_1 + ((size_t)n * p.C1 + cg) : nullptr;
+    }
+    if (dbg & 64) s.ss = nullptr;
+    return s;
+}
+
+// one (voxel, octet) item in prod_issue's scalar-base form
+// (T: uint4, or u32x4_t where the item has to stay ONE 128-bit value for the register allocator, see touch128)
+template <typename T>
+__device__ __forceinline__ T prod_load_item(const unsigned char* sbase, int gi, int q) {
+    return *(const T*)(sbase + (__umul24((unsigned)gi, 32u) + (unsigned)(q & 1) * 16u));
+}
+
+// this lane's octet of the chunk's (scale, shift) words
+template <typename T>
+__device__ __forceinline__ void prod_load_ss(const unsigned* ss, int q, T& s0, T& s1) {
+    unsigned so = (unsigned)(q & 1) * 32u;
+    asm volatile("" : "+v"(so));  // keep the 32 -> 64 bit extension in this block: scalar-base load form
+    s0 = *(const T*)((const unsigned char*)ss + so);
+    s1 = *(const T*)((const unsigned char*)ss + so + 16);
+}
+
 __device__ __forceinline__ void prod_issue(const ConvArgs& p, const TileCoord& tc, const ProdItems& it, unsigned live, int cc,
                                            bool skip_halo, int q, int dbg, ChunkRegs& rg) {
     int cg = cc * 16;
