@@ -96,6 +96,8 @@ _PROTOS = {
     "boa_tissue_projections": (i32, [vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, vp, vp]),
     "boa_label_hu_histogram": (i32, [vp, vp, vp, vp, u64, i32, i32, vp]),
     "boa_label_hu_mask": (i32, [vp, vp, vp, vp, i32, i32, i32, u64, vp]),
+    "boa_label_basic_stats": (i32, [vp, vp, i32, vp, ip, i32, vp]),
+    "boa_label_apply_lut": (i32, [vp, vp, u64, vp, vp]),
     "boa_group_stats_f64": (i32, [vp, vp, vp, u64, vp, i32, vp, vp]),
     "boa_label_hu_mask_f64": (i32, [vp, vp, vp, vp, i32, C.c_double, C.c_double, u64, vp]),
     "boa_tissue_aggregate_f64": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]),

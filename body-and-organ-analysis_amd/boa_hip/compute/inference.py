@@ -17,10 +17,10 @@ from typing import Any, Dict, Iterable, Optional, Union
 
 import numpy as np
 
-from .. import label_maps, model_store, nifti, orientation
+from .. import label_maps, model_store, nifti, orientation, statistics
 from ..device import Context
 from ..pipeline import BcaPipelineHip
-from ..task import SegmentationTask, run_cascade_task, run_with_body_crop
+from ..task import SegmentationTask, run_cascade_task, run_roi_subset, run_with_body_crop
 from .config import resolve_device
 from .constants import BASE_MODELS
 from .measurements import compute_measurements
@@ -117,34 +117,78 @@ def compute_all_models(
     return stats
 
 
+def total_model_key(fast: bool, fastest: bool) -> str:
+    """model_store.TASKS key of task `total` (TS/python_api.py:168-189): `fast` -> Dataset297 at 3 mm, else `fastest` -> Dataset298 at
+    6 mm, else the five part models at 1.5 mm."""
+    return "total_fast" if fast else ("total_6mm" if fastest else "total")
+
+
 def _segment_one(ctx, name, ct, affine, hdr, folder, fast, recompute, totalsegmentator_params=None):
     """One TotalSegmentator-style model -> `<name>.nii.gz` with the label table in the header extension.  Of the TotalSegmentator
-    parameters `remove_small_blobs` (`total`, `body`) and `body_seg` (`total`) are honoured; both default to off."""
+    parameters these are honoured; all default to off, and without them every output is what it was:
+      `remove_small_blobs` (`total`, `body`), `body_seg` (`total`);
+      `fastest` (`total`: Dataset298 at 6 mm, TS/python_api.py:176-181; `fast` wins when both are set);
+      `roi_subset` / `roi_subset_robust` (`total`; TS/python_api.py:655-736): rough model, crop, only the part models that hold the
+          names, only their labels in the volume and in the header's label table (`task.run_roi_subset`); switches `body_seg` off;
+      `statistics` with `statistics_exclude_masks_at_border` (default on), `stats_aggregation` (mean | median) and
+          `statistics_normalized_intensities` (TS/python_api.py:636-641,778-796): `statistics.json` next to the label volume, from
+          one device pass (`boa_hip/statistics.py`) -- on the input grid, or with `fast` on the model grid (`statistics_fast`)."""
     params = totalsegmentator_params or {}
     small_blobs = bool(params.get("remove_small_blobs", False))
+    roi_subset, robust = params.get("roi_subset"), False
+    if params.get("roi_subset_robust") is not None:              # TS/python_api.py:655-664
+        roi_subset, robust = params["roi_subset_robust"], True
+    if roi_subset is not None and type(roi_subset) is not list:
+        raise ValueError("roi_subset must be a list of strings")
+    if roi_subset is not None and not name.startswith("total"):
+        raise ValueError("roi_subset only works with task 'total' or 'total_mr'")
+    want_stats = bool(params.get("statistics", False))
+    stats_kw = dict(exclude_masks_at_border=bool(params.get("statistics_exclude_masks_at_border", True)), roi_subset=roi_subset,
+                    metric=params.get("stats_aggregation", "mean"),
+                    normalized_intensities=bool(params.get("statistics_normalized_intensities", False)))
+    # statistics together with fast are taken on the downsampled image inside the task (TS/python_api.py:636-641)
+    stats_fast = {"params": dict(stats_kw, file_out=folder / "statistics.json")} if (want_stats and fast) else None
     target = folder / f"{name}.nii.gz"
     logger.info("Computing model %s...", name)
     if target.is_file() and not recompute:
         logger.info("The model was already computed, skipping...")
         return
     if name == "total":
-        key = "total_fast" if fast else "total"
-        if params.get("body_seg", False):                       # TS/python_api.py:739-764
+        key = total_model_key(fast, bool(params.get("fastest", False)))
+        multimodel = key == "total"
+        resample = model_store.TASKS[key]["resample"]
+        if roi_subset is not None:                                # (body_seg cannot be used together with it, TS/python_api.py:675)
+            selected = label_maps.parts_for_roi_subset(roi_subset) if multimodel else None
+            rough = "total_fast" if robust else "total_6mm"
+            seg = run_roi_subset(ctx, ct, affine, model_store.load_task_models(rough), model_store.load_task_models(key, task_ids=selected),
+                                 roi_subset, resample=resample, multimodel=multimodel, rough_resample=model_store.TASKS[rough]["resample"],
+                                 remove_small_blobs=small_blobs, force_split=bool(params.get("force_split", False)),
+                                 statistics_out=stats_fast)
+        elif params.get("body_seg", False):                       # TS/python_api.py:739-764
+            if stats_fast is not None:
+                raise NotImplementedError("statistics together with fast and body_seg")
             seg = run_with_body_crop(ctx, "total", ct, affine, model_store.load_task_models("body_fast"), model_store.load_task_models(key),
-                                     resample=model_store.TASKS[key]["resample"], multimodel=not fast, remove_small_blobs=small_blobs)
+                                     resample=resample, multimodel=multimodel, remove_small_blobs=small_blobs)
         else:
-            task = SegmentationTask(ctx, "total", model_store.load_task_models(key), resample=model_store.TASKS[key]["resample"],
-                                    multimodel=not fast)
+            task = SegmentationTask(ctx, "total", model_store.load_task_models(key), resample=resample, multimodel=multimodel)
             try:
-                seg = task.predict_image(ct, affine, remove_small_blobs=small_blobs)
+                if stats_fast is None:
+                    seg = task.predict_image(ct, affine, remove_small_blobs=small_blobs)
+                else:
+                    seg = task.predict_image(ct, affine, remove_small_blobs=small_blobs, statistics_out=stats_fast)
             finally:
                 task.close()
         names = label_maps.CLASS_MAP_TOTAL
+        if roi_subset is not None:
+            names = {k: v for k, v in names.items() if v in roi_subset}
     elif name == "body":                                        # TS/python_api.py:272-287
         key = "body_fast" if fast else "body"
         task = SegmentationTask(ctx, "body", model_store.load_task_models(key), resample=model_store.TASKS[key]["resample"], multimodel=False)
         try:
-            seg = task.predict_image(ct, affine, remove_small_blobs=small_blobs)
+            if stats_fast is None:
+                seg = task.predict_image(ct, affine, remove_small_blobs=small_blobs)
+            else:
+                seg = task.predict_image(ct, affine, remove_small_blobs=small_blobs, statistics_out=stats_fast)
         finally:
             task.close()
         names = label_maps.class_map("body")
@@ -158,6 +202,9 @@ def _segment_one(ctx, name, ct, affine, hdr, folder, fast, recompute, totalsegme
                                rough_resample=model_store.TASKS[rough]["resample"], remove_outside=info.get("remove_outside"),
                                remove_outside_dilation=info.get("remove_outside_dilation"))
         names = label_maps.class_map(name)
+    if want_stats and not fast:                                 # get_basic_statistics(seg, ct_img, ...), TS/python_api.py:778-796
+        statistics.basic_statistics(ctx, seg, ct, np.asarray(hdr.get_zooms()[:3], dtype=np.float32), task=name,
+                                    file_out=folder / "statistics.json", **stats_kw)
     nifti.save_volume(target, seg, affine, ctx=ctx, like=hdr, extensions=[(0, nifti.label_xml(names))])
 
 

@@ -75,6 +75,27 @@ def part_lut(task_id: int):
     return lut
 
 
+def parts_for_roi_subset(names):
+    """Task ids of the `total` part models whose class map holds any of `names`, in part order (TS/nnunet.py:519-529: with
+    `roi_subset` only those parts are computed).  A name outside the `total` class map raises KeyError naming it, as the
+    reference's `class_map_inv[roi]` does when it builds the crop mask (TS/python_api.py:723-724)."""
+    names = list(names)
+    unknown = [n for n in names if n not in CLASS_MAP_TOTAL_INV]
+    if unknown:
+        raise KeyError(f"roi_subset: {unknown} not in the class map of task total")
+    return [tid for tid in PART_TASK_IDS if any(n in names for n in CLASS_MAP_PARTS[tid].values())]
+
+
+def subset_lut(names):
+    """uint8[256] table of `img_data *= np.isin(img_data, subset labels)` (TS/nnunet.py:388-390,707-709): a `total` label of `names`
+    maps to itself, every other value to 0."""
+    import numpy as np
+    lut = np.zeros(256, dtype=np.uint8)
+    for n in names:
+        lut[CLASS_MAP_TOTAL_INV[n]] = CLASS_MAP_TOTAL_INV[n]
+    return lut
+
+
 # ---- label tables of the other models BOA measures (data file generated from the reference tables, pinned by G11) ----
 _DATA = None
 

@@ -85,13 +85,21 @@ def find_dataset_dir(dataset_id: int, root: str = None) -> str:
     return os.path.join(root, hits[0])
 
 
-def load_task_models(task: str, fast_bca: bool = False, root: str = None, configuration: str = "3d_fullres"
-                     ) -> List[Tuple[int, P.ModelConfig, List[np.ndarray]]]:
-    """-> [(task_id, ModelConfig, [weight blob per fold])] for SegmentationTask."""
+def load_task_models(task: str, fast_bca: bool = False, root: str = None, configuration: str = "3d_fullres",
+                     task_ids: Sequence[int] = None) -> List[Tuple[int, P.ModelConfig, List[np.ndarray]]]:
+    """-> [(task_id, ModelConfig, [weight blob per fold])] for SegmentationTask.  `task_ids`: load only these of the task's models
+    (in the task's order; `roi_subset` computes 1-2 of the 5 parts of `total`) -- the folders of the others are not even looked up."""
     info = TASKS[task]
     folds = [0] if (fast_bca and task in ("body_parts", "body_regions")) else info["folds"]
+    if task_ids is not None:
+        task_ids = [int(t) for t in task_ids]
+        foreign = [t for t in task_ids if t not in info["task_id"]]
+        if foreign:
+            raise ValueError(f"task {task} has no models {foreign} (its models: {info['task_id']})")
     out = []
     for tid in info["task_id"]:
+        if task_ids is not None and tid not in task_ids:
+            continue
         folder = os.path.join(find_dataset_dir(tid, root), f"{info['trainer']}__nnUNetPlans__{configuration}")
         cfg = P.load_model_folder(folder, configuration)
         if folds is None:  # nnU-Net: use every fold present (predict_from_raw_data.py:68-73 auto-detection)

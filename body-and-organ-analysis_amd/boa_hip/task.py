@@ -19,6 +19,7 @@ model's plans (`boa_hip/nnunet_resample.py`); it is the identity at every BASELI
 from __future__ import annotations
 
 import contextlib
+import ctypes as C
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -352,7 +353,8 @@ class SegmentationTask:
     def predict_image(self, data, affine: np.ndarray, force_split: bool = False,
                       crop_mask: Optional[np.ndarray] = None, crop_addon=(3, 3, 3), axcodes: str = "RAS",
                       return_device: bool = False, save_probabilities=None, remove_small_blobs: bool = False,
-                      model_grid_out: Optional[dict] = None):
+                      model_grid_out: Optional[dict] = None, roi_subset: Optional[Sequence[str]] = None,
+                      statistics_out: Optional[dict] = None):
         """CT array in file axis order + its affine -> uint8 label array on the same grid.  The volume is uploaded
         once; reorientation, crops, splits and restores are device views / copies, resampling and inference run on the
         device, only the final label volume comes back.  `data` may be a resident DevArray (not freed here);
@@ -372,7 +374,21 @@ class SegmentationTask:
         resample back (`_postprocess_model_grid`): task `body` always keeps the largest blob of `body_trunc` and drops the blobs
         of `body_extremities` of at most 50 000 mm^3; `remove_small_blobs=True` then drops, for every label of the task's class
         map, the blobs of at most 200 mm^3.  Not implemented for the sharded modes.  `model_grid_out` (a dict; test seam): gets
-        `labels`, the model-grid label array (x, y, z) BEFORE that post-processing, and `zooms`, its float32 header zooms."""
+        `labels`, the model-grid label array (x, y, z) BEFORE that post-processing, and `zooms`, its float32 header zooms; with
+        `statistics_out` also `labels_post`, the labels AFTER it, and `ct`, the model-grid image (the two arrays the statistics see).
+
+        `roi_subset` (names of the task's class map; nnUNet_predict_image(roi_subset=...), TS/nnunet.py:388-390,707-709): on the
+        input grid, after the restore, every label that is not one of them is cleared -- one look-up table pass on the device
+        (`boa_label_apply_lut`).  Which part models run is the caller's choice of `models` (`run_roi_subset`).
+
+        `statistics_out` (a dict; `statistics_fast` of TS/python_api.py:636-641, TS/nnunet.py:642-659): get_basic_statistics on the
+        MODEL grid -- the resampled (and cropped) canonical image and the labels after the blob post-processing, before the resample
+        back, header zooms those of that grid -- through `statistics.basic_statistics`; `statistics_out["params"]` (optional) holds
+        its keyword arguments (exclude_masks_at_border, roi_subset, metric, normalized_intensities, file_out), the result goes to
+        `statistics_out["stats"]`.  Neither is implemented for the sharded modes."""
+        if (roi_subset is not None or statistics_out is not None) and (self.shard is not None or self.model_shard is not None):
+            raise NotImplementedError("roi_subset / statistics with a tile- or model-sharded task")
+        keep_lut = None if roi_subset is None else label_maps.subset_lut(roi_subset)
         if save_probabilities is not None and (self.shard is not None or self.model_shard is not None):
             raise NotImplementedError("save_probabilities with a tile- or model-sharded task")
         blob_pp = bool(remove_small_blobs) or self.task_name == "body"
@@ -469,6 +485,12 @@ class SegmentationTask:
                 model_grid_out["labels"], model_grid_out["zooms"] = seg.download(), zooms_rsp
             if blob_pp:
                 self._postprocess_model_grid(seg, zooms_rsp, bool(remove_small_blobs))
+            if statistics_out is not None:
+                from . import statistics as st
+                statistics_out["stats"] = st.basic_statistics(ctx, seg, img_rsp, zooms_rsp, task=self.task_name,
+                                                              **dict(statistics_out.get("params") or {}))
+                if model_grid_out is not None:
+                    model_grid_out["labels_post"], model_grid_out["ct"] = seg.download(), img_rsp.download()
             if zoom is not None:                                         # back to the input grid (TS/nnunet.py:685-687)
                 if tuple(in_shape) != tuple(ss):
                     buf = rs.resample_nearest_device(ctx, seg.buf, ss, in_shape)
@@ -484,6 +506,10 @@ class SegmentationTask:
                 out = full
             if tuple(out.shape) != orig_shape[:3]:
                 raise ValueError(f"shape mismatch after restore: {out.shape} vs {orig_shape}")   # check_if_shape_and_affine_identical
+            if keep_lut is not None:                                     # img_data *= np.isin(img_data, subset), TS/nnunet.py:707-709
+                out = own(out.contiguous(force_copy=True))
+                check(ctx.lib.boa_label_apply_lut(ctx.h, out.buf.vp, out.size, keep_lut.ctypes.data_as(C.c_void_p), out.buf.vp),
+                      "boa_label_apply_lut")
             if return_device:
                 return sc.release(out.contiguous(force_copy=(resident and out.buf is data.buf)))
             return out.download()
@@ -552,6 +578,55 @@ def run_cascade_task(ctx: Context, task: str, data: np.ndarray, affine: np.ndarr
         vx = int(remove_outside_dilation / np.mean(zooms))
         seg = remove_outside_of_mask(ctx, seg, remove_mask, addon=vx)
     return seg
+
+
+def rough_crop_mask(ctx: Context, data, affine: np.ndarray, rough_models, names: Sequence[str], rough_resample: float = 6.0,
+                    max_batch: int = 16, precision: Optional[str] = None) -> np.ndarray:
+    """The crop mask of `roi_subset` (TS/python_api.py:705-725): the rough single-model `total` segmentation at `rough_resample` mm,
+    then the union of the `names` structures as a uint8 0 / 1 mask on the input grid."""
+    rough = SegmentationTask(ctx, "total", rough_models, resample=rough_resample, multimodel=False, max_batch=max_batch, precision=precision)
+    try:
+        organ_seg = rough.predict_image(data, affine)
+    finally:
+        rough.close()
+    return np.isin(organ_seg, [label_maps.CLASS_MAP_TOTAL_INV[n] for n in names]).astype(np.uint8)
+
+
+def run_roi_subset(ctx: Context, data, affine: np.ndarray, rough_models, task_models, roi_subset: Sequence[str],
+                   resample: Optional[float] = 1.5, multimodel: bool = True, rough_resample: float = 6.0, max_batch: int = 16,
+                   precision: Optional[str] = None, remove_small_blobs: bool = False, force_split: bool = False,
+                   statistics_out: Optional[dict] = None, model_grid_out: Optional[dict] = None, info_out: Optional[dict] = None) -> np.ndarray:
+    """`roi_subset` of task `total` (TS/python_api.py:655-736, TS/nnunet.py:388-390,519-531,707-709): a rough `total` segmentation
+    (single model Dataset298 at 6 mm; with `roi_subset_robust` Dataset297 at 3 mm: `rough_models`, `rough_resample`) -> crop mask =
+    union of the named structures -> the image cropped to it plus 20 mm -> of the five part models only those whose class map holds
+    one of the names (`label_maps.parts_for_roi_subset`; the others in `task_models` are never instantiated, and
+    `model_store.load_task_models(task_ids=...)` need not even have read them), merged in part order -> on the input grid every label
+    outside the subset cleared.  `multimodel=False` (`fast`: the single model Dataset297) has no part selection, only crop and filter.
+    An empty crop mask gives the all-zero volume without running a part model.  `remove_small_blobs`, `force_split`,
+    `statistics_out` and `model_grid_out` are those of `SegmentationTask.predict_image`; `info_out` (a dict; test seam) gets
+    `task_ids`, the models that were instantiated, and `crop_mask`.  Names outside the class map raise KeyError."""
+    roi_subset = list(roi_subset)
+    selected = label_maps.parts_for_roi_subset(roi_subset)        # (validates the names also when there is nothing to select)
+    if multimodel:
+        have = [m[0] for m in task_models]
+        missing = [t for t in selected if t not in have]
+        if missing:
+            raise ValueError(f"roi_subset {roi_subset} needs the part models {missing}, which were not given")
+        task_models = [m for m in task_models if m[0] in selected]
+    crop_mask = rough_crop_mask(ctx, data, affine, rough_models, roi_subset, rough_resample, max_batch=max_batch, precision=precision)
+    if info_out is not None:
+        info_out["crop_mask"], info_out["task_ids"] = crop_mask, []
+    if crop_mask.sum() == 0:                                      # TS/nnunet.py:428-446: nothing to segment
+        return np.zeros(crop_mask.shape, dtype=np.uint8)
+    t = SegmentationTask(ctx, "total", task_models, resample=resample, multimodel=multimodel, max_batch=max_batch, precision=precision)
+    try:
+        if info_out is not None:
+            info_out["task_ids"] = [p[0] for p in t.parts]
+        return t.predict_image(data, affine, force_split=force_split, crop_mask=crop_mask, crop_addon=[20, 20, 20],
+                               remove_small_blobs=remove_small_blobs, roi_subset=roi_subset, statistics_out=statistics_out,
+                               model_grid_out=model_grid_out)
+    finally:
+        t.close()
 
 
 def body_crop_mask(ctx: Context, data, affine: np.ndarray, body_models, max_batch: int = 16, precision: Optional[str] = None) -> np.ndarray:

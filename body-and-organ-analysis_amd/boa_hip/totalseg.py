@@ -12,7 +12,7 @@ import numpy as np
 
 from .device import Context
 from .plans import ModelConfig
-from .task import SegmentationTask, nonzero_bbox  # noqa: F401  (nonzero_bbox re-exported)
+from .task import SegmentationTask, nonzero_bbox, rough_crop_mask  # noqa: F401  (nonzero_bbox re-exported)
 
 TOTAL_TASK = {"task_id": [291, 292, 293, 294, 295], "resample": 1.5, "trainer": "nnUNetTrainerNoMirroring",
               "model": "3d_fullres", "folds": [0], "step_size": 0.8}          # TS/python_api.py:183-189
@@ -31,8 +31,43 @@ class TotalSegmentatorHip(SegmentationTask):
             for _, _, p, _ in self.parts:
                 p.tile_step_size = float(step_size)
 
-    def predict(self, ct_xyz: np.ndarray, spacing_xyz=(1.5, 1.5, 1.5), affine=None, force_split: bool = False) -> np.ndarray:
-        """(x,y,z) CT in RAS+ order with `spacing_xyz` (or any axis order with an explicit `affine`)."""
+    def predict(self, ct_xyz: np.ndarray, spacing_xyz=(1.5, 1.5, 1.5), affine=None, force_split: bool = False,
+                roi_subset=None, roi_subset_robust=None, rough_models=None, remove_small_blobs: bool = False,
+                statistics: bool = False, statistics_exclude_masks_at_border: bool = True, stats_aggregation: str = "mean",
+                statistics_normalized_intensities: bool = False):
+        """(x,y,z) CT in RAS+ order with `spacing_xyz` (or any axis order with an explicit `affine`) -> the `total` label volume.
+
+        The TotalSegmentator keywords of `compute_all_models` (TS/python_api.py:636-664,778-796):
+        `roi_subset` / `roi_subset_robust` (a list of structure names): `rough_models` -- the single rough `total` model, Dataset298
+        at 6 mm, for `roi_subset_robust` Dataset297 at 3 mm, as `model_store.load_task_models` gives it -- makes the crop mask, only
+        the parts that hold the names run on the crop (+ 20 mm), only their labels are kept; `statistics`: returns
+        (labels, get_basic_statistics dict of the labels and the CT on the input grid) instead of the labels."""
+        from . import label_maps, orientation
         if affine is None:
             affine = np.diag([float(spacing_xyz[0]), float(spacing_xyz[1]), float(spacing_xyz[2]), 1.0])
-        return self.predict_image(ct_xyz, affine, force_split=force_split)
+        robust = roi_subset_robust is not None
+        if robust:
+            roi_subset = roi_subset_robust
+        if roi_subset is None:
+            seg = self.predict_image(ct_xyz, affine, force_split=force_split, remove_small_blobs=remove_small_blobs)
+        else:
+            if type(roi_subset) is not list:
+                raise ValueError("roi_subset must be a list of strings")
+            if rough_models is None:
+                raise ValueError("roi_subset needs the rough `total` model: rough_models=model_store.load_task_models('total_6mm')")
+            selected = label_maps.parts_for_roi_subset(roi_subset)
+            crop_mask = rough_crop_mask(self.ctx, ct_xyz, affine, rough_models, roi_subset, 3.0 if robust else 6.0)
+            every_part = self.parts
+            self.parts = [p for p in every_part if p[0] in selected]      # (the others stay loaded, they just do not run)
+            try:
+                seg = self.predict_image(ct_xyz, affine, force_split=force_split, crop_mask=crop_mask, crop_addon=[20, 20, 20],
+                                         remove_small_blobs=remove_small_blobs, roi_subset=roi_subset)
+            finally:
+                self.parts = every_part
+        if not statistics:
+            return seg
+        from . import statistics as st
+        zooms = np.asarray(orientation.zooms_from_affine(np.asarray(affine, dtype=np.float64)), dtype=np.float32)
+        return seg, st.basic_statistics(self.ctx, seg, ct_xyz, zooms, task="total",
+                                        exclude_masks_at_border=statistics_exclude_masks_at_border, roi_subset=roi_subset,
+                                        metric=stats_aggregation, normalized_intensities=statistics_normalized_intensities)

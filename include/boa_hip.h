@@ -393,6 +393,23 @@ int boa_label_hu_histogram(boa_ctx* ctx, const int16_t* dev_ct, const uint8_t* d
 int boa_label_hu_mask(boa_ctx* ctx, const int16_t* dev_ct, const uint8_t* dev_labels, const uint8_t* host_lut,
                       int mode, int hu_lo, int hu_hi, size_t n_voxels, uint8_t* dev_mask_out);
 
+/* get_basic_statistics (TS/statistics.py:76-141: `seg == k`, touches_border, `data.sum()`, np.average per structure, 117 times over
+ * the volume) as one pass over a contiguous uint8 label volume [d0][d1][d2] (d2 fastest) and the CT on the same grid (ct_dtype 1 int16,
+ * 2 int32: the model-grid image needs no conversion copy).  dev_out, BOA_LABEL_STATS_WORDS 64-bit words, is overwritten:
+ *   [0, 256)    uint64 count of every label value (0 included)
+ *   [256, 512)  int64  sum of the CT values under it
+ *   [512, 768)  uint64 non-zero if a voxel of the label has `i < border || i >= dim - border` on any axis -- numpy's `mask[:3]` /
+ *               `mask[-3:]` of touches_border (TS/statistics.py:76-88), also for dims shorter than 2 * border and than border
+ *   [768], [769] int64 min and max of the CT (INT64_MAX, INT64_MIN for an empty volume)
+ * Integer arithmetic throughout: independent of the order of arrival, bitwise reproducible.  Both arrays must be 16-byte aligned.
+ * Does not synchronise. */
+#define BOA_LABEL_STATS_WORDS 770
+int boa_label_basic_stats(boa_ctx* ctx, const void* dev_ct, int ct_dtype, const uint8_t* dev_labels, const int dims[3], int border,
+                          uint64_t* dev_out);
+/* out[i] = host_lut[labels[i]]; `img_data *= np.isin(img_data, subset labels)` of roi_subset (TS/nnunet.py:707-709) is the table with
+ * lut[v] = v for the subset and 0 elsewhere.  In place (out == labels) is allowed. */
+int boa_label_apply_lut(boa_ctx* ctx, const uint8_t* dev_labels, size_t n, const uint8_t host_lut[256], uint8_t* dev_out);
+
 /* ---- the same measurements on CT values held as float64 (`get_fdata()` of a float-valued, scaled or out-of-int16-range CT;
  * the reference computes on whatever array its reader hands over: BOA/compute/measurements.py:257-258, BCA/report/builder.py).
  *
