@@ -154,6 +154,9 @@ _PROTOS = {
     "boa_deflate_bound": (u64, [u64, u64]),
     "boa_deflate_members": (i32, [vp, vp, u64, u64, i32, vp, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]),
     "boa_deflate_members2": (i32, [vp, vp, u64, u64, i32, i32, i32, vp, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]),
+    "boa_label_member_presence": (i32, [vp, vp, u64, u64, C.POINTER(C.c_uint32)]),
+    "boa_deflate_label_pairs": (i32, [vp, vp, u64, u64, i32, i32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), i32, vp, u64, C.POINTER(u64),
+                                      C.POINTER(C.c_uint32)]),
     "boa_inflate_default_chunk": (u64, []),
     "boa_inflate_streams": (i32, [vp, vp, u64, i32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_uint32), u64, vp, u64, ip,
                                   C.POINTER(u64), C.POINTER(C.c_float)]),

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import json
 import logging
+import os
 import pathlib
 from typing import Any, Dict, Iterable, Optional, Union
 
@@ -20,7 +21,7 @@ import numpy as np
 from .. import label_maps, model_store, nifti, orientation, statistics
 from ..device import Context
 from ..pipeline import BcaPipelineHip
-from ..task import SegmentationTask, run_cascade_task, run_roi_subset, run_with_body_crop
+from ..task import SegmentationTask, run_cascade_task, run_roi_subset, run_with_body_crop, write_structure_masks
 from .config import resolve_device
 from .constants import BASE_MODELS
 from .measurements import compute_measurements
@@ -132,8 +133,17 @@ def _segment_one(ctx, name, ct, affine, hdr, folder, fast, recompute, totalsegme
           names, only their labels in the volume and in the header's label table (`task.run_roi_subset`); switches `body_seg` off;
       `statistics` with `statistics_exclude_masks_at_border` (default on), `stats_aggregation` (mean | median) and
           `statistics_normalized_intensities` (TS/python_api.py:636-641,778-796): `statistics.json` next to the label volume, from
-          one device pass (`boa_hip/statistics.py`) -- on the input grid, or with `fast` on the model grid (`statistics_fast`)."""
+          one device pass (`boa_hip/statistics.py`) -- on the input grid, or with `fast` on the model grid (`statistics_fast`);
+      `ml`: an explicit False also writes TotalSegmentator's default output, one binary mask file per class of the task (of
+          `roi_subset`, where given; TS/nnunet.py:732-734,782-802), into the DIRECTORY `<folder>/<name>/`, binarised and deflated on
+          the device from the label volume (`task.write_structure_masks`).  A deviation: the reference puts that directory at
+          `<name>.nii.gz` instead of the label volume, which `compute_measurements` reads.  Not for `body`, whose derived
+          body.nii.gz / skin.nii.gz (TS/nnunet.py:821-827) are not built here."""
     params = totalsegmentator_params or {}
+    split_masks = params.get("ml", True) is False
+    if split_masks and name == "body":
+        raise NotImplementedError("ml=False with task body: the derived masks body.nii.gz and skin.nii.gz (combine_masks, extract_skin; "
+                                  "TS/nnunet.py:821-827) are not implemented; use ml=True")
     small_blobs = bool(params.get("remove_small_blobs", False))
     roi_subset, robust = params.get("roi_subset"), False
     if params.get("roi_subset_robust") is not None:              # TS/python_api.py:655-664
@@ -206,6 +216,8 @@ def _segment_one(ctx, name, ct, affine, hdr, folder, fast, recompute, totalsegme
         statistics.basic_statistics(ctx, seg, ct, np.asarray(hdr.get_zooms()[:3], dtype=np.float32), task=name,
                                     file_out=folder / "statistics.json", **stats_kw)
     nifti.save_volume(target, seg, affine, ctx=ctx, like=hdr, extensions=[(0, nifti.label_xml(names))])
+    if split_masks:                                             # (`names` is already cut down to the roi_subset)
+        write_structure_masks(ctx, seg, affine, names, folder / name, like=hdr, dynamic=os.environ.get(nifti.SAVE_DEVICE_ENV) == "2")
 
 
 def _write_total_measurements(ctx, ct_path, folder, models, cnr_adjustment, recompute):

@@ -472,30 +472,19 @@ def quatern_from_affine(affine: np.ndarray) -> Tuple[Tuple[float, float, float],
     return (float(b), float(c), float(d)), tuple(float(x) for x in A[:3, 3]), qfac
 
 
-def save(path, data: np.ndarray, affine: np.ndarray, like: Optional[NiftiHeader] = None,
-         extensions: Optional[List[Tuple[int, bytes]]] = None, compresslevel: int = 1, threads: Optional[int] = None,
-         form_codes: Optional[Tuple[int, int]] = None, ctx=None, dynamic: bool = False):
-    """Write `data` (file axis order); `.gz` paths are deflated on `threads` cores (default SAVE_THREADS).  With `ctx` (a device
-    Context) the data body of a `.gz` path is deflated on the device instead (device_deflate; same member container, so read_bytes
-    inflates it in parallel as well), from a numpy array after an upload or from a 3-D DevArray without a download; the header and
-    the extensions stay on the CPU path.  `dynamic` (with `ctx`): dynamic Huffman codes, the near distance = the item size.  `like`: header to copy (pixdim units, descrip, q/s-form codes ... as
-    `img_in_orig.header.copy()` keeps them); datatype/bitpix/dim/vox_offset and the affine fields are set from the
-    arguments; scl_slope/inter are reset (label volumes are stored unscaled).  `form_codes`: also store the affine as a qform."""
-    on_device = ctx is not None and str(path).endswith(".gz")
-    if on_device:
-        from .devarray import DevArray
-    if not (on_device and isinstance(data, DevArray)):   # (a DevArray is taken as it is)
-        data = np.asarray(data)
-    ndim = len(data.shape)
-    if data.dtype not in _DT_INV:
-        raise TypeError(f"unsupported dtype {data.dtype}")
+def _file_head(shape, dtype, affine, like, extensions, form_codes) -> bytes:
+    """The bytes in front of the data body of `save`: the 348-byte header, the extender and the extensions."""
+    dtype = np.dtype(dtype)
+    ndim = len(shape)
+    if dtype not in _DT_INV:
+        raise TypeError(f"unsupported dtype {dtype}")
     affine = np.asarray(affine, dtype=np.float64)
     v = list(struct.unpack(_HDR, like.raw)) if like is not None else list(struct.unpack(_HDR, b"\0" * 348))
     v[0] = 348
-    dim = [ndim] + list(data.shape) + [1] * (7 - ndim)
+    dim = [ndim] + list(shape) + [1] * (7 - ndim)
     v[7:15] = dim
-    v[19] = _DT_INV[data.dtype]
-    v[20] = data.dtype.itemsize * 8
+    v[19] = _DT_INV[dtype]
+    v[20] = dtype.itemsize * 8
     zooms = np.sqrt(np.sum(affine[:3, :3] ** 2, axis=0))
     if like is None:
         v[22:30] = [1.0, float(zooms[0]), float(zooms[1]), float(zooms[2]), 1.0, 1.0, 1.0, 1.0]
@@ -520,7 +509,24 @@ def save(path, data: np.ndarray, affine: np.ndarray, like: Optional[NiftiHeader]
     v[30] = float(352 + len(ext_blob))
     v[-1] = b"n+1\0"
     hdr = struct.pack(_HDR, *v)
-    head = hdr + bytes([1 if exts else 0, 0, 0, 0]) + ext_blob
+    return hdr + bytes([1 if exts else 0, 0, 0, 0]) + ext_blob
+
+
+def save(path, data: np.ndarray, affine: np.ndarray, like: Optional[NiftiHeader] = None,
+         extensions: Optional[List[Tuple[int, bytes]]] = None, compresslevel: int = 1, threads: Optional[int] = None,
+         form_codes: Optional[Tuple[int, int]] = None, ctx=None, dynamic: bool = False):
+    """Write `data` (file axis order); `.gz` paths are deflated on `threads` cores (default SAVE_THREADS).  With `ctx` (a device
+    Context) the data body of a `.gz` path is deflated on the device instead (device_deflate; same member container, so read_bytes
+    inflates it in parallel as well), from a numpy array after an upload or from a 3-D DevArray without a download; the header and
+    the extensions stay on the CPU path.  `dynamic` (with `ctx`): dynamic Huffman codes, the near distance = the item size.  `like`: header to copy (pixdim units, descrip, q/s-form codes ... as
+    `img_in_orig.header.copy()` keeps them); datatype/bitpix/dim/vox_offset and the affine fields are set from the
+    arguments; scl_slope/inter are reset (label volumes are stored unscaled).  `form_codes`: also store the affine as a qform."""
+    on_device = ctx is not None and str(path).endswith(".gz")
+    if on_device:
+        from .devarray import DevArray
+    if not (on_device and isinstance(data, DevArray)):   # (a DevArray is taken as it is)
+        data = np.asarray(data)
+    head = _file_head(data.shape, data.dtype, affine, like, extensions, form_codes)
     if on_device:
         buf, addr, nbytes, row = _device_body(ctx, data)
         try:
@@ -543,3 +549,129 @@ def save(path, data: np.ndarray, affine: np.ndarray, like: Optional[NiftiHeader]
         else:
             f.write(head)
             f.write(body.tobytes())
+
+
+def label_member_presence(ctx, src, n: int, member_bytes: int = 0) -> np.ndarray:
+    """bool [members][256]: label k occurs in member m of the `n` label bytes on the device at `src` (a c_void_p / address),
+    from one pass of `boa_label_member_presence` (csrc/label_masks.hip).  Members as in device_deflate."""
+    import ctypes as C
+    from . import _lib
+    member_bytes = int(member_bytes) or _GZ_BLOCK
+    n = int(n)
+    n_mem = max(1, -(-n // member_bytes))
+    bits = np.zeros((n_mem, 8), dtype="<u4")
+    src = src if isinstance(src, C.c_void_p) else C.c_void_p(src)
+    _lib.check(ctx.lib.boa_label_member_presence(ctx.h, src, n, member_bytes, bits.ctypes.data_as(C.POINTER(C.c_uint32))),
+               "boa_label_member_presence")
+    return np.unpackbits(bits.view(np.uint8), axis=1, bitorder="little").astype(bool)
+
+
+def pair_capacity(ctx, n: int, member_bytes: int, pair_members) -> int:
+    """The output bytes `boa_deflate_label_pairs` asks for: every listed member stored (5 bytes per 16 KiB block, at least one)."""
+    total = 0
+    for m in pair_members:
+        length = max(0, min(member_bytes, n - int(m) * member_bytes))
+        total += int(ctx.lib.boa_deflate_bound(length, max(length, 1)))
+    return total
+
+
+def device_deflate_label_pairs(ctx, src, n: int, pairs, row_bytes: int = 0, member_bytes: int = 0, *, dynamic: bool = False, info=None):
+    """The members of binary masks of the `n` label bytes on the device at `src`, without the masks: `pairs` = [(label, member)]
+    -> [(body, crc32, size)] of the payload (labels == label) over that member, what device_deflate gives for it on the mask
+    (`boa_deflate_label_pairs`, csrc/deflate.hip).  `info` (a dict): seconds spent in "encode" and "download" are added to it."""
+    import ctypes as C
+    import time
+    from . import _lib
+    member_bytes = int(member_bytes) or _GZ_BLOCK
+    n, pairs = int(n), list(pairs)
+    n_mem = max(1, -(-n // member_bytes))
+    if not pairs:
+        return []
+    if any(not (0 <= int(k) <= 255 and 0 <= int(m) < n_mem) for k, m in pairs):
+        raise ValueError(f"device_deflate_label_pairs: a pair outside labels 0 .. 255 x members 0 .. {n_mem - 1}")
+    lab = (C.c_uint8 * len(pairs))(*[int(k) for k, _ in pairs])
+    mem = (C.c_uint32 * len(pairs))(*[int(m) for _, m in pairs])
+    cap = pair_capacity(ctx, n, member_bytes, (m for _, m in pairs))
+    offs, crcs = (C.c_size_t * (len(pairs) + 1))(), (C.c_uint32 * len(pairs))()
+    out = ctx.alloc(max(cap, 1))
+    try:
+        src = src if isinstance(src, C.c_void_p) else C.c_void_p(src)
+        t0 = time.perf_counter()
+        _lib.check(ctx.lib.boa_deflate_label_pairs(ctx.h, src, n, member_bytes, int(row_bytes), _lib.BOA_DEFLATE_DYNAMIC if dynamic else 0,
+                                                   lab, mem, len(pairs), out.vp, cap, offs, crcs), "boa_deflate_label_pairs")
+        t1 = time.perf_counter()
+        comp = memoryview(out.download((int(offs[len(pairs)]),), np.uint8)) if offs[len(pairs)] else memoryview(b"")
+        t2 = time.perf_counter()
+    finally:
+        out.free()
+    if info is not None:
+        info["encode"] = info.get("encode", 0.0) + t1 - t0
+        info["download"] = info.get("download", 0.0) + t2 - t1
+    return [(comp[offs[p]:offs[p + 1]], int(crcs[p]), max(0, min(member_bytes, n - int(m) * member_bytes))) for p, (_, m) in enumerate(pairs)]
+
+
+def save_label_masks(folder, labels, affine, names: Dict[int, str], ctx, like: Optional[NiftiHeader] = None, dynamic: bool = False,
+                     group_bytes: int = 1 << 30, info=None):
+    """`<folder>/<name>.nii.gz` for every (k, name) of `names`: the uint8 mask (labels == k), each file byte for byte what
+    `save(path, mask, affine, like=like, ctx=ctx, dynamic=dynamic)` writes -- TotalSegmentator's one-file-per-structure output
+    (TS/nnunet.py:782-802) -- without a mask ever being made: `labels` (a uint8 DevArray or numpy volume, file axis order) is put
+    on the device as `_device_body` does, one pass finds the (label, member) pairs that hold a voxel (label_member_presence), only
+    those are encoded (device_deflate_label_pairs, in groups of at most `group_bytes` of payload, which bounds the workspace), and
+    every other pair is the all-zero member, encoded once per member length.  A structure without a voxel gets an all-zero file, as
+    the reference writes.  `info` (a dict) receives "pairs", "present", "compressed_bytes" and the seconds of "presence", "encode",
+    "download" and "write"."""
+    import io
+    import time
+    from .devarray import DevArray
+    if not isinstance(labels, DevArray):
+        labels = np.asarray(labels)
+    if np.dtype(labels.dtype) != np.uint8 or len(labels.shape) != 3:
+        raise TypeError(f"save_label_masks: a 3-D uint8 label volume is required, got {labels.dtype} {tuple(labels.shape)}")
+    names = {int(k): str(v) for k, v in names.items()}
+    if any(not 0 <= k <= 255 for k in names):
+        raise ValueError("save_label_masks: label ids must be 0 .. 255")
+    group_bytes = int(group_bytes)
+    if group_bytes < 1:
+        raise ValueError(f"save_label_masks: group_bytes {group_bytes}")
+    folder = os.fspath(folder)
+    stats = info if info is not None else {}
+    head_gz = io.BytesIO()
+    write_gzip_members(head_gz, _file_head(tuple(labels.shape), np.uint8, affine, like, None, None), 1, 1)
+    mb = _GZ_BLOCK
+    buf, addr, n, row = _device_body(ctx, labels)
+    try:
+        n_mem = max(1, -(-n // mb))
+        length = [max(0, min(mb, n - m * mb)) for m in range(n_mem)]
+        t0 = time.perf_counter()
+        present = label_member_presence(ctx, addr, n, mb)
+        stats["presence"] = time.perf_counter() - t0
+        todo = [(k, m) for k in names for m in range(n_mem) if present[m, k]]
+        members = {}
+        lo = 0
+        while lo < len(todo):                                  # groups of whole pairs, at least one
+            hi, total = lo + 1, length[todo[lo][1]]
+            while hi < len(todo) and total + length[todo[hi][1]] <= group_bytes:
+                total += length[todo[hi][1]]
+                hi += 1
+            for pair, (body, crc, size) in zip(todo[lo:hi], device_deflate_label_pairs(ctx, addr, n, todo[lo:hi], row, mb, dynamic=dynamic, info=stats)):
+                members[pair] = (bytes(body), crc, size)
+            lo = hi
+        zero = {}                                              # the all-zero member of every member length that an absent pair has
+        for size in sorted({length[m] for k in names for m in range(n_mem) if not present[m, k]}):
+            z = ctx.zeros(max(size, 1))
+            try:
+                (body, crc, _), = device_deflate(ctx, z.ptr, size, row, max(size, 1), dynamic=dynamic)
+                zero[size] = (bytes(body), crc, size)
+            finally:
+                z.free()
+    finally:
+        if buf is not None:
+            buf.free()
+    t0 = time.perf_counter()
+    written = 0
+    for k, name in names.items():
+        with open(os.path.join(folder, f"{name}.nii.gz"), "wb") as f:
+            f.write(head_gz.getbuffer())
+            write_wrapped_members(f, (members.get((k, m)) or zero[length[m]] for m in range(n_mem)))
+            written += f.tell()
+    stats.update(write=time.perf_counter() - t0, pairs=len(names) * n_mem, present=len(todo), compressed_bytes=written)

@@ -530,6 +530,22 @@ def write_probabilities(path, probabilities: np.ndarray, properties: dict) -> No
         pickle.dump(dict(properties), f)
 
 
+def write_structure_masks(ctx: Context, seg, affine: np.ndarray, names: Dict[int, str], folder, like=None,
+                          roi_subset: Optional[Sequence[str]] = None, dynamic: bool = False) -> List[str]:
+    """The `ml=False` output of nnUNet_predict_image (TS/nnunet.py:782-802): `<folder>/<name>.nii.gz` = uint8 (seg == k) for every
+    class (k, name) of the task's class map `names`, or with `roi_subset` only for the names it lists (:732-734); the header is a
+    copy of `like` with the data type set to uint8.  `seg`: the task's uint8 label volume on the input grid, numpy or a DevArray.
+    The masks are binarised and deflated on the device from the label volume (`nifti.save_label_masks`).  -> the names written."""
+    import os
+    from . import nifti
+    selected = dict(names)
+    if roi_subset is not None:
+        selected = {k: v for k, v in selected.items() if v in roi_subset}
+    os.makedirs(os.fspath(folder), exist_ok=True)
+    nifti.save_label_masks(folder, seg, affine, selected, ctx, like=like, dynamic=dynamic)
+    return list(selected.values())
+
+
 def remove_outside_of_mask(ctx: Context, seg: np.ndarray, mask: np.ndarray, addon: int = 1) -> np.ndarray:
     """TS/postprocessing.py:101-131 on arrays of the same grid: dilate `mask != 0` `addon` times with the 6-neighbour cross
     (scipy.ndimage.binary_dilation(mask, iterations=addon)), clear `seg` outside.  Runs on the device."""

@@ -8,6 +8,8 @@
 //   k_deflate_compact  slots -> one contiguous body per member
 // Every block ends on a byte boundary (an empty stored block after a non-final fixed block, as pigz does), so bodies concatenate
 // by byte copy.  A match never reaches before its member's first byte nor past its block's last, so a member inflates alone.
+// boa_deflate_label_pairs runs the same three kernels over a list of (label, member) pairs of a label volume: a pair takes the
+// place of the member, and k_deflate_block<., true> fills LDS with (byte == label) instead of the byte, so the mask exists in LDS only.
 #include <algorithm>
 
 #include "common.h"
@@ -35,6 +37,22 @@ constexpr int OFF_MISC = OFF_LEAD + 2 * DFL_NT;                // uint32 [32]
 constexpr int OFF_DATA = OFF_MISC + 128;                       // uint8 [hist + DFL_BLK + 16]: history, then the block
 static_assert(OFF_DATA % 16 == 0 && OFF_TOK % 16 == 0 && OFF_MARK % 16 == 0, "LDS carve alignment");
 static_assert(OFF_DATA >= DFL_MAXROW + 16, "a row candidate of an early piece reads below s_d, inside the carve");
+
+// What a launch encodes: every member of the payload in file order (first == nullptr), or a list of pairs.  Pair p is member
+// member[p] of the mask (payload == label[p]); its blocks are [first[p], first[p + 1]) of the grid.
+struct DflPairs {
+    const unsigned* first;           // [n + 1]
+    const unsigned* member;          // [n]
+    const unsigned char* label;      // [n]
+    unsigned n;
+};
+
+// four bytes of w -> 1 where the byte equals the label (lab4 = the label in every byte), else 0
+__device__ __forceinline__ unsigned eq_label4(unsigned w, unsigned lab4) {
+    const unsigned x = w ^ lab4;
+    const unsigned nz = ((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x;      // bit 7 of a byte = that byte of x is not zero
+    return (~nz >> 7) & 0x01010101u;
+}
 
 // bit k = (block byte p0 + k equals the byte `d` before it); 16 positions.  Reads LDS words only; the caller masks what is invalid.
 __device__ __forceinline__ unsigned eq_mask16(const unsigned char* s_d, int a, const uint4 own) {
@@ -190,10 +208,12 @@ __device__ __forceinline__ void for_each_token(unsigned starts, int p0, const un
 
 // grid = blocks of all members in file order; dynamic LDS = OFF_DATA + hist + DFL_BLK + 16.  DYN: also try a dynamic-Huffman block
 // (BTYPE = 10) and take it where it is smaller than both other forms; near = the short candidate distance (1 without DYN).
-template <bool DYN>
+// PAIRS: grid = the blocks of the pairs of `pr` in list order; the payload of a pair's block is (src byte == label) ? 1 : 0.
+template <bool DYN, bool PAIRS>
 __global__ __launch_bounds__(DFL_NT) void k_deflate_block(const unsigned char* __restrict__ src, size_t n, unsigned member_bytes,
                                                           unsigned bpm, int row, int hist, int near_arg, const unsigned* __restrict__ pw,
-                                                          unsigned* __restrict__ ws, unsigned* __restrict__ blk_size, unsigned* __restrict__ blk_crc) {
+                                                          unsigned* __restrict__ ws, unsigned* __restrict__ blk_size, unsigned* __restrict__ blk_crc,
+                                                          const DflPairs pr) {
     const int near = DYN ? near_arg : 1;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned short* s_next = (unsigned short*)(smem + OFF_NEXT);
@@ -207,8 +227,22 @@ __global__ __launch_bounds__(DFL_NT) void k_deflate_block(const unsigned char* _
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const size_t g = blockIdx.x;
-    const size_t moff = (g / bpm) * (size_t)member_bytes;
-    const unsigned boff = (unsigned)(g % bpm) * DFL_BLK;                              // block start inside its member
+    size_t moff;
+    unsigned boff;                                                                    // block start inside its member
+    unsigned lab4 = 0;
+    if constexpr (PAIRS) {
+        unsigned lo = 0, hi = pr.n;                                                   // the last pair whose first block is not after g
+        while (hi - lo > 1) {
+            const unsigned mid = (lo + hi) >> 1;
+            if (pr.first[mid] <= g) lo = mid; else hi = mid;
+        }
+        moff = pr.member[lo] * (size_t)member_bytes;
+        boff = ((unsigned)g - pr.first[lo]) * DFL_BLK;
+        lab4 = pr.label[lo] * 0x01010101u;
+    } else {
+        moff = (g / bpm) * (size_t)member_bytes;
+        boff = (unsigned)(g % bpm) * DFL_BLK;
+    }
     const size_t mlen = n - moff < member_bytes ? n - moff : member_bytes;            // 0 only for the empty payload
     const int blen = (int)(mlen - boff < (size_t)DFL_BLK ? mlen - boff : DFL_BLK);
     const bool bfinal = boff + (size_t)blen == mlen;
@@ -221,8 +255,17 @@ __global__ __launch_bounds__(DFL_NT) void k_deflate_block(const unsigned char* _
         unsigned char* ldst = s_d + H - avail;
         const int total = avail + blen;
         const int n16 = ((uintptr_t)gsrc & 15) == 0 ? total >> 4 : 0;
-        for (int i = t; i < n16; i += DFL_NT) ((uint4*)ldst)[i] = ((const uint4*)gsrc)[i];
-        for (int i = n16 * 16 + t; i < total; i += DFL_NT) ldst[i] = gsrc[i];
+        if constexpr (PAIRS) {
+            // the mask is made here and nowhere else: history, CRC, matches and the stored form all read LDS
+            for (int i = t; i < n16; i += DFL_NT) {
+                const uint4 v = ((const uint4*)gsrc)[i];
+                ((uint4*)ldst)[i] = make_uint4(eq_label4(v.x, lab4), eq_label4(v.y, lab4), eq_label4(v.z, lab4), eq_label4(v.w, lab4));
+            }
+            for (int i = n16 * 16 + t; i < total; i += DFL_NT) ldst[i] = gsrc[i] == (lab4 & 0xffu) ? 1 : 0;
+        } else {
+            for (int i = t; i < n16; i += DFL_NT) ((uint4*)ldst)[i] = ((const uint4*)gsrc)[i];
+            for (int i = n16 * 16 + t; i < total; i += DFL_NT) ldst[i] = gsrc[i];
+        }
     }
     if (t < 256) s_tab[t] = crc32_table_entry((unsigned)t);
     for (int i = t; i < DFL_BLK / 32 + 4; i += DFL_NT) s_mark[i] = (i == 0 && blen > 0) ? 1u : 0u;
@@ -579,11 +622,13 @@ __global__ __launch_bounds__(DFL_NT) void k_deflate_block(const unsigned char* _
     if (t == 0) blk_size[g] = out_bytes;
 }
 
-// one workgroup: exclusive scan of the block sizes (members are consecutive runs of blocks), then one thread per member
+// one workgroup: exclusive scan of the block sizes (members are consecutive runs of blocks), then one thread per member -- or per
+// pair of `pr` (nmem = pr.n), which has the payload length of its member and its own run of blocks
 __global__ __launch_bounds__(DFL_NT) void k_deflate_scan(const unsigned* __restrict__ blk_size, const unsigned* __restrict__ blk_crc,
                                                          unsigned nblocks, unsigned bpm, unsigned nmem, size_t n, unsigned member_bytes,
                                                          const unsigned* __restrict__ pw, unsigned long long* __restrict__ blk_off,
-                                                         unsigned long long* __restrict__ mem_off, unsigned* __restrict__ mem_crc) {
+                                                         unsigned long long* __restrict__ mem_off, unsigned* __restrict__ mem_crc,
+                                                         const DflPairs pr) {
     __shared__ unsigned long long s_wave[DFL_NT / 64];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     unsigned long long carry = 0;
@@ -610,10 +655,10 @@ __global__ __launch_bounds__(DFL_NT) void k_deflate_scan(const unsigned* __restr
     __threadfence_block();
     __syncthreads();
     for (unsigned m = t; m < nmem; m += DFL_NT) {
-        const size_t moff = (size_t)m * member_bytes;
+        const size_t moff = (size_t)(pr.first ? pr.member[m] : m) * member_bytes;
         const size_t mlen = n - moff < member_bytes ? n - moff : member_bytes;
-        const unsigned first = m * bpm;
-        const unsigned nb = m + 1 < nmem ? bpm : nblocks - first;
+        const unsigned first = pr.first ? pr.first[m] : m * bpm;
+        const unsigned nb = pr.first ? pr.first[m + 1] - first : m + 1 < nmem ? bpm : nblocks - first;
         unsigned c = 0;
         for (unsigned k = 0; k < nb; ++k) {
             const size_t left = mlen - (size_t)k * DFL_BLK;
@@ -664,6 +709,77 @@ void deflate_shape(size_t n, size_t member_bytes, size_t* nmem, size_t* bpm, siz
 constexpr size_t DFL_MAX_N = (size_t)1 << 40;
 constexpr size_t DFL_MAX_MEMBER = (size_t)1 << 30;
 
+// The three kernels over `nblocks` blocks of `nmem` members -- or pairs, where pair_first (host, nmem + 1: the first block of every
+// pair), pair_member and pair_label (host, nmem) are given -- and the download of the offset and CRC tables.  Arguments are checked.
+int deflate_run(boa_ctx* c, const uint8_t* dev_src, size_t n, size_t member_bytes, size_t nmem, size_t bpm, size_t nblocks, int row_bytes,
+                int near_bytes, bool dyn, const unsigned* pair_first, const uint32_t* pair_member, const uint8_t* pair_label,
+                uint8_t* dev_out, size_t* host_offsets, uint32_t* host_crc32) {
+    const bool pairs = pair_first != nullptr;
+    const int row = (row_bytes >= 1 && row_bytes <= DFL_MAXROW) ? row_bytes : 0;      // anything else: no row candidate
+    const int hist = std::max(16, (row + 15) & ~15);
+    const size_t lds = (size_t)OFF_DATA + hist + DFL_BLK + 16;
+
+    // workspace: [slots][block offsets u64][member offsets u64][block sizes][block CRCs][member CRCs][x^(8 2^k) table]
+    //            [first block of every pair][member of every pair][label of every pair]
+    const size_t slots_b = nblocks * (size_t)DFL_SLOT;
+    const size_t boff_b = nblocks * 8, moff_b = (nmem + 1) * 8, bsz_b = nblocks * 4, bcrc_b = nblocks * 4, mcrc_b = nmem * 4;
+    const size_t pfirst_b = pairs ? (nmem + 1) * 4 : 0, pmem_b = pairs ? nmem * 4 : 0, plab_b = pairs ? nmem : 0;
+    const size_t fixed_b = slots_b + boff_b + moff_b + bsz_b + bcrc_b + mcrc_b + sizeof(DflCrcPow);
+    unsigned char* blk = nullptr;
+    BOA_TRY(boa_malloc(c, fixed_b + pfirst_b + pmem_b + plab_b, (void**)&blk));
+    unsigned* d_slots = (unsigned*)blk;
+    unsigned long long* d_boff = (unsigned long long*)(blk + slots_b);
+    unsigned long long* d_moff = (unsigned long long*)(blk + slots_b + boff_b);
+    unsigned* d_bsz = (unsigned*)(blk + slots_b + boff_b + moff_b);
+    unsigned* d_bcrc = (unsigned*)(blk + slots_b + boff_b + moff_b + bsz_b);
+    unsigned* d_mcrc = (unsigned*)(blk + slots_b + boff_b + moff_b + bsz_b + bcrc_b);
+    unsigned* d_pw = (unsigned*)(blk + slots_b + boff_b + moff_b + bsz_b + bcrc_b + mcrc_b);
+    DflPairs pr = {nullptr, nullptr, nullptr, 0};
+    if (pairs) pr = {(const unsigned*)(blk + fixed_b), (const unsigned*)(blk + fixed_b + pfirst_b), blk + fixed_b + pfirst_b + pmem_b, (unsigned)nmem};
+
+    static bool once = (hipFuncSetAttribute((const void*)k_deflate_block<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
+                        hipFuncSetAttribute((const void*)k_deflate_block<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
+                        hipFuncSetAttribute((const void*)k_deflate_block<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
+                        hipFuncSetAttribute((const void*)k_deflate_block<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), true);
+    (void)once;
+    std::vector<unsigned long long> offs(nmem + 1);
+    hipError_t e = hipMemcpyAsync(d_pw, crc_pow().x, sizeof(DflCrcPow), hipMemcpyHostToDevice, c->stream);
+    if (pairs) {
+        if (e == hipSuccess) e = hipMemcpyAsync((void*)pr.first, pair_first, pfirst_b, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync((void*)pr.member, pair_member, pmem_b, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync((void*)pr.label, pair_label, plab_b, hipMemcpyHostToDevice, c->stream);
+    }
+    if (e != hipSuccess) {
+        hipStreamSynchronize(c->stream);
+        boa_free(c, blk);
+        BOA_HIP_TRY(e);
+    }
+    c->prof_break = true;
+    KernelTimer t(c, BOA_K_OTHER, 0, (double)(pairs ? nblocks * (size_t)DFL_BLK : n) * 2 + (double)nblocks * 16);
+    const dim3 grid((unsigned)nblocks), wg(DFL_NT);
+    const unsigned mb = (unsigned)member_bytes, ubpm = (unsigned)bpm;
+    if (pairs && dyn)
+        hipLaunchKernelGGL((k_deflate_block<true, true>), grid, wg, lds, c->stream, dev_src, n, mb, ubpm, row, hist, near_bytes, d_pw, d_slots, d_bsz, d_bcrc, pr);
+    else if (pairs)
+        hipLaunchKernelGGL((k_deflate_block<false, true>), grid, wg, lds, c->stream, dev_src, n, mb, ubpm, row, hist, near_bytes, d_pw, d_slots, d_bsz, d_bcrc, pr);
+    else if (dyn)
+        hipLaunchKernelGGL((k_deflate_block<true, false>), grid, wg, lds, c->stream, dev_src, n, mb, ubpm, row, hist, near_bytes, d_pw, d_slots, d_bsz, d_bcrc, pr);
+    else
+        hipLaunchKernelGGL((k_deflate_block<false, false>), grid, wg, lds, c->stream, dev_src, n, mb, ubpm, row, hist, near_bytes, d_pw, d_slots, d_bsz, d_bcrc, pr);
+    hipLaunchKernelGGL(k_deflate_scan, dim3(1), dim3(DFL_NT), 0, c->stream, d_bsz, d_bcrc, (unsigned)nblocks, ubpm, (unsigned)nmem, n, mb, d_pw,
+                       d_boff, d_moff, d_mcrc, pr);
+    hipLaunchKernelGGL(k_deflate_compact, grid, dim3(256), 0, c->stream, d_slots, d_bsz, d_boff, dev_out);
+    t.stop();
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(offs.data(), d_moff, moff_b, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(host_crc32, d_mcrc, mcrc_b, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    boa_free(c, blk);
+    BOA_HIP_TRY(e);
+    for (size_t m = 0; m <= nmem; ++m) host_offsets[m] = (size_t)offs[m];
+    return BOA_OK;
+}
+
 }  // namespace
 
 extern "C" size_t boa_deflate_bound(size_t n, size_t member_bytes) {
@@ -687,55 +803,45 @@ extern "C" int boa_deflate_members2(boa_ctx* c, const uint8_t* dev_src, size_t n
     BOA_REQUIRE(nblocks <= 0x7fffffffu && nmem <= 0x7fffffffu, "boa_deflate_members: %zu blocks in %zu members", nblocks, nmem);
     const size_t bound = n + 5 * nblocks;
     BOA_REQUIRE(out_capacity >= bound, "boa_deflate_members: out_capacity %zu below boa_deflate_bound = %zu", out_capacity, bound);
-    const int row = (row_bytes >= 1 && row_bytes <= DFL_MAXROW) ? row_bytes : 0;      // anything else: no row candidate
-    const int hist = std::max(16, (row + 15) & ~15);
-    const size_t lds = (size_t)OFF_DATA + hist + DFL_BLK + 16;
-
-    // workspace: [slots][block offsets u64][member offsets u64][block sizes][block CRCs][member CRCs][x^(8 2^k) table]
-    const size_t slots_b = nblocks * (size_t)DFL_SLOT;
-    const size_t boff_b = nblocks * 8, moff_b = (nmem + 1) * 8, bsz_b = nblocks * 4, bcrc_b = nblocks * 4, mcrc_b = nmem * 4;
-    unsigned char* blk = nullptr;
-    BOA_TRY(boa_malloc(c, slots_b + boff_b + moff_b + bsz_b + bcrc_b + mcrc_b + sizeof(DflCrcPow), (void**)&blk));
-    unsigned* d_slots = (unsigned*)blk;
-    unsigned long long* d_boff = (unsigned long long*)(blk + slots_b);
-    unsigned long long* d_moff = (unsigned long long*)(blk + slots_b + boff_b);
-    unsigned* d_bsz = (unsigned*)(blk + slots_b + boff_b + moff_b);
-    unsigned* d_bcrc = (unsigned*)(blk + slots_b + boff_b + moff_b + bsz_b);
-    unsigned* d_mcrc = (unsigned*)(blk + slots_b + boff_b + moff_b + bsz_b + bcrc_b);
-    unsigned* d_pw = (unsigned*)(blk + slots_b + boff_b + moff_b + bsz_b + bcrc_b + mcrc_b);
-
-    static bool once = (hipFuncSetAttribute((const void*)k_deflate_block<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-                        hipFuncSetAttribute((const void*)k_deflate_block<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), true);
-    (void)once;
-    std::vector<unsigned long long> offs(nmem + 1);
-    hipError_t e = hipMemcpyAsync(d_pw, crc_pow().x, sizeof(DflCrcPow), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) {
-        boa_free(c, blk);
-        BOA_HIP_TRY(e);
-    }
-    c->prof_break = true;
-    KernelTimer t(c, BOA_K_OTHER, 0, (double)n * 2 + (double)nblocks * 16);
-    if (dyn)
-        hipLaunchKernelGGL(k_deflate_block<true>, dim3((unsigned)nblocks), dim3(DFL_NT), lds, c->stream, dev_src, n, (unsigned)member_bytes,
-                           (unsigned)bpm, row, hist, near_bytes, d_pw, d_slots, d_bsz, d_bcrc);
-    else
-        hipLaunchKernelGGL(k_deflate_block<false>, dim3((unsigned)nblocks), dim3(DFL_NT), lds, c->stream, dev_src, n, (unsigned)member_bytes,
-                           (unsigned)bpm, row, hist, near_bytes, d_pw, d_slots, d_bsz, d_bcrc);
-    hipLaunchKernelGGL(k_deflate_scan, dim3(1), dim3(DFL_NT), 0, c->stream, d_bsz, d_bcrc, (unsigned)nblocks, (unsigned)bpm,
-                       (unsigned)nmem, n, (unsigned)member_bytes, d_pw, d_boff, d_moff, d_mcrc);
-    hipLaunchKernelGGL(k_deflate_compact, dim3((unsigned)nblocks), dim3(256), 0, c->stream, d_slots, d_bsz, d_boff, dev_out);
-    t.stop();
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(offs.data(), d_moff, moff_b, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(host_crc32, d_mcrc, mcrc_b, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    boa_free(c, blk);
-    BOA_HIP_TRY(e);
-    for (size_t m = 0; m <= nmem; ++m) host_offsets[m] = (size_t)offs[m];
-    return BOA_OK;
+    return deflate_run(c, dev_src, n, member_bytes, nmem, bpm, nblocks, row_bytes, near_bytes, dyn, nullptr, nullptr, nullptr, dev_out, host_offsets,
+                       host_crc32);
 }
 
 extern "C" int boa_deflate_members(boa_ctx* c, const uint8_t* dev_src, size_t n, size_t member_bytes, int row_bytes, uint8_t* dev_out,
                                    size_t out_capacity, size_t* host_offsets, uint32_t* host_crc32) {
     return boa_deflate_members2(c, dev_src, n, member_bytes, row_bytes, 1, 0, dev_out, out_capacity, host_offsets, host_crc32);
+}
+
+extern "C" int boa_deflate_label_pairs(boa_ctx* c, const uint8_t* dev_labels, size_t n, size_t member_bytes, int row_bytes, int flags,
+                                       const uint8_t* host_pair_label, const uint32_t* host_pair_member, int n_pairs, uint8_t* dev_out,
+                                       size_t out_capacity, size_t* host_offsets, uint32_t* host_crc32) {
+    BOA_REQUIRE(c && host_offsets && (dev_labels || n == 0), "boa_deflate_label_pairs: NULL argument");
+    BOA_REQUIRE(n_pairs >= 0, "boa_deflate_label_pairs: n_pairs %d", n_pairs);
+    BOA_REQUIRE(n_pairs == 0 || (dev_out && host_crc32 && host_pair_label && host_pair_member), "boa_deflate_label_pairs: NULL argument");
+    BOA_REQUIRE(member_bytes >= 1 && member_bytes <= DFL_MAX_MEMBER, "boa_deflate_label_pairs: member_bytes %zu outside [1, 2^30]", member_bytes);
+    BOA_REQUIRE(n <= DFL_MAX_N, "boa_deflate_label_pairs: %zu payload bytes (at most 2^40)", n);
+    BOA_REQUIRE((flags & ~BOA_DEFLATE_DYNAMIC) == 0, "boa_deflate_label_pairs: unknown flags 0x%x", (unsigned)flags);
+    size_t nmem, bpm, all_blocks;
+    deflate_shape(n, member_bytes, &nmem, &bpm, &all_blocks);
+    const size_t last_len = n - (nmem - 1) * member_bytes;                         // (0 only for the empty payload)
+    const size_t last_blocks = std::max<size_t>(1, (last_len + DFL_BLK - 1) / DFL_BLK);
+    std::vector<unsigned> first((size_t)n_pairs + 1);
+    size_t nblocks = 0, bound = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        const size_t m = host_pair_member[p];
+        BOA_REQUIRE(m < nmem, "boa_deflate_label_pairs: pair %d names member %zu of %zu", p, m, nmem);
+        first[p] = (unsigned)nblocks;
+        const size_t nb = m + 1 < nmem ? bpm : last_blocks;
+        nblocks += nb;
+        bound += (m + 1 < nmem ? member_bytes : last_len) + 5 * nb;                // every block stored
+        BOA_REQUIRE(nblocks <= 0x7fffffffu, "boa_deflate_label_pairs: more than 2^31 - 1 blocks in %d pairs", n_pairs);
+    }
+    first[n_pairs] = (unsigned)nblocks;
+    BOA_REQUIRE(out_capacity >= bound, "boa_deflate_label_pairs: out_capacity %zu below the pairs' bound = %zu", out_capacity, bound);
+    if (n_pairs == 0) {
+        host_offsets[0] = 0;
+        return BOA_OK;
+    }
+    return deflate_run(c, dev_labels, n, member_bytes, (size_t)n_pairs, bpm, nblocks, row_bytes, 1, (flags & BOA_DEFLATE_DYNAMIC) != 0, first.data(),
+                       host_pair_member, host_pair_label, dev_out, host_offsets, host_crc32);
 }

@@ -892,6 +892,27 @@ int boa_deflate_members(boa_ctx* ctx, const uint8_t* dev_src, size_t n, size_t m
 int boa_deflate_members2(boa_ctx* ctx, const uint8_t* dev_src, size_t n, size_t member_bytes, int row_bytes, int near_bytes, int flags,
                          uint8_t* dev_out, size_t out_capacity, size_t* host_offsets, uint32_t* host_crc32);
 
+/* ---- per-structure mask files of a label volume (label_masks.hip, deflate.hip) ----
+ * One binary mask file per structure is the payload (labels == k) ? 1 : 0 for every k, cut into the same members.  A structure fills
+ * a small part of the volume, so most (label, member) pairs are all zero: the presence pass finds the others, and only those are
+ * encoded, straight from the label volume -- the mask bytes exist in LDS only.
+ *
+ * boa_label_member_presence: host_bits = n_members rows of 8 words, n_members = max(1, ceil(n / member_bytes)) as above; bit k of row m
+ * (word k / 32, bit k % 32) = label k occurs in bytes [m member_bytes, (m + 1) member_bytes) of dev_labels.  member_bytes 1 .. 2^30,
+ * any alignment of dev_labels; n == 0 gives one all-zero row.  One pass, deterministic, synchronous. */
+int boa_label_member_presence(boa_ctx* ctx, const uint8_t* dev_labels, size_t n, size_t member_bytes, uint32_t* host_bits);
+/* boa_deflate_label_pairs: pair p = (host_pair_label[p], host_pair_member[p]) yields the raw deflate body and the CRC-32 of the payload
+ * (dev_labels[i] == label) ? 1 : 0 over that member: body p at [host_offsets[p], host_offsets[p + 1]) of dev_out (n_pairs + 1 entries),
+ * byte for byte what boa_deflate_members2(mask, n, member_bytes, row_bytes, 1, flags, ..) yields for the member on the materialised
+ * mask.  Any pair may be listed, in any order, present or not, more than once.  The launch covers the blocks of the listed pairs
+ * only.  BOA_EINVAL before anything is launched: out_capacity below the sum over the pairs of (member length + 5 bytes per 16 KiB
+ * block of it; at least one block: boa_deflate_bound(member length, member length), 5 for the empty payload), a member index at or
+ * beyond n_members, an unknown flag bit, n_pairs < 0.  n_pairs == 0 returns BOA_OK with host_offsets[0] = 0 and launches nothing.
+ * Deterministic.  Synchronous. */
+int boa_deflate_label_pairs(boa_ctx* ctx, const uint8_t* dev_labels, size_t n, size_t member_bytes, int row_bytes, int flags,
+                            const uint8_t* host_pair_label, const uint32_t* host_pair_member, int n_pairs, uint8_t* dev_out,
+                            size_t out_capacity, size_t* host_offsets, uint32_t* host_crc32);
+
 /* ------------------------------------------------------------------ inflate of .nii.gz inputs (inflate.hip) --- */
 /* Raw deflate streams (RFC 1951) decoded on the device, each checked against its gzip trailer (RFC 1952).  A stream is one member's
  * body: stream_off[m] / stream_len[m] = its place in dev_src (src_bytes), an empty history, stream_size[m] = its payload bytes (the
