@@ -10,6 +10,7 @@ TS/python_api.py:670-757).  Anything else raises NotImplementedError -- nothing 
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import logging
 import os
@@ -30,7 +31,6 @@ from .util import convert_resampling_slices
 logger = logging.getLogger(__name__)
 
 _CTX: Dict[int, Context] = {}
-BODY_PARTS_MAP = {1: "torso", 2: "head", 3: "arms", 4: "legs", 5: "others", 6: "breasts"}   # BCA/body_parts/definition.py
 
 
 def get_context(device: Optional[str] = None) -> Context:
@@ -144,7 +144,8 @@ def _segment_one(ctx, name, ct, affine, hdr, folder, fast, recompute, totalsegme
     if split_masks and name == "body":
         raise NotImplementedError("ml=False with task body: the derived masks body.nii.gz and skin.nii.gz (combine_masks, extract_skin; "
                                   "TS/nnunet.py:821-827) are not implemented; use ml=True")
-    small_blobs = bool(params.get("remove_small_blobs", False))
+    small_blobs, fastest = bool(params.get("remove_small_blobs", False)), bool(params.get("fastest", False))
+    body_seg, force_split = bool(params.get("body_seg", False)), bool(params.get("force_split", False))
     roi_subset, robust = params.get("roi_subset"), False
     if params.get("roi_subset_robust") is not None:              # TS/python_api.py:655-664
         roi_subset, robust = params["roi_subset_robust"], True
@@ -163,45 +164,28 @@ def _segment_one(ctx, name, ct, affine, hdr, folder, fast, recompute, totalsegme
     if target.is_file() and not recompute:
         logger.info("The model was already computed, skipping...")
         return
-    if name == "total":
-        key = total_model_key(fast, bool(params.get("fastest", False)))
+    if name in ("total", "body"):
+        if name == "total":
+            key, names = total_model_key(fast, fastest), label_maps.CLASS_MAP_TOTAL
+        else:                                                     # TS/python_api.py:272-287
+            key, names = ("body_fast" if fast else "body"), label_maps.class_map("body")
         multimodel = key == "total"
         resample = model_store.TASKS[key]["resample"]
-        if roi_subset is not None:                                # (body_seg cannot be used together with it, TS/python_api.py:675)
+        if roi_subset is not None:                                # (`total` only; body_seg cannot be used together with it, TS/python_api.py:675)
             selected = label_maps.parts_for_roi_subset(roi_subset) if multimodel else None
             rough = "total_fast" if robust else "total_6mm"
             seg = run_roi_subset(ctx, ct, affine, model_store.load_task_models(rough), model_store.load_task_models(key, task_ids=selected),
                                  roi_subset, resample=resample, multimodel=multimodel, rough_resample=model_store.TASKS[rough]["resample"],
-                                 remove_small_blobs=small_blobs, force_split=bool(params.get("force_split", False)),
-                                 statistics_out=stats_fast)
-        elif params.get("body_seg", False):                       # TS/python_api.py:739-764
+                                 remove_small_blobs=small_blobs, force_split=force_split, statistics_out=stats_fast)
+            names = {k: v for k, v in names.items() if v in roi_subset}
+        elif name == "total" and body_seg:                        # TS/python_api.py:739-764
             if stats_fast is not None:
                 raise NotImplementedError("statistics together with fast and body_seg")
             seg = run_with_body_crop(ctx, "total", ct, affine, model_store.load_task_models("body_fast"), model_store.load_task_models(key),
                                      resample=resample, multimodel=multimodel, remove_small_blobs=small_blobs)
         else:
-            task = SegmentationTask(ctx, "total", model_store.load_task_models(key), resample=resample, multimodel=multimodel)
-            try:
-                if stats_fast is None:
-                    seg = task.predict_image(ct, affine, remove_small_blobs=small_blobs)
-                else:
-                    seg = task.predict_image(ct, affine, remove_small_blobs=small_blobs, statistics_out=stats_fast)
-            finally:
-                task.close()
-        names = label_maps.CLASS_MAP_TOTAL
-        if roi_subset is not None:
-            names = {k: v for k, v in names.items() if v in roi_subset}
-    elif name == "body":                                        # TS/python_api.py:272-287
-        key = "body_fast" if fast else "body"
-        task = SegmentationTask(ctx, "body", model_store.load_task_models(key), resample=model_store.TASKS[key]["resample"], multimodel=False)
-        try:
-            if stats_fast is None:
-                seg = task.predict_image(ct, affine, remove_small_blobs=small_blobs)
-            else:
+            with SegmentationTask(ctx, name, model_store.load_task_models(key), resample=resample, multimodel=multimodel) as task:
                 seg = task.predict_image(ct, affine, remove_small_blobs=small_blobs, statistics_out=stats_fast)
-        finally:
-            task.close()
-        names = label_maps.class_map("body")
     else:
         if fast:
             raise ValueError(f"task {name} does not work with option --fast")   # TS/python_api.py:242 ff.
@@ -246,8 +230,7 @@ def _run_bca_model(ctx, name, ct, affine, hdr, folder, fast_bca, bca_params, spl
     if name != "bca" and name in done:
         return
     models = {t: (model_store.load_task_models(t, fast_bca)[0][1:3] if t not in done else None) for t in wanted}
-    pipe = BcaPipelineHip(ctx, models.get("body_parts"), models.get("body_regions"), fast_bca=fast_bca)
-    try:
+    with contextlib.closing(BcaPipelineHip(ctx, models.get("body_parts"), models.get("body_regions"), fast_bca=fast_bca)) as pipe:
         if name != "bca":
             nifti.save_volume(folder / f"{name}.nii.gz", pipe.inference(name, ct, affine, force_split=split), affine, ctx=ctx, like=hdr)
             return
@@ -265,5 +248,3 @@ def _run_bca_model(ctx, name, ct, affine, hdr, folder, fast_bca, bca_params, spl
                 json.dump(out["vertebrae"], fh, indent=2)
         with (folder / "bca-measurements.json").open("w") as fh:
             json.dump(out["bca_measurements"], fh, indent=2, default=float)
-    finally:
-        pipe.close()

@@ -73,6 +73,23 @@ def _raise_if_inf(flag, ring=None, message: str = INF_MESSAGE):
         raise RuntimeError(message)
 
 
+def _finalize(pred: "HipPredictor", w: _Window, acc, nacc, fold, f: int, flag, labels=None, lut_p=None, merge: bool = False, planes=None):
+    """The one place that calls boa_finalize_labels / boa_finalize_labels_planes and knows their integer flags.  `acc / nacc` become
+    the normalised fp16 logits of fold `f`; with an ensemble buffer `fold` (None: a single fold) they are added to it in fold order
+    (fold 0 starts it) and the last fold takes the mean over `w.nf`.  `labels` (a buffer): the caller wants labels -- the last fold
+    writes the argmax through `lut_p`, merged when `merge`, cropped to `w.V`.  `labels=None`: the caller wants the normalised
+    (fold-mean) logits left in place -- in `fold`, or without one written back into `acc`; lut, merge and crop are then unused.
+    `planes` = (lo, hi): only those planes of axis 0, a rank's share."""
+    last, crop = f == w.nf - 1, w.crop and labels is not None
+    args = (pred.ctx.h, acc.vp, nacc.vp, w.C_, int3(w.PV), fold.vp if fold else None, 1 if (fold and f) else 0,
+            w.nf if (last and fold) else 0, 0 if (labels is not None or fold) else 1, lut_p, 1 if merge else 0,
+            labels.vp if (last and labels is not None) else None, int3(w.below) if crop else None, int3(w.V) if crop else None, flag.vp)
+    if planes is None:
+        check(pred.lib.boa_finalize_labels(*args), "boa_finalize_labels")
+    else:
+        check(pred.lib.boa_finalize_labels_planes(*args, int(planes[0]), int(planes[1])), "boa_finalize_labels_planes")
+
+
 class HipPredictor:
     _PRECISIONS = {"fp16": 0, "fp32_ref": 1, "fp32": 2}
 
@@ -231,16 +248,15 @@ class HipPredictor:
 
     def predict_sliding_window_return_logits(self, input_image: np.ndarray, fold: int = 0) -> np.ndarray:
         V, PV, below, origins = self._setup(input_image)
-        C_ = self.geom.num_classes
-        nvox = int(np.prod(PV))
+        w = _Window(self, V)
+        C_, nvox = w.C_, w.nvox
         with Scope() as sc:
             dvol = sc.own(self.ctx.from_numpy(np.ascontiguousarray(input_image, dtype=np.float32)))
             acc = sc.own(self.ctx.alloc(C_ * nvox * 2))
             nacc = sc.own(self.ctx.alloc(nvox * 2))
             flag = sc.own(self.ctx.zeros(4))
             self._run_fold(dvol, V, PV, below, origins, acc, nacc, fold)
-            check(self.lib.boa_finalize_labels(self.ctx.h, acc.vp, nacc.vp, C_, int3(PV), None, 0, 0, 1, None, 0, None,
-                                               None, None, flag.vp), "boa_finalize_labels")
+            _finalize(self, w, acc, nacc, None, fold, flag)      # (this fold's normalised logits, in `acc`)
             _raise_if_inf(flag, message="Encountered inf in predicted array. Aborting... If this problem persists, reduce "
                                         "value_scaling_factor in compute_gaussian or increase the dtype of predicted_logits "
                                         "to fp32")
@@ -273,7 +289,7 @@ class HipPredictor:
         grid (nnU-Net's own resampling, export_prediction.py:25-33): the fold-mean logits are resampled with order 1 to
         `out_dims` and reduced to labels there (`boa_resize_logits_argmax`); labels_out is then uint8 [*out_dims]."""
         if shard is not None and shard.comm.world > 1:
-            return self._predict_segmentation_sharded(dvol, V, labels_out, lut, merge, work, shard, resample_to)
+            return self.begin_segmentation_sharded(dvol, V, labels_out, lut, merge, work, shard, resample_to).finish()
         w = _Window(self, V, lut)
         direct = resample_to is None
         with _scratch(self.ctx, work) as ws:
@@ -284,14 +300,9 @@ class HipPredictor:
             acc, nacc, fold = self._planes(w, ws)
             for f in range(w.nf):
                 self._run_fold(dvol, w.V, w.PV, w.below, w.origins, acc, nacc, f, gather=True)
-                last = f == w.nf - 1
                 # resampled path: keep the normalised (fold-mean) logits -- in `acc` for one fold, in `fold` otherwise -- and
                 # take the argmax after the resampling
-                check(self.lib.boa_finalize_labels(
-                    self.ctx.h, acc.vp, nacc.vp, w.C_, int3(w.PV), fold.vp if fold else None, 0 if f == 0 else 1,
-                    w.nf if (last and fold) else 0, 0 if (direct or fold) else 1, w.lut_p,
-                    1 if merge else 0, labels_out.vp if (last and direct) else None, int3(w.below) if w.crop else None,
-                    int3(w.V) if w.crop else None, flag.vp), "boa_finalize_labels")
+                _finalize(self, w, acc, nacc, fold, f, flag, labels_out if direct else None, w.lut_p, merge)
             _raise_if_inf(flag, ws.ring)
             if not direct:
                 out_dims, slice_axis = resample_to
@@ -329,10 +340,6 @@ class HipPredictor:
             check(rc, "boa_net_predict_labels_fold")
         return True
 
-    def _predict_segmentation_sharded(self, dvol, V, labels_out, lut, merge, work, shard, resample_to=None):
-        job = self.begin_segmentation_sharded(dvol, V, labels_out, lut, merge, work, shard, resample_to)
-        job.finish()
-
     def begin_segmentation_sharded(self, dvol, V, labels_out, lut, merge, work, shard, resample_to=None, after_first_start=None):
         """Shared-volume prediction in two halves (tile_shard.start_fold_sharded / finish_fold_sharded): this call runs the tiles
         of every fold and queues the slab exchanges; the returned job's `finish()` applies what arrived, reduces the owned planes
@@ -352,7 +359,7 @@ class HipPredictor:
                                      bbox_lo=None, full_dims=None, perm=(0, 1, 2)):
         """All folds -> class probabilities on device (convert_predicted_logits_to_segmentation_with_correct_shape with
         return_probabilities=True, export_prediction.py:14-71).  dvol: fp32 [Cin,*V] resident.  The scatter form of the tile loop
-        and `boa_finalize_labels(write_logits=1)` per fold leave the normalised fp16 logits, their fold mean goes through
+        and `_finalize` without `labels` per fold leave the normalised fp16 logits, their fold mean goes through
         `boa_logits_to_probabilities`: pad reverted, `resample_to` = (out_dims, slice_axis) as in predict_segmentation_device,
         the box inserted at `bbox_lo` of `full_dims` (default: the box is the grid) with background (1, 0, ..) around it, the
         spatial axes permuted by `perm`.  prob_out: fp32 [C, *full_dims permuted]; labels_out (optional): uint8, the first maximum
@@ -363,10 +370,7 @@ class HipPredictor:
             acc, nacc, fold = self._planes(w, ws)
             for f in range(w.nf):
                 self._run_fold(dvol, w.V, w.PV, w.below, w.origins, acc, nacc, f)
-                last = f == w.nf - 1
-                check(self.lib.boa_finalize_labels(
-                    self.ctx.h, acc.vp, nacc.vp, w.C_, int3(w.PV), fold.vp if fold else None, 0 if f == 0 else 1,
-                    w.nf if (last and fold) else 0, 0 if fold else 1, None, 0, None, None, None, flag.vp), "boa_finalize_labels")
+                _finalize(self, w, acc, nacc, fold, f, flag)
             _raise_if_inf(flag, ws.ring)
             out_dims, slice_axis = resample_to if resample_to is not None else (None, -1)
             box = list(out_dims) if out_dims is not None else w.V
@@ -443,8 +447,7 @@ class _ShardedJob:
                 finally:
                     eng.close()
                 # acc / n -> normalised fp16 logits in place on the planes this rank owns (inf check included)
-                check(self.lib.boa_finalize_labels_planes(self.ctx.h, F.vp, nacc.vp, self.w.C_, int3(self.w.PV), None, 0, 0, 1, None, 0, None,
-                                                          None, None, self.flag.vp, lo, hi), "boa_finalize_labels_planes")
+                _finalize(self.p, self.w, F, nacc, None, f, self.flag, planes=(lo, hi))
             self.flogits.append((F, lo, hi))
             if f == 0 and after_first_start is not None:
                 after_first_start()
@@ -468,11 +471,7 @@ class _ShardedJob:
         ones = self.work.buf("ones", self.w.nvox * 2, init=lambda b: b.upload(np.full(self.w.nvox, 0x3C00, np.uint16)))
         fold = self.work.buf("fold", self.w.C_ * self.w.nvox * 2)
         for f, (F, _, _) in enumerate(self.flogits):
-            last = f == self.w.nf - 1
-            check(self.lib.boa_finalize_labels_planes(
-                self.ctx.h, F.vp, ones.vp, self.w.C_, int3(self.w.PV), fold.vp, 0 if f == 0 else 1, self.w.nf if last else 0, 0, self.w.lut_p, 0,
-                self.part.vp if last else None, int3(self.w.below) if self.w.crop else None, int3(self.w.V) if self.w.crop else None, self.flag.vp,
-                P0, P1), "boa_finalize_labels_planes")
+            _finalize(self.p, self.w, F, ones, fold, f, self.flag, self.part, self.w.lut_p, planes=(P0, P1))
 
     def begin(self, after_first_start=None):
         self.flag = self.work.buf(f"flag{self.work.turn('job')}", 4)      # (its own alternating flags: read by all_reduce_flag in `finish`)
@@ -498,15 +497,10 @@ class _ShardedJob:
             self.lo, self.hi = self.ts.finish_fold_sharded(state)
         finally:
             eng.close()
-        last = f == self.w.nf - 1
-        fold, direct = self.fold, self.direct
         # (resampled path: keep the normalised fold-mean logits of the owned planes -- in the accumulators for one fold, in `fold` otherwise)
-        check(self.lib.boa_finalize_labels_planes(
-            self.ctx.h, eng.acc.vp, eng.nacc.vp, self.w.C_, int3(self.w.PV), fold.vp if fold else None, 0 if f == 0 else 1,
-            self.w.nf if (last and fold) else 0, 0 if (direct or fold) else 1, self.w.lut_p, 0, self.part.vp if (last and direct) else None,
-            int3(self.w.below) if self.w.crop else None, int3(self.w.V) if self.w.crop else None, self.flag.vp, self.lo, self.hi),
-            "boa_finalize_labels_planes")
-        self.logits = fold if fold else eng.acc
+        _finalize(self.p, self.w, eng.acc, eng.nacc, self.fold, f, self.flag, self.part if self.direct else None, self.w.lut_p,
+                  planes=(self.lo, self.hi))
+        self.logits = self.fold if self.fold else eng.acc
 
     def finish(self):
         if self.done:

@@ -20,7 +20,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -70,9 +70,21 @@ def split_bounds(nz: int) -> Tuple[List[Tuple[int, int]], List[Tuple[slice, slic
     return parts, comb
 
 
-class SegmentationTask:
+class _WayBack(NamedTuple):
+    """What `SegmentationTask._to_model_grid` did to the input, for `_to_input_grid` to undo."""
+    bbox: Optional[list]              # crop to the mask, on the input array (None: no crop)
+    cropped_affine: np.ndarray        # of the cropped input: its orientation is what undo_canonical restores
+    thick_ornt: Optional[np.ndarray]  # the `resample_only_thickness` reorientation RAS -> axcodes (None: none)
+    in_shape: tuple                   # before change_spacing
+    zoom: Optional[np.ndarray]        # of change_spacing (None: the spacing did not change)
+    ss: tuple                         # after it: the model grid
+    orig_shape: tuple                 # of the input array
+    cast: Optional[type]              # dtype of crop_to_mask (None: no crop)
+
+
+class SegmentationTask(contextlib.AbstractContextManager):
     """`models`: [(task_id, ModelConfig, [weight blob per fold])]; several entries = multi-model task (`total`)
-    whose part label maps are merged into the global map (later parts overwrite)."""
+    whose part label maps are merged into the global map (later parts overwrite).  `with SegmentationTask(...) as t:` closes it."""
 
     def __init__(self, ctx: Context, task_name: str, models: Sequence[Tuple[int, ModelConfig, Sequence[np.ndarray]]],
                  resample: Optional[float] = None, resample_only_thickness: bool = False, multimodel: Optional[bool] = None,
@@ -118,9 +130,13 @@ class SegmentationTask:
             p.close()
         self._work.free()
 
+    def __exit__(self, *exc):
+        self.close()
+
     # ---- device core: resident CT [z,y,x] -> resident uint8 labels -----------------------------------------
-    def predict_zyx_device(self, d_ct, shape, d_labels, in_dtype: int = 0, spacing_zyx=None):
-        """in_dtype 0 int16 / 1 float32 / 2 int32.  Labels are zeroed here, then every model writes (merges) into them.
+    def predict_zyx_device(self, d_ct, shape, d_labels, in_dtype: int = 0, spacing_zyx=None, only=None):
+        """in_dtype 0 int16 / 1 float32 / 2 int32.  Labels are zeroed here, then every model -- with `only` (task ids; `roi_subset`, not
+        for the sharded modes) every model it lists -- writes (merges) into them.
         `spacing_zyx`: voxel spacing of the array (nnU-Net axis order); when it differs from a model's plans spacing the
         normalised volume is resampled to the plans' grid and the logits back (nnU-Net's own resampling,
         default_preprocessor.py:82-93 / export_prediction.py:25-33) -- None = the array is at the plans' spacing."""
@@ -138,7 +154,8 @@ class SegmentationTask:
             self._predict_zyx_unit_sharded(d_ct, shape, d_labels, in_dtype, n)
         else:
             for k in range(len(self.parts)):
-                self._run_model(k, d_ct, shape, d_labels, in_dtype, n, spacing_zyx, merge=self.multimodel, shard=self.shard)
+                if only is None or self.parts[k][0] in only:
+                    self._run_model(k, d_ct, shape, d_labels, in_dtype, n, spacing_zyx, merge=self.multimodel, shard=self.shard)
         ring.check()   # the models' inf flags of this rank, one read per volume
 
     # ---- (row x model) units: all ranks busy on one multi-model volume ---------------------------------------------------------
@@ -233,13 +250,13 @@ class SegmentationTask:
 
     # ---- one (sub-)volume, device resident ----------------------------------------------------------------------
     def _predict_part_device(self, part_xyz: DevArray, dst_xyz: DevArray, src_lo: int, src_hi: int, spacing_zyx=None,
-                             save_probabilities=None):
+                             save_probabilities=None, only=None):
         """`part_xyz`: (x,y,z) view of the (resampled) CT that TS would write to s0k_0000.nii.gz.  Its labels for the
         part-local z range [src_lo, src_hi) are written into `dst_xyz` (a zero-initialised (x,y,z) view of the same
         x/y extent and src_hi - src_lo slices).  nibabel reader view change, crop_to_nonzero and insert_crop_into_image
         (export_prediction.py:44-47) are views + one device copy each way.  `save_probabilities` (a path): every model's class
         probabilities on this part's (z, y, x) grid are written there and the labels are taken from them
-        (`_predict_part_probabilities`)."""
+        (`_predict_part_probabilities`).  `only`: as in `predict_zyx_device`."""
         dt = part_xyz.dtype
         want = dt if dt in (np.dtype(np.int16), np.dtype(np.int32)) else np.dtype(np.float32)
         code = {np.dtype(np.int16): 0, np.dtype(np.float32): 1, np.dtype(np.int32): 2}[want]
@@ -258,11 +275,11 @@ class SegmentationTask:
             crop = work if full else copy_of(work.box(bbox_t).contiguous(), work)
             if save_probabilities is not None:
                 # (the labels come back on the part's whole (z, y, x) grid: the crop box is already put back)
-                lab_zyx = sc.own(self._predict_part_probabilities(crop, work.shape, bbox_t, code, spacing_zyx, sp_t, save_probabilities))
+                lab_zyx = sc.own(self._predict_part_probabilities(crop, work.shape, bbox_t, code, spacing_zyx, sp_t, save_probabilities, only))
                 bbox = [[0, int(v)] for v in lab_zyx.shape]
             else:
                 d_lab = sc.own(DevArray.empty(self.ctx, crop.shape, np.uint8))
-                self.predict_zyx_device(crop.buf, crop.shape, d_lab.buf, in_dtype=code, spacing_zyx=sp_t)
+                self.predict_zyx_device(crop.buf, crop.shape, d_lab.buf, in_dtype=code, spacing_zyx=sp_t, only=only)
                 # back to (z, y, x): axis i of the transposed array is axis tf[i] of the original
                 bbox = [None, None, None]
                 for i in range(3):
@@ -274,7 +291,7 @@ class SegmentationTask:
                 dst = dst_xyz.slice(2, k0 - src_lo, k1 - src_lo).slice(1, bbox[1][0], bbox[1][1]).slice(0, bbox[2][0], bbox[2][1])
                 src.copy_to(dst)
 
-    def _predict_part_probabilities(self, crop: DevArray, full_shape, bbox_t, in_dtype: int, spacing_zyx, sp_t, path) -> DevArray:
+    def _predict_part_probabilities(self, crop: DevArray, full_shape, bbox_t, in_dtype: int, spacing_zyx, sp_t, path, only=None) -> DevArray:
         """export_prediction_from_logits with save_probabilities (export_prediction.py:14-71, :99-102) for every model of the task
         on one part: `crop` is the transposed, nonzero-cropped array, `full_shape` its shape before the crop, `bbox_t` the crop box.
         Per model: the fold-mean logits -> `boa_logits_to_probabilities` (plan-spacing resampling reverted, the box put back into
@@ -300,6 +317,8 @@ class SegmentationTask:
             labels = sc.own(DevArray.zeros(ctx, out_shape, np.uint8))
             part = sc.own(DevArray.empty(ctx, out_shape, np.uint8)) if self.multimodel else labels
             for task_id, cfg, p, lut in self.parts:
+                if only is not None and task_id not in only:
+                    continue
                 nc = p.geom.num_classes
                 prob = ctx.alloc(nc * n_full * 4)
                 try:
@@ -314,14 +333,6 @@ class SegmentationTask:
                 finally:
                     prob.free()
             return sc.release(labels)
-
-    def predict_part_xyz(self, data_xyz: np.ndarray) -> np.ndarray:
-        """One (sub-)volume as TS writes it to s0k_0000.nii.gz: (x,y,z) array -> uint8 labels (x,y,z)."""
-        with Scope() as sc:
-            src = sc.own(DevArray.from_numpy(self.ctx, self._supported(data_xyz)))
-            seg = sc.own(DevArray.zeros(self.ctx, src.shape, np.uint8))
-            self._predict_part_device(src, seg, 0, src.shape[2])
-            return seg.download()
 
     @staticmethod
     def _supported(data: np.ndarray) -> np.ndarray:
@@ -377,23 +388,27 @@ class SegmentationTask:
         `labels`, the model-grid label array (x, y, z) BEFORE that post-processing, and `zooms`, its float32 header zooms; with
         `statistics_out` also `labels_post`, the labels AFTER it, and `ct`, the model-grid image (the two arrays the statistics see).
 
-        `roi_subset` (names of the task's class map; nnUNet_predict_image(roi_subset=...), TS/nnunet.py:388-390,707-709): on the
-        input grid, after the restore, every label that is not one of them is cleared -- one look-up table pass on the device
-        (`boa_label_apply_lut`).  Which part models run is the caller's choice of `models` (`run_roi_subset`).
+        `roi_subset` (names of the task's class map; nnUNet_predict_image(roi_subset=...), TS/nnunet.py:388-390,519-531,707-709): of
+        a multi-model `total` task only the part models whose class map holds one of the names run
+        (`label_maps.parts_for_roi_subset`; a single-model task runs its one model), and on the input grid, after the restore, every
+        label that is not one of them is cleared -- one look-up table pass on the device (`boa_label_apply_lut`).
 
         `statistics_out` (a dict; `statistics_fast` of TS/python_api.py:636-641, TS/nnunet.py:642-659): get_basic_statistics on the
         MODEL grid -- the resampled (and cropped) canonical image and the labels after the blob post-processing, before the resample
         back, header zooms those of that grid -- through `statistics.basic_statistics`; `statistics_out["params"]` (optional) holds
         its keyword arguments (exclude_masks_at_border, roi_subset, metric, normalized_intensities, file_out), the result goes to
         `statistics_out["stats"]`.  Neither is implemented for the sharded modes."""
-        if (roi_subset is not None or statistics_out is not None) and (self.shard is not None or self.model_shard is not None):
-            raise NotImplementedError("roi_subset / statistics with a tile- or model-sharded task")
-        keep_lut = None if roi_subset is None else label_maps.subset_lut(roi_subset)
-        if save_probabilities is not None and (self.shard is not None or self.model_shard is not None):
-            raise NotImplementedError("save_probabilities with a tile- or model-sharded task")
-        blob_pp = bool(remove_small_blobs) or self.task_name == "body"
-        if blob_pp and (self.shard is not None or self.model_shard is not None):
-            raise NotImplementedError("blob post-processing (remove_small_blobs, task body) with a tile- or model-sharded task")
+        if self.shard is not None or self.model_shard is not None:
+            option = ("roi_subset" if roi_subset is not None else "statistics" if statistics_out is not None else
+                      "save_probabilities" if save_probabilities is not None else
+                      "blob post-processing (remove_small_blobs, task body)" if (remove_small_blobs or self.task_name == "body") else None)
+            if option is not None:
+                raise NotImplementedError(f"{option} with a tile- or model-sharded task")
+        keep_lut = only = None
+        if roi_subset is not None:
+            keep_lut = label_maps.subset_lut(roi_subset)
+            if self.multimodel and self.task_name == "total":
+                only = label_maps.parts_for_roi_subset(roi_subset)
         resident = isinstance(data, DevArray)
         if not resident:
             if data.ndim == 2:
@@ -402,117 +417,143 @@ class SegmentationTask:
                 data = data[:, :, :, 0]
             if data.dtype.fields is not None:
                 raise TypeError(f"Invalid dtype {data.dtype}. Expected a simple dtype, not a structured one.")
-        ctx = self.ctx
+        if crop_mask is not None and crop_mask.sum() == 0:              # TS/nnunet.py:428-446
+            shape = tuple(int(v) for v in data.shape)
+            return DevArray.zeros(self.ctx, shape, np.uint8) if return_device else np.zeros(shape, dtype=np.uint8)
+        with Scope() as sc:                                            # device arrays to release
+            img, spacing, back = self._to_model_grid(sc, data, affine, crop_mask, crop_addon, axcodes)
+            seg = self._model_grid_labels(sc, img, spacing, force_split, save_probabilities, remove_small_blobs, model_grid_out,
+                                          statistics_out, only)
+            out = self._to_input_grid(sc, seg, back, axcodes, keep_lut)
+            if return_device:
+                return sc.release(out.contiguous(force_copy=(resident and out.buf is data.buf)))
+            return out.download()
+
+    def _to_model_grid(self, sc: Scope, data, affine, crop_mask, crop_addon, axcodes):
+        """Input grid -> model grid: crop to the mask, as_closest_canonical, the `resample_only_thickness` reorientation to
+        `axcodes`, change_spacing (order 3, through `resample_cache` for a resident volume).  -> (the model-grid image, its spacing
+        (x, y, z), the `_WayBack`).  Views of `data` stay its owner's, copies go to `sc`, a cached resample buffer is the cache's."""
+        ctx, own = self.ctx, sc.own
+        resident = isinstance(data, DevArray)
         orig_shape = tuple(int(v) for v in data.shape)
         affine = np.asarray(affine, dtype=np.float64)
         aff = affine
         bbox = None
-        if crop_mask is not None and crop_mask.sum() == 0:              # TS/nnunet.py:428-446
-            return DevArray.zeros(ctx, orig_shape, np.uint8) if return_device else np.zeros(orig_shape, dtype=np.uint8)
-        with Scope() as sc:                                            # device arrays to release
-            own = sc.own
-            view = data if resident else own(DevArray.from_numpy(ctx, self._supported(data)))
-            cast = None
-            if crop_mask is not None:
-                addon = (np.array(crop_addon) / orientation.zooms_from_affine(aff)).astype(int)   # mm -> voxels
-                bbox = get_bbox_from_mask(crop_mask, outside_value=0, addon=addon)
-                view = view.box(bbox)
-                aff = aff.copy()
-                aff[:3, 3] = np.dot(affine, np.array([bbox[0][0], bbox[1][0], bbox[2][0], 1]))[:3]
-                cast = np.int32                                          # crop_to_mask(dtype=np.int32)
-            cropped_affine = aff
-            ornt = orientation.io_orientation(aff)                       # as_closest_canonical
-            if not np.array_equal(ornt, orientation.RAS_ORNT):
-                aff = aff.dot(orientation.inv_ornt_aff(ornt, view.shape))
-                view = view.apply_orientation(ornt)
-            resample = None if self.resample is None else [self.resample] * 3
-            thick_ornt = None
-            if self.resample_only_thickness:
-                cur = "".join(orientation.aff2axcodes(aff))
-                if cur != "".join(axcodes):
-                    thick_ornt = orientation.ornt_transform(orientation.axcodes2ornt(cur), orientation.axcodes2ornt(axcodes))
-                    aff = aff.dot(orientation.inv_ornt_aff(thick_ornt, view.shape))
-                    view = view.apply_orientation(thick_ornt)
-                zooms = orientation.zooms_from_affine(aff)
-                resample = [zooms[0], zooms[1], resample[0]]
-            in_shape = view.shape
+        view = data if resident else own(DevArray.from_numpy(ctx, self._supported(data)))
+        cast = None
+        if crop_mask is not None:
+            addon = (np.array(crop_addon) / orientation.zooms_from_affine(aff)).astype(int)   # mm -> voxels
+            bbox = get_bbox_from_mask(crop_mask, outside_value=0, addon=addon)
+            view = view.box(bbox)
+            aff = aff.copy()
+            aff[:3, 3] = np.dot(affine, np.array([bbox[0][0], bbox[1][0], bbox[2][0], 1]))[:3]
+            cast = np.int32                                          # crop_to_mask(dtype=np.int32)
+        cropped_affine = aff
+        ornt = orientation.io_orientation(aff)                       # as_closest_canonical
+        if not np.array_equal(ornt, orientation.RAS_ORNT):
+            aff = aff.dot(orientation.inv_ornt_aff(ornt, view.shape))
+            view = view.apply_orientation(ornt)
+        resample = None if self.resample is None else [self.resample] * 3
+        thick_ornt = None
+        if self.resample_only_thickness:
+            cur = "".join(orientation.aff2axcodes(aff))
+            if cur != "".join(axcodes):
+                thick_ornt = orientation.ornt_transform(orientation.axcodes2ornt(cur), orientation.axcodes2ornt(axcodes))
+                aff = aff.dot(orientation.inv_ornt_aff(thick_ornt, view.shape))
+                view = view.apply_orientation(thick_ornt)
             zooms = orientation.zooms_from_affine(aff)
-            zoom = None
-            if resample is not None:                                     # change_spacing (TS/resampling.py:165-181)
-                new_spacing = np.array(resample)
-                zoom = zooms / new_spacing
-                if np.array_equal(zooms, new_spacing):
-                    zoom = None
-            if zoom is not None:
-                out_shape = rs.zoomed_shape(in_shape, zoom)
-                key = None
-                if self.resample_cache is not None and resident:
-                    key = (data.buf.ptr, view.offset, view.shape, view.strides, str(view.dtype), str(cast), tuple(out_shape),
-                           tuple(float(z) for z in zoom))   # (the cache lives for ONE resident volume: pipeline.run_resident)
-                if key is not None and key in self.resample_cache:
-                    img_rsp = DevArray(ctx, self.resample_cache[key], out_shape, np.int32)      # (not owned: the cache's)
+            resample = [zooms[0], zooms[1], resample[0]]
+        in_shape = view.shape
+        zooms = orientation.zooms_from_affine(aff)
+        zoom = None
+        if resample is not None:                                     # change_spacing (TS/resampling.py:165-181)
+            new_spacing = np.array(resample)
+            zoom = zooms / new_spacing
+            if np.array_equal(zooms, new_spacing):
+                zoom = None
+        if zoom is not None:
+            out_shape = rs.zoomed_shape(in_shape, zoom)
+            key = None
+            if self.resample_cache is not None and resident:
+                key = (data.buf.ptr, view.offset, view.shape, view.strides, str(view.dtype), str(cast), tuple(out_shape),
+                       tuple(float(z) for z in zoom))   # (the cache lives for ONE resident volume: pipeline.run_resident)
+            if key is not None and key in self.resample_cache:
+                img_rsp = DevArray(ctx, self.resample_cache[key], out_shape, np.int32)      # (not owned: the cache's)
+            else:
+                src = view.contiguous(cast)
+                if src.buf is not view.buf:
+                    own(src)
+                if src.dtype == np.uint8:
+                    src = own(src.contiguous(np.int16, force_copy=True))
+                buf = rs.resample_cubic_device(ctx, src.buf, src.dtype, src.shape, out_shape, np.int32)
+                img_rsp = DevArray(ctx, buf, out_shape, np.int32)
+                if key is not None:
+                    self.resample_cache[key] = buf
                 else:
-                    src = view.contiguous(cast)
-                    if src.buf is not view.buf:
-                        own(src)
-                    if src.dtype == np.uint8:
-                        src = own(src.contiguous(np.int16, force_copy=True))
-                    buf = rs.resample_cubic_device(ctx, src.buf, src.dtype, src.shape, out_shape, np.int32)
-                    img_rsp = DevArray(ctx, buf, out_shape, np.int32)
-                    if key is not None:
-                        self.resample_cache[key] = buf
-                    else:
-                        own(img_rsp)
-                sp_rsp = np.array(resample, dtype=np.float64)
-            else:
-                img_rsp = view if cast is None else own(view.contiguous(cast))
-                sp_rsp = zooms
-            ss = img_rsp.shape
-            # nnU-Net reads the spacing from the header of the file TS wrote (float32 pixdim), in array axis order (z, y, x)
-            sp_zyx = [float(np.float32(v)) for v in sp_rsp[::-1]]
-            seg = own(DevArray.zeros(ctx, ss, np.uint8))
-            do_split = (np.prod(ss) > NR_VOXELS_THR and ss[2] > 200 and self.multimodel) or force_split
-            if do_split:
-                parts, comb = split_bounds(ss[2])
-                for k, ((lo, hi), (dst, srcsl)) in enumerate(zip(parts, comb)):
-                    a, b, _ = srcsl.indices(hi - lo)
-                    self._predict_part_device(img_rsp.slice(2, lo, hi), seg.slice(2, dst.start, dst.stop), a, b, sp_zyx,
-                                              save_probabilities=save_probabilities if k == 0 else None)
-            else:
-                self._predict_part_device(img_rsp, seg, 0, ss[2], sp_zyx, save_probabilities=save_probabilities)
-            zooms_rsp = np.asarray(sp_rsp, dtype=np.float32)            # header zooms of the model-grid image (float32 pixdim)
+                    own(img_rsp)
+            sp_rsp = np.array(resample, dtype=np.float64)
+        else:
+            img_rsp = view if cast is None else own(view.contiguous(cast))
+            sp_rsp = zooms
+        return img_rsp, sp_rsp, _WayBack(bbox, cropped_affine, thick_ornt, in_shape, zoom, img_rsp.shape, orig_shape, cast)
+
+    def _model_grid_labels(self, sc: Scope, img_rsp: DevArray, sp_rsp, force_split, save_probabilities, remove_small_blobs,
+                           model_grid_out, statistics_out, only) -> DevArray:
+        """Model-grid image -> its uint8 labels (x, y, z), owned by `sc`: the triple z-split or one part, per part every model of the
+        task (`only`: of these task ids), then on the whole grid the `model_grid_out` seam, the blob post-processing and the
+        `statistics_out` seam, as `predict_image` documents them."""
+        ss = img_rsp.shape
+        # nnU-Net reads the spacing from the header of the file TS wrote (float32 pixdim), in array axis order (z, y, x)
+        sp_zyx = [float(np.float32(v)) for v in sp_rsp[::-1]]
+        seg = sc.own(DevArray.zeros(self.ctx, ss, np.uint8))
+        if (np.prod(ss) > NR_VOXELS_THR and ss[2] > 200 and self.multimodel) or force_split:
+            parts, comb = split_bounds(ss[2])
+            for k, ((lo, hi), (dst, srcsl)) in enumerate(zip(parts, comb)):
+                a, b, _ = srcsl.indices(hi - lo)
+                self._predict_part_device(img_rsp.slice(2, lo, hi), seg.slice(2, dst.start, dst.stop), a, b, sp_zyx,
+                                          save_probabilities=save_probabilities if k == 0 else None, only=only)
+        else:
+            self._predict_part_device(img_rsp, seg, 0, ss[2], sp_zyx, save_probabilities=save_probabilities, only=only)
+        zooms_rsp = np.asarray(sp_rsp, dtype=np.float32)            # header zooms of the model-grid image (float32 pixdim)
+        if model_grid_out is not None:
+            model_grid_out["labels"], model_grid_out["zooms"] = seg.download(), zooms_rsp
+        if remove_small_blobs or self.task_name == "body":
+            self._postprocess_model_grid(seg, zooms_rsp, bool(remove_small_blobs))
+        if statistics_out is not None:
+            from . import statistics as st
+            statistics_out["stats"] = st.basic_statistics(self.ctx, seg, img_rsp, zooms_rsp, task=self.task_name,
+                                                          **dict(statistics_out.get("params") or {}))
             if model_grid_out is not None:
-                model_grid_out["labels"], model_grid_out["zooms"] = seg.download(), zooms_rsp
-            if blob_pp:
-                self._postprocess_model_grid(seg, zooms_rsp, bool(remove_small_blobs))
-            if statistics_out is not None:
-                from . import statistics as st
-                statistics_out["stats"] = st.basic_statistics(ctx, seg, img_rsp, zooms_rsp, task=self.task_name,
-                                                              **dict(statistics_out.get("params") or {}))
-                if model_grid_out is not None:
-                    model_grid_out["labels_post"], model_grid_out["ct"] = seg.download(), img_rsp.download()
-            if zoom is not None:                                         # back to the input grid (TS/nnunet.py:685-687)
-                if tuple(in_shape) != tuple(ss):
-                    buf = rs.resample_nearest_device(ctx, seg.buf, ss, in_shape)
-                    seg = own(DevArray(ctx, buf, in_shape, np.uint8))
-            out = seg
-            if thick_ornt is not None:
-                # the labels are in `axcodes` order; back to RAS before undo_canonical
-                out = out.apply_orientation(orientation.ornt_transform(orientation.axcodes2ornt(axcodes), orientation.RAS_ORNT))
-            out = out.apply_orientation(orientation.ornt_transform(orientation.RAS_ORNT, orientation.io_orientation(cropped_affine)))
-            if bbox is not None:                                         # undo_crop, TS/cropping.py:126-132
-                full = own(DevArray.zeros(ctx, orig_shape, np.uint8))
-                out.copy_to(full.box(bbox))
-                out = full
-            if tuple(out.shape) != orig_shape[:3]:
-                raise ValueError(f"shape mismatch after restore: {out.shape} vs {orig_shape}")   # check_if_shape_and_affine_identical
-            if keep_lut is not None:                                     # img_data *= np.isin(img_data, subset), TS/nnunet.py:707-709
-                out = own(out.contiguous(force_copy=True))
-                check(ctx.lib.boa_label_apply_lut(ctx.h, out.buf.vp, out.size, keep_lut.ctypes.data_as(C.c_void_p), out.buf.vp),
-                      "boa_label_apply_lut")
-            if return_device:
-                return sc.release(out.contiguous(force_copy=(resident and out.buf is data.buf)))
-            return out.download()
+                model_grid_out["labels_post"], model_grid_out["ct"] = seg.download(), img_rsp.download()
+        return seg
+
+    def _to_input_grid(self, sc: Scope, seg: DevArray, back: "_WayBack", axcodes, keep_lut) -> DevArray:
+        """Model-grid labels -> labels on the input grid (views of `seg`, or copies owned by `sc`): nearest resample back, the
+        thickness reorientation and the canonical one undone, undo_crop, the shape check, the `roi_subset` table `keep_lut`."""
+        ctx, out = self.ctx, seg
+        if back.zoom is not None and tuple(back.in_shape) != tuple(back.ss):      # back to the input grid (TS/nnunet.py:685-687)
+            buf = rs.resample_nearest_device(ctx, seg.buf, back.ss, back.in_shape)
+            out = sc.own(DevArray(ctx, buf, back.in_shape, np.uint8))
+        if back.thick_ornt is not None:
+            # the labels are in `axcodes` order; back to RAS before undo_canonical
+            out = out.apply_orientation(orientation.ornt_transform(orientation.axcodes2ornt(axcodes), orientation.RAS_ORNT))
+        out = out.apply_orientation(orientation.ornt_transform(orientation.RAS_ORNT, orientation.io_orientation(back.cropped_affine)))
+        if back.bbox is not None:                                    # undo_crop, TS/cropping.py:126-132
+            full = sc.own(DevArray.zeros(ctx, back.orig_shape, np.uint8))
+            out.copy_to(full.box(back.bbox))
+            out = full
+        if tuple(out.shape) != back.orig_shape[:3]:
+            raise ValueError(f"shape mismatch after restore: {out.shape} vs {back.orig_shape}")   # check_if_shape_and_affine_identical
+        if keep_lut is not None:                                     # img_data *= np.isin(img_data, subset), TS/nnunet.py:707-709
+            out = sc.own(out.contiguous(force_copy=True))
+            check(ctx.lib.boa_label_apply_lut(ctx.h, out.buf.vp, out.size, keep_lut.ctypes.data_as(C.c_void_p), out.buf.vp),
+                  "boa_label_apply_lut")
+        return out
+
+    def predict_roi_subset(self, data, affine, crop_mask: np.ndarray, roi_subset: Sequence[str], **options):
+        """`roi_subset` from the crop mask onward (TS/python_api.py:725-736): `predict_image` on the image cropped to the mask plus
+        20 mm, the parts that hold the names, only their labels.  `options`: further keywords of `predict_image`."""
+        return self.predict_image(data, affine, crop_mask=crop_mask, crop_addon=[20, 20, 20], roi_subset=roi_subset, **options)
 
 
 def write_probabilities(path, probabilities: np.ndarray, properties: dict) -> None:
@@ -575,18 +616,11 @@ def run_cascade_task(ctx: Context, task: str, data: np.ndarray, affine: np.ndarr
     rough_models / task_models: [(task_id, ModelConfig, [weight blob per fold])] as `model_store.load_task_models` gives.
     `save_probabilities` (a path): passed to the TASK's model (`SegmentationTask.predict_image`: the probabilities of the cropped
     image's grid); the rough model's are not kept -- in the reference every later model run overwrites the file."""
-    rough = SegmentationTask(ctx, "total", rough_models, resample=rough_resample, multimodel=False, max_batch=max_batch, precision=precision)
-    try:
-        organ_seg = rough.predict_image(data, affine)
-    finally:
-        rough.close()
+    organ_seg = rough_total(ctx, data, affine, rough_models, rough_resample, max_batch=max_batch, precision=precision)
     inv = label_maps.CLASS_MAP_TOTAL_INV
     crop_mask = np.isin(organ_seg, [inv[n] for n in crop_names]).astype(np.uint8)
-    t = SegmentationTask(ctx, task, task_models, resample=None, multimodel=False, max_batch=max_batch, precision=precision)
-    try:
+    with SegmentationTask(ctx, task, task_models, resample=None, multimodel=False, max_batch=max_batch, precision=precision) as t:
         seg = t.predict_image(data, affine, crop_mask=crop_mask, crop_addon=crop_addon, save_probabilities=save_probabilities)
-    finally:
-        t.close()
     if remove_outside_dilation is not None:
         remove_mask = np.isin(organ_seg, [inv[n] for n in (remove_outside or [])]).astype(np.uint8)
         # header zooms are float32 (nibabel): int(mm / np.mean(img.header.get_zooms()))
@@ -596,15 +630,19 @@ def run_cascade_task(ctx: Context, task: str, data: np.ndarray, affine: np.ndarr
     return seg
 
 
+def rough_total(ctx: Context, data, affine: np.ndarray, rough_models, rough_resample: float = 6.0, max_batch: int = 16,
+                precision: Optional[str] = None) -> np.ndarray:
+    """The rough single-model `total` segmentation at `rough_resample` mm that the crop masks are cut from (TS/python_api.py:705-722):
+    its `total` label volume on the input grid."""
+    with SegmentationTask(ctx, "total", rough_models, resample=rough_resample, multimodel=False, max_batch=max_batch, precision=precision) as rough:
+        return rough.predict_image(data, affine)
+
+
 def rough_crop_mask(ctx: Context, data, affine: np.ndarray, rough_models, names: Sequence[str], rough_resample: float = 6.0,
                     max_batch: int = 16, precision: Optional[str] = None) -> np.ndarray:
-    """The crop mask of `roi_subset` (TS/python_api.py:705-725): the rough single-model `total` segmentation at `rough_resample` mm,
-    then the union of the `names` structures as a uint8 0 / 1 mask on the input grid."""
-    rough = SegmentationTask(ctx, "total", rough_models, resample=rough_resample, multimodel=False, max_batch=max_batch, precision=precision)
-    try:
-        organ_seg = rough.predict_image(data, affine)
-    finally:
-        rough.close()
+    """The crop mask of `roi_subset` (TS/python_api.py:705-725): of `rough_total`, the union of the `names` structures as a uint8
+    0 / 1 mask on the input grid."""
+    organ_seg = rough_total(ctx, data, affine, rough_models, rough_resample, max_batch=max_batch, precision=precision)
     return np.isin(organ_seg, [label_maps.CLASS_MAP_TOTAL_INV[n] for n in names]).astype(np.uint8)
 
 
@@ -634,26 +672,18 @@ def run_roi_subset(ctx: Context, data, affine: np.ndarray, rough_models, task_mo
         info_out["crop_mask"], info_out["task_ids"] = crop_mask, []
     if crop_mask.sum() == 0:                                      # TS/nnunet.py:428-446: nothing to segment
         return np.zeros(crop_mask.shape, dtype=np.uint8)
-    t = SegmentationTask(ctx, "total", task_models, resample=resample, multimodel=multimodel, max_batch=max_batch, precision=precision)
-    try:
+    with SegmentationTask(ctx, "total", task_models, resample=resample, multimodel=multimodel, max_batch=max_batch, precision=precision) as t:
         if info_out is not None:
             info_out["task_ids"] = [p[0] for p in t.parts]
-        return t.predict_image(data, affine, force_split=force_split, crop_mask=crop_mask, crop_addon=[20, 20, 20],
-                               remove_small_blobs=remove_small_blobs, roi_subset=roi_subset, statistics_out=statistics_out,
-                               model_grid_out=model_grid_out)
-    finally:
-        t.close()
+        return t.predict_roi_subset(data, affine, crop_mask, roi_subset, force_split=force_split, remove_small_blobs=remove_small_blobs,
+                                    statistics_out=statistics_out, model_grid_out=model_grid_out)
 
 
 def body_crop_mask(ctx: Context, data, affine: np.ndarray, body_models, max_batch: int = 16, precision: Optional[str] = None) -> np.ndarray:
     """The rough body segmentation of `body_seg` (TS/python_api.py:739-749): Dataset300 at 6 mm as task `body` with its blob
     post-processing, binarised (`save_binary`, TS/nnunet.py:700-701) -> uint8 0 / 1 mask on the input grid."""
-    body = SegmentationTask(ctx, "body", body_models, resample=6.0, multimodel=False, max_batch=max_batch, precision=precision)
-    try:
-        seg = body.predict_image(data, affine)
-    finally:
-        body.close()
-    return (seg > 0).astype(np.uint8)
+    with SegmentationTask(ctx, "body", body_models, resample=6.0, multimodel=False, max_batch=max_batch, precision=precision) as body:
+        return (body.predict_image(data, affine) > 0).astype(np.uint8)
 
 
 def run_with_body_crop(ctx: Context, task: str, data, affine: np.ndarray, body_models, task_models, resample: Optional[float] = None,
@@ -664,9 +694,6 @@ def run_with_body_crop(ctx: Context, task: str, data, affine: np.ndarray, body_m
     box the result is 0, and an empty body mask gives an all-zero result without running the task's models (the early return of
     `predict_image`).  body_models / task_models: [(task_id, ModelConfig, [weight blob per fold])]."""
     crop_mask = body_crop_mask(ctx, data, affine, body_models, max_batch=max_batch, precision=precision)
-    t = SegmentationTask(ctx, task, task_models, resample=resample, multimodel=multimodel, max_batch=max_batch, precision=precision)
-    try:
+    with SegmentationTask(ctx, task, task_models, resample=resample, multimodel=multimodel, max_batch=max_batch, precision=precision) as t:
         return t.predict_image(data, affine, force_split=force_split, crop_mask=crop_mask, crop_addon=crop_addon,
                                remove_small_blobs=remove_small_blobs)
-    finally:
-        t.close()

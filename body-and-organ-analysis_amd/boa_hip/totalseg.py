@@ -55,15 +55,10 @@ class TotalSegmentatorHip(SegmentationTask):
                 raise ValueError("roi_subset must be a list of strings")
             if rough_models is None:
                 raise ValueError("roi_subset needs the rough `total` model: rough_models=model_store.load_task_models('total_6mm')")
-            selected = label_maps.parts_for_roi_subset(roi_subset)
+            label_maps.parts_for_roi_subset(roi_subset)      # (validates the names before the rough model runs)
             crop_mask = rough_crop_mask(self.ctx, ct_xyz, affine, rough_models, roi_subset, 3.0 if robust else 6.0)
-            every_part = self.parts
-            self.parts = [p for p in every_part if p[0] in selected]      # (the others stay loaded, they just do not run)
-            try:
-                seg = self.predict_image(ct_xyz, affine, force_split=force_split, crop_mask=crop_mask, crop_addon=[20, 20, 20],
-                                         remove_small_blobs=remove_small_blobs, roi_subset=roi_subset)
-            finally:
-                self.parts = every_part
+            # (the parts that do not hold the names stay loaded, they just do not run)
+            seg = self.predict_roi_subset(ct_xyz, affine, crop_mask, roi_subset, force_split=force_split, remove_small_blobs=remove_small_blobs)
         if not statistics:
             return seg
         from . import statistics as st
