@@ -130,6 +130,7 @@ _PROTOS = {
     "boa_nonzero_bbox": (i32, [vp, vp, i32, ip, ip]),
     "boa_resample_cubic": (i32, [vp, vp, i32, ip, vp, i32, ip]),
     "boa_resample_nearest_u8": (i32, [vp, vp, ip, vp, ip]),
+    "boa_resample_onehot_u8": (i32, [vp, vp, ip, vp, ip, i32]),
     "boa_resize_skimage_f32": (i32, [vp, vp, ip, vp, ip, i32, i32]),
     "boa_resize_logits_argmax": (i32, [vp, vp, i32, ip, ip, ip, ip, i32, vp, i32, vp]),
     "boa_logits_to_probabilities": (i32, [vp, vp, i32, ip, ip, ip, ip, i32, ip, ip, ip, vp, vp, vp]),

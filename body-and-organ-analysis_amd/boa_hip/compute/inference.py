@@ -134,6 +134,9 @@ def _segment_one(ctx, name, ct, affine, hdr, folder, fast, recompute, totalsegme
       `statistics` with `statistics_exclude_masks_at_border` (default on), `stats_aggregation` (mean | median) and
           `statistics_normalized_intensities` (TS/python_api.py:636-641,778-796): `statistics.json` next to the label volume, from
           one device pass (`boa_hip/statistics.py`) -- on the input grid, or with `fast` on the model grid (`statistics_fast`);
+      `higher_order_resampling` (every model; TS/python_api.py:104,763 -> TS/nnunet.py:670-683): the labels go back to the input
+          grid by nnU-Net's one-hot order-1 resampling instead of nearest neighbour, in one device pass for all classes
+          (`boa_resample_onehot_u8`); the rough models of `roi_subset`, `body_seg` and the cascade keep nearest;
       `ml`: an explicit False also writes TotalSegmentator's default output, one binary mask file per class of the task (of
           `roi_subset`, where given; TS/nnunet.py:732-734,782-802), into the DIRECTORY `<folder>/<name>/`, binarised and deflated on
           the device from the label volume (`task.write_structure_masks`).  A deviation: the reference puts that directory at
@@ -146,6 +149,7 @@ def _segment_one(ctx, name, ct, affine, hdr, folder, fast, recompute, totalsegme
                                   "TS/nnunet.py:821-827) are not implemented; use ml=True")
     small_blobs, fastest = bool(params.get("remove_small_blobs", False)), bool(params.get("fastest", False))
     body_seg, force_split = bool(params.get("body_seg", False)), bool(params.get("force_split", False))
+    higher_order = bool(params.get("higher_order_resampling", False))
     roi_subset, robust = params.get("roi_subset"), False
     if params.get("roi_subset_robust") is not None:              # TS/python_api.py:655-664
         roi_subset, robust = params["roi_subset_robust"], True
@@ -176,16 +180,19 @@ def _segment_one(ctx, name, ct, affine, hdr, folder, fast, recompute, totalsegme
             rough = "total_fast" if robust else "total_6mm"
             seg = run_roi_subset(ctx, ct, affine, model_store.load_task_models(rough), model_store.load_task_models(key, task_ids=selected),
                                  roi_subset, resample=resample, multimodel=multimodel, rough_resample=model_store.TASKS[rough]["resample"],
-                                 remove_small_blobs=small_blobs, force_split=force_split, statistics_out=stats_fast)
+                                 remove_small_blobs=small_blobs, force_split=force_split, statistics_out=stats_fast,
+                                 higher_order_resampling=higher_order)
             names = {k: v for k, v in names.items() if v in roi_subset}
         elif name == "total" and body_seg:                        # TS/python_api.py:739-764
             if stats_fast is not None:
                 raise NotImplementedError("statistics together with fast and body_seg")
             seg = run_with_body_crop(ctx, "total", ct, affine, model_store.load_task_models("body_fast"), model_store.load_task_models(key),
-                                     resample=resample, multimodel=multimodel, remove_small_blobs=small_blobs)
+                                     resample=resample, multimodel=multimodel, remove_small_blobs=small_blobs,
+                                     higher_order_resampling=higher_order)
         else:
             with SegmentationTask(ctx, name, model_store.load_task_models(key), resample=resample, multimodel=multimodel) as task:
-                seg = task.predict_image(ct, affine, remove_small_blobs=small_blobs, statistics_out=stats_fast)
+                seg = task.predict_image(ct, affine, remove_small_blobs=small_blobs, statistics_out=stats_fast,
+                                         higher_order_resampling=higher_order)
     else:
         if fast:
             raise ValueError(f"task {name} does not work with option --fast")   # TS/python_api.py:242 ff.
@@ -194,7 +201,7 @@ def _segment_one(ctx, name, ct, affine, hdr, folder, fast, recompute, totalsegme
         seg = run_cascade_task(ctx, name, ct, affine, model_store.load_task_models(rough),
                                model_store.load_task_models(name), info["crop"], model_store.effective_crop_addon(name),
                                rough_resample=model_store.TASKS[rough]["resample"], remove_outside=info.get("remove_outside"),
-                               remove_outside_dilation=info.get("remove_outside_dilation"))
+                               remove_outside_dilation=info.get("remove_outside_dilation"), higher_order_resampling=higher_order)
         names = label_maps.class_map(name)
     if want_stats and not fast:                                 # get_basic_statistics(seg, ct_img, ...), TS/python_api.py:778-796
         statistics.basic_statistics(ctx, seg, ct, np.asarray(hdr.get_zooms()[:3], dtype=np.float32), task=name,

@@ -10,9 +10,14 @@
 
 Only the kwargs every nnU-Net v2 planner writes (and the BOA / TotalSegmentator models ship) are implemented:
 resample_data_or_seg_to_shape with is_seg False, order 3 (data) / 1 (probabilities), order_z 0; `force_separate_z` may be
-None, True or False.  Anything else raises instead of silently resampling differently."""
+None, True or False.  Anything else raises instead of silently resampling differently.
+
+  onehot_plan(...)   TotalSegmentator's `higher_order_resampling`: change_spacing(..., target_shape, order=1, nnunet_resample=True)
+                     -> resample_img_nnunet -> resample_patient (TS/resampling.py:79-126,157-205, TS/resample_nnunet.py:46-116) of
+                     the model-grid labels; the arithmetic is `boa_resample_onehot_u8`"""
 from __future__ import annotations
 
+import warnings
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -71,3 +76,41 @@ def slice_axis_for(kw: dict, current_spacing, new_spacing) -> int:
     """-1: one 3-D resize; else the axis that is resampled separately (per-slice 2-D resize + nearest along it)."""
     sep, axis = determine_do_sep_z_and_axis(kw["force_separate_z"], current_spacing, new_spacing)
     return axis if sep else -1
+
+
+def onehot_plan(old_shape: Sequence[int], target_shape: Sequence[int], img_spacing) -> Tuple[bool, Optional[int], Tuple[int, ...]]:
+    """The decisions of change_spacing(img, target_shape=..., nnunet_resample=True) for a label image of `old_shape` (x, y, z) whose
+    header zooms are `img_spacing` (float32, as header.get_zooms() gives them): -> (do_separate_z, axis, new_shape), axis and
+    new_shape in the reference's [z, x, y] order (TS/resampling.py:105-116), axis None unless do_separate_z.
+
+    zoom = target_shape / old_shape, new_spacing = img_spacing / zoom (TS/resampling.py:171-175, dtypes as there: float32 zooms,
+    float64 target spacing); resample_patient(force_separate_z=None): separate z when max / min > 3 on the original spacing, else
+    on the target spacing; the coarse axis from get_lowres_axis, three equal axes -> axis 0, two equal axes -> separate z off with
+    the reference's warning; new_shape = round(original / target * shape) must be the target shape (the reference would fail its
+    shape check after the resampling), else ValueError."""
+    old = np.array([int(v) for v in old_shape])
+    img_spacing = np.array(img_spacing, dtype=np.float32)
+    zoom = np.array([int(v) for v in target_shape]) / old
+    new_spacing = img_spacing / zoom
+    front = lambda l: np.array([l[2], l[0], l[1]])                   # noqa: E731  (move_last_elem_to_front)
+    original_spacing, target_spacing, shape = front(img_spacing), front(new_spacing), front(old)
+    new_shape = np.round((np.array(original_spacing) / np.array(target_spacing)).astype(float) * shape).astype(int)
+    if get_do_separate_z(original_spacing):
+        do_separate_z, axis = True, get_lowres_axis(original_spacing)
+    elif get_do_separate_z(target_spacing):
+        do_separate_z, axis = True, get_lowres_axis(target_spacing)
+    else:
+        do_separate_z, axis = False, None
+    if axis is not None:
+        if len(axis) == 3:
+            axis = (0,)
+        elif len(axis) == 2:
+            warnings.warn(f"axis has len 2, axis: {axis}, spacing: {original_spacing}, target_spacing: {target_spacing}: "
+                          "no separate resampling of the coarse axis")
+            do_separate_z = False
+    want = tuple(int(v) for v in front([int(v) for v in target_shape]))
+    got = tuple(int(v) for v in new_shape)
+    if got != want:
+        raise ValueError(f"higher_order_resampling: the reference's new_shape {got} is not the target shape {want} "
+                         f"(spacing {img_spacing}, shape {tuple(old)})")
+    return bool(do_separate_z), (int(axis[0]) if do_separate_z else None), got

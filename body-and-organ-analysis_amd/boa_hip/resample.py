@@ -35,6 +35,20 @@ def resample_nearest_device(ctx: Context, dev_in: DeviceBuffer, in_shape, out_sh
     return out
 
 
+REF_TO_MEMORY_AXIS = (2, 0, 1)     # axis a of the reference's [z, x, y] order is axis REF_TO_MEMORY_AXIS[a] of an (x, y, z) array
+
+
+def resample_onehot_device(ctx: Context, dev_in: DeviceBuffer, in_shape, out_shape, sep_axis=None):
+    """`higher_order_resampling` (TS/nnunet.py:670-683): nnU-Net's one-hot order-1 resampling of a device-resident uint8 label
+    volume (x, y, z) to `out_shape`.  `sep_axis`: None / -1 for one 3-D resize, else the separately treated axis in the
+    reference's [z, x, y] numbering, as `nnunet_resample.onehot_plan` returns it.  Returns a new DeviceBuffer."""
+    out = DeviceBuffer(ctx, int(np.prod(out_shape)))
+    ax = -1 if sep_axis is None or int(sep_axis) < 0 else REF_TO_MEMORY_AXIS[int(sep_axis)]
+    check(ctx.lib.boa_resample_onehot_u8(ctx.h, dev_in.vp, int3(in_shape), out.vp, int3(out_shape), ax),
+          "boa_resample_onehot_u8")
+    return out
+
+
 def resample_img(ctx: Context, img: np.ndarray, zoom=0.5, order: int = 0, out_dtype=None, target_shape=None):
     """`resample_img(img, zoom, order)` for a 3-D array.  order 3 -> float64 (or int32 with the reference's `.astype`
     truncation when out_dtype=np.int32); order 0 -> uint8 labels.  Other orders are not on the reference's path."""

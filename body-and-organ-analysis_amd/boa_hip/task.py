@@ -365,7 +365,7 @@ class SegmentationTask(contextlib.AbstractContextManager):
                       crop_mask: Optional[np.ndarray] = None, crop_addon=(3, 3, 3), axcodes: str = "RAS",
                       return_device: bool = False, save_probabilities=None, remove_small_blobs: bool = False,
                       model_grid_out: Optional[dict] = None, roi_subset: Optional[Sequence[str]] = None,
-                      statistics_out: Optional[dict] = None):
+                      statistics_out: Optional[dict] = None, higher_order_resampling: bool = False):
         """CT array in file axis order + its affine -> uint8 label array on the same grid.  The volume is uploaded
         once; reorientation, crops, splits and restores are device views / copies, resampling and inference run on the
         device, only the final label volume comes back.  `data` may be a resident DevArray (not freed here);
@@ -397,9 +397,18 @@ class SegmentationTask(contextlib.AbstractContextManager):
         MODEL grid -- the resampled (and cropped) canonical image and the labels after the blob post-processing, before the resample
         back, header zooms those of that grid -- through `statistics.basic_statistics`; `statistics_out["params"]` (optional) holds
         its keyword arguments (exclude_masks_at_border, roi_subset, metric, normalized_intensities, file_out), the result goes to
-        `statistics_out["stats"]`.  Neither is implemented for the sharded modes."""
+        `statistics_out["stats"]`.  Neither is implemented for the sharded modes.
+
+        `higher_order_resampling` (nnUNet_predict_image(nnunet_resampling=True), TS/nnunet.py:670-683): the model-grid labels go
+        back to the input grid by nnU-Net's one-hot resampling instead of nearest neighbour -- every label's 0/1 mask resized with
+        order 1, the label written where the result is >= 0.5, per slice with nearest along the coarse axis on anisotropic grids
+        (`nnunet_resample.onehot_plan` decides as `resample_patient` does) -- in one device pass for all labels
+        (`boa_resample_onehot_u8`).  With `roi_subset` the labels outside the subset are cleared on the model grid BEFORE the
+        resampling as well (:671-674): they interpolate as background.  A task without `resample` is not resampled either way.
+        Not implemented for the sharded modes."""
         if self.shard is not None or self.model_shard is not None:
-            option = ("roi_subset" if roi_subset is not None else "statistics" if statistics_out is not None else
+            option = ("higher_order_resampling" if higher_order_resampling else
+                      "roi_subset" if roi_subset is not None else "statistics" if statistics_out is not None else
                       "save_probabilities" if save_probabilities is not None else
                       "blob post-processing (remove_small_blobs, task body)" if (remove_small_blobs or self.task_name == "body") else None)
             if option is not None:
@@ -424,7 +433,7 @@ class SegmentationTask(contextlib.AbstractContextManager):
             img, spacing, back = self._to_model_grid(sc, data, affine, crop_mask, crop_addon, axcodes)
             seg = self._model_grid_labels(sc, img, spacing, force_split, save_probabilities, remove_small_blobs, model_grid_out,
                                           statistics_out, only)
-            out = self._to_input_grid(sc, seg, back, axcodes, keep_lut)
+            out = self._to_input_grid(sc, seg, back, axcodes, keep_lut, spacing if higher_order_resampling else None)
             if return_device:
                 return sc.release(out.contiguous(force_copy=(resident and out.buf is data.buf)))
             return out.download()
@@ -527,12 +536,22 @@ class SegmentationTask(contextlib.AbstractContextManager):
                 model_grid_out["labels_post"], model_grid_out["ct"] = seg.download(), img_rsp.download()
         return seg
 
-    def _to_input_grid(self, sc: Scope, seg: DevArray, back: "_WayBack", axcodes, keep_lut) -> DevArray:
+    def _to_input_grid(self, sc: Scope, seg: DevArray, back: "_WayBack", axcodes, keep_lut, onehot_spacing=None) -> DevArray:
         """Model-grid labels -> labels on the input grid (views of `seg`, or copies owned by `sc`): nearest resample back, the
-        thickness reorientation and the canonical one undone, undo_crop, the shape check, the `roi_subset` table `keep_lut`."""
+        thickness reorientation and the canonical one undone, undo_crop, the shape check, the `roi_subset` table `keep_lut`.
+        `onehot_spacing` (higher_order_resampling: the model grid's spacing (x, y, z)): nnU-Net's one-hot resampling instead of
+        the nearest one, on the labels `keep_lut` has already filtered."""
         ctx, out = self.ctx, seg
         if back.zoom is not None and tuple(back.in_shape) != tuple(back.ss):      # back to the input grid (TS/nnunet.py:685-687)
-            buf = rs.resample_nearest_device(ctx, seg.buf, back.ss, back.in_shape)
+            if onehot_spacing is None:
+                buf = rs.resample_nearest_device(ctx, seg.buf, back.ss, back.in_shape)
+            else:                                                    # nnunet_resampling, TS/nnunet.py:670-683
+                if keep_lut is not None:                             # (:671-674; `seg` is this call's own array)
+                    check(ctx.lib.boa_label_apply_lut(ctx.h, seg.buf.vp, seg.size, keep_lut.ctypes.data_as(C.c_void_p), seg.buf.vp),
+                          "boa_label_apply_lut")
+                # img_pred's header zooms: the float32 pixdim of the model-grid image
+                _, axis, _ = nr.onehot_plan(back.ss, back.in_shape, np.asarray(onehot_spacing, dtype=np.float32))
+                buf = rs.resample_onehot_device(ctx, seg.buf, back.ss, back.in_shape, axis)
             out = sc.own(DevArray(ctx, buf, back.in_shape, np.uint8))
         if back.thick_ornt is not None:
             # the labels are in `axcodes` order; back to RAS before undo_canonical
@@ -608,19 +627,22 @@ def remove_outside_of_mask(ctx: Context, seg: np.ndarray, mask: np.ndarray, addo
 def run_cascade_task(ctx: Context, task: str, data: np.ndarray, affine: np.ndarray, rough_models, task_models,
                      crop_names: Sequence[str], crop_addon=(3, 3, 3), max_batch: int = 16, rough_resample: float = 6.0,
                      remove_outside: Optional[Sequence[str]] = None, remove_outside_dilation: Optional[float] = None,
-                     precision: Optional[str] = None, save_probabilities=None) -> np.ndarray:
+                     precision: Optional[str] = None, save_probabilities=None, higher_order_resampling: bool = False) -> np.ndarray:
     """Crop-cascade task of `--models all` (TS/python_api.py:670-757): a rough `total` segmentation at 6 mm (single model
     Dataset298; 3 mm / Dataset297 with robust_crop: `rough_resample`), labels = the `total` map -> crop mask = union of the
     `crop_names` structures -> the task's own model at native resolution on the cropped image -> labels on the input grid
     -> optionally cleared outside the dilated union of the `remove_outside` structures (TS/nnunet.py:711-716).
     rough_models / task_models: [(task_id, ModelConfig, [weight blob per fold])] as `model_store.load_task_models` gives.
     `save_probabilities` (a path): passed to the TASK's model (`SegmentationTask.predict_image`: the probabilities of the cropped
-    image's grid); the rough model's are not kept -- in the reference every later model run overwrites the file."""
+    image's grid); the rough model's are not kept -- in the reference every later model run overwrites the file.
+    `higher_order_resampling`: that of `predict_image`, for the task's model (which resamples only if the task has a `resample`
+    spacing; the cascade tasks run at native resolution); the rough model keeps nearest, as in the reference."""
     organ_seg = rough_total(ctx, data, affine, rough_models, rough_resample, max_batch=max_batch, precision=precision)
     inv = label_maps.CLASS_MAP_TOTAL_INV
     crop_mask = np.isin(organ_seg, [inv[n] for n in crop_names]).astype(np.uint8)
     with SegmentationTask(ctx, task, task_models, resample=None, multimodel=False, max_batch=max_batch, precision=precision) as t:
-        seg = t.predict_image(data, affine, crop_mask=crop_mask, crop_addon=crop_addon, save_probabilities=save_probabilities)
+        seg = t.predict_image(data, affine, crop_mask=crop_mask, crop_addon=crop_addon, save_probabilities=save_probabilities,
+                              higher_order_resampling=higher_order_resampling)
     if remove_outside_dilation is not None:
         remove_mask = np.isin(organ_seg, [inv[n] for n in (remove_outside or [])]).astype(np.uint8)
         # header zooms are float32 (nibabel): int(mm / np.mean(img.header.get_zooms()))
@@ -649,7 +671,8 @@ def rough_crop_mask(ctx: Context, data, affine: np.ndarray, rough_models, names:
 def run_roi_subset(ctx: Context, data, affine: np.ndarray, rough_models, task_models, roi_subset: Sequence[str],
                    resample: Optional[float] = 1.5, multimodel: bool = True, rough_resample: float = 6.0, max_batch: int = 16,
                    precision: Optional[str] = None, remove_small_blobs: bool = False, force_split: bool = False,
-                   statistics_out: Optional[dict] = None, model_grid_out: Optional[dict] = None, info_out: Optional[dict] = None) -> np.ndarray:
+                   statistics_out: Optional[dict] = None, model_grid_out: Optional[dict] = None, info_out: Optional[dict] = None,
+                   higher_order_resampling: bool = False) -> np.ndarray:
     """`roi_subset` of task `total` (TS/python_api.py:655-736, TS/nnunet.py:388-390,519-531,707-709): a rough `total` segmentation
     (single model Dataset298 at 6 mm; with `roi_subset_robust` Dataset297 at 3 mm: `rough_models`, `rough_resample`) -> crop mask =
     union of the named structures -> the image cropped to it plus 20 mm -> of the five part models only those whose class map holds
@@ -657,7 +680,8 @@ def run_roi_subset(ctx: Context, data, affine: np.ndarray, rough_models, task_mo
     `model_store.load_task_models(task_ids=...)` need not even have read them), merged in part order -> on the input grid every label
     outside the subset cleared.  `multimodel=False` (`fast`: the single model Dataset297) has no part selection, only crop and filter.
     An empty crop mask gives the all-zero volume without running a part model.  `remove_small_blobs`, `force_split`,
-    `statistics_out` and `model_grid_out` are those of `SegmentationTask.predict_image`; `info_out` (a dict; test seam) gets
+    `statistics_out`, `model_grid_out` and `higher_order_resampling` are those of `SegmentationTask.predict_image` (the task's
+    models only: the rough model keeps nearest, TS/python_api.py:705-722); `info_out` (a dict; test seam) gets
     `task_ids`, the models that were instantiated, and `crop_mask`.  Names outside the class map raise KeyError."""
     roi_subset = list(roi_subset)
     selected = label_maps.parts_for_roi_subset(roi_subset)        # (validates the names also when there is nothing to select)
@@ -676,7 +700,8 @@ def run_roi_subset(ctx: Context, data, affine: np.ndarray, rough_models, task_mo
         if info_out is not None:
             info_out["task_ids"] = [p[0] for p in t.parts]
         return t.predict_roi_subset(data, affine, crop_mask, roi_subset, force_split=force_split, remove_small_blobs=remove_small_blobs,
-                                    statistics_out=statistics_out, model_grid_out=model_grid_out)
+                                    statistics_out=statistics_out, model_grid_out=model_grid_out,
+                                    higher_order_resampling=higher_order_resampling)
 
 
 def body_crop_mask(ctx: Context, data, affine: np.ndarray, body_models, max_batch: int = 16, precision: Optional[str] = None) -> np.ndarray:
@@ -688,12 +713,13 @@ def body_crop_mask(ctx: Context, data, affine: np.ndarray, body_models, max_batc
 
 def run_with_body_crop(ctx: Context, task: str, data, affine: np.ndarray, body_models, task_models, resample: Optional[float] = None,
                        multimodel: Optional[bool] = None, crop_addon=(3, 3, 3), max_batch: int = 16, precision: Optional[str] = None,
-                       remove_small_blobs: bool = False, force_split: bool = False) -> np.ndarray:
+                       remove_small_blobs: bool = False, force_split: bool = False, higher_order_resampling: bool = False) -> np.ndarray:
     """`body_seg=True` (TS/python_api.py:739-764), TotalSegmentator's speed-up for large images: the task runs on the image cropped
     to the bounding box of the rough body mask (`body_crop_mask`) plus `crop_addon` mm (the API's default [3, 3, 3]); outside the
     box the result is 0, and an empty body mask gives an all-zero result without running the task's models (the early return of
-    `predict_image`).  body_models / task_models: [(task_id, ModelConfig, [weight blob per fold])]."""
+    `predict_image`).  body_models / task_models: [(task_id, ModelConfig, [weight blob per fold])].  `higher_order_resampling`:
+    that of `predict_image`, for the task; the body model keeps nearest."""
     crop_mask = body_crop_mask(ctx, data, affine, body_models, max_batch=max_batch, precision=precision)
     with SegmentationTask(ctx, task, task_models, resample=resample, multimodel=multimodel, max_batch=max_batch, precision=precision) as t:
         return t.predict_image(data, affine, force_split=force_split, crop_mask=crop_mask, crop_addon=crop_addon,
-                               remove_small_blobs=remove_small_blobs)
+                               remove_small_blobs=remove_small_blobs, higher_order_resampling=higher_order_resampling)

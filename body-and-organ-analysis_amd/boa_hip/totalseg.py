@@ -34,14 +34,16 @@ class TotalSegmentatorHip(SegmentationTask):
     def predict(self, ct_xyz: np.ndarray, spacing_xyz=(1.5, 1.5, 1.5), affine=None, force_split: bool = False,
                 roi_subset=None, roi_subset_robust=None, rough_models=None, remove_small_blobs: bool = False,
                 statistics: bool = False, statistics_exclude_masks_at_border: bool = True, stats_aggregation: str = "mean",
-                statistics_normalized_intensities: bool = False):
+                statistics_normalized_intensities: bool = False, higher_order_resampling: bool = False):
         """(x,y,z) CT in RAS+ order with `spacing_xyz` (or any axis order with an explicit `affine`) -> the `total` label volume.
 
         The TotalSegmentator keywords of `compute_all_models` (TS/python_api.py:636-664,778-796):
         `roi_subset` / `roi_subset_robust` (a list of structure names): `rough_models` -- the single rough `total` model, Dataset298
         at 6 mm, for `roi_subset_robust` Dataset297 at 3 mm, as `model_store.load_task_models` gives it -- makes the crop mask, only
         the parts that hold the names run on the crop (+ 20 mm), only their labels are kept; `statistics`: returns
-        (labels, get_basic_statistics dict of the labels and the CT on the input grid) instead of the labels."""
+        (labels, get_basic_statistics dict of the labels and the CT on the input grid) instead of the labels;
+        `higher_order_resampling`: the labels go back to the input grid by nnU-Net's one-hot order-1 resampling instead of nearest
+        neighbour (`SegmentationTask.predict_image`; the rough model of `roi_subset` keeps nearest)."""
         from . import label_maps, orientation
         if affine is None:
             affine = np.diag([float(spacing_xyz[0]), float(spacing_xyz[1]), float(spacing_xyz[2]), 1.0])
@@ -49,7 +51,8 @@ class TotalSegmentatorHip(SegmentationTask):
         if robust:
             roi_subset = roi_subset_robust
         if roi_subset is None:
-            seg = self.predict_image(ct_xyz, affine, force_split=force_split, remove_small_blobs=remove_small_blobs)
+            seg = self.predict_image(ct_xyz, affine, force_split=force_split, remove_small_blobs=remove_small_blobs,
+                                     higher_order_resampling=higher_order_resampling)
         else:
             if type(roi_subset) is not list:
                 raise ValueError("roi_subset must be a list of strings")
@@ -58,7 +61,8 @@ class TotalSegmentatorHip(SegmentationTask):
             label_maps.parts_for_roi_subset(roi_subset)      # (validates the names before the rough model runs)
             crop_mask = rough_crop_mask(self.ctx, ct_xyz, affine, rough_models, roi_subset, 3.0 if robust else 6.0)
             # (the parts that do not hold the names stay loaded, they just do not run)
-            seg = self.predict_roi_subset(ct_xyz, affine, crop_mask, roi_subset, force_split=force_split, remove_small_blobs=remove_small_blobs)
+            seg = self.predict_roi_subset(ct_xyz, affine, crop_mask, roi_subset, force_split=force_split, remove_small_blobs=remove_small_blobs,
+                                          higher_order_resampling=higher_order_resampling)
         if not statistics:
             return seg
         from . import statistics as st

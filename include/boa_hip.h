@@ -570,6 +570,24 @@ int boa_resample_cubic(boa_ctx* ctx, const void* dev_in, int in_dtype, const int
 /* order 0 (labels back to the original grid, TS/nnunet.py:685-687): index floor(out * (n_in-1)/(n_out-1) + 0.5). */
 int boa_resample_nearest_u8(boa_ctx* ctx, const uint8_t* dev_in, const int in_dims[3], uint8_t* dev_out,
                             const int out_dims[3]);
+/* higher_order_resampling (labels back to the original grid with nnunet_resample=True, TS/nnunet.py:670-683 ->
+ * TS/resample_nnunet.py:11-33,119-205): nnU-Net's one-hot resampling of a label volume in one pass.  The reference resizes the
+ * 0/1 mask of every label with order 1 (skimage.transform.resize(mode="edge", anti_aliasing=False), restated as for
+ * boa_resize_skimage_f32: scipy.ndimage.zoom(grid_mode=True, mode="nearest"), fp64) and writes the label where the result is
+ * >= 0.5, labels ascending, later ones overwriting.  Here every output voxel gathers its (at most) 8 taps, sums per distinct
+ * label the fp64 tap weights 1.0 * w * w * w in scipy's tap order and keeps the LARGEST label whose sum is >= 0.5, else 0 -- the
+ * same fp64 values, so exact ties at 0.5 (integer zoom factors) decide as in the reference.  Bit-identical to the per-label loop
+ * (tests/onehot_reference.py) for any number of labels.
+ *   dev_in / dev_out  uint8 [d0][d1][d2], d2 fastest: (x, y, z) of the model-grid / input-grid image.  The reference works on the
+ *                     transposed array [z, x, y] (TS/resampling.py:105-125); the taps are visited in ITS axis order (d2 outermost,
+ *                     then d0, then d1).  in_dims / out_dims and sep_axis number the axes in memory order.
+ *   sep_axis          -1: one 3-D resize.  0..2 ("separate z"): every slice along that axis is resized in 2-D (4 taps) and the
+ *                     axis itself is sampled nearest, floor(cc + 0.5) clamped (map_coordinates order 0); the identity when its
+ *                     extent does not change.
+ * in_dims == out_dims copies ("no resampling necessary").  dev_in and dev_out must not alias.  Asynchronous on the context's
+ * stream (its table of d0 + d1 output entries comes from and goes back to the context's pool). */
+int boa_resample_onehot_u8(boa_ctx* ctx, const uint8_t* dev_in, const int in_dims[3], uint8_t* dev_out, const int out_dims[3],
+                           int sep_axis);
 
 
 /* ------------------------------------------------------------------ nnU-Net's own resampling to / from the plans' spacing --- */
