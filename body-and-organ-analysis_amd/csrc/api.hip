@@ -54,7 +54,7 @@ extern "C" void boa_destroy(boa_ctx* c) {
     }
     for (auto& r : c->prof_pending) hipEventDestroy(r.ev);
     for (auto e : c->ev_pool) hipEventDestroy(e);
-    for (auto& r : c->ws_runs) hipFree(r.second);
+    conv_sched_destroy(c);
     for (auto& b : c->pool_free) hipFree(b.second);
     for (auto& b : c->pool_live) hipFree(b.first);  // buffers the caller never freed
     if (c->stash) hipFree(c->stash);
@@ -84,7 +84,7 @@ int boa_malloc_raw(boa_ctx* c, size_t bytes, void** dev_out) {
     BOA_HIP_TRY(hipSetDevice(c->device));
     void* p = nullptr;
     hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
-    if (e != hipSuccess && (c->pool_bytes || (c->stash && !c->stash_busy))) {  // give the parked blocks (and an idle tile stash) back and try once more
+    if (e != hipSuccess && (c->pool_bytes || (c->stash && !c->stash_busy) || conv_sched_desc_bytes(c))) {  // give the parked blocks (an idle tile stash, the convs' descriptor tables) back and try once more
         (void)hipGetLastError();
         boa_trim(c);
         e = hipMalloc(&p, bytes ? bytes : 1);
@@ -175,17 +175,9 @@ static int trim_locked(boa_ctx* c) {
     // the other lane's context, torch / RCCL buffers, a post-processing volume whose hipMalloc failed -- and the next volume's
     // tile loop re-allocates it (or falls back to the scatter form if it no longer fits)
     const bool drop_stash = c->stash && !c->stash_busy;
-    if (c->pool_free.empty() && !drop_stash && c->ws_desc_bytes == 0) return BOA_OK;
+    if (c->pool_free.empty() && !drop_stash && conv_sched_desc_bytes(c) == 0) return BOA_OK;
     BOA_HIP_TRY(hipStreamSynchronize(c->stream));
-    // the conv kernels' tile descriptor tables (one per layer geometry, batch and grid: the tail batches of differently sized volumes keep
-    // adding some) are rebuilt on their next use -- one small kernel each; the run tables (per layer geometry only) stay
-    for (size_t i = c->ws_runs.size(); i-- > 0;)
-        if (!c->ws_runs[i].first.empty() && c->ws_runs[i].first[0] == -1) {
-            hipFree(c->ws_runs[i].second);
-            c->ws_runs.erase(c->ws_runs.begin() + i);
-            c->ws_runs_host.erase(c->ws_runs_host.begin() + i);
-        }
-    c->ws_desc_bytes = 0;
+    conv_sched_release_desc(c);  // rebuilt on their next use -- one small kernel each
     for (auto& b : c->pool_free) hipFree(b.second);
     c->pool_free.clear();
     c->pool_bytes = 0;

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "boa_hip.h"
+#include "conv_sched.h"
 
 void boa_set_error(const char* fmt, ...);
 
@@ -61,11 +62,7 @@ struct boa_ctx {
     double prof_flops[BOA_K_COUNT] = {};
     double prof_bytes[BOA_K_COUNT] = {};
     long long counters[BOA_CNT_COUNT] = {};  // launches per kernel variant (boa_debug_counter)
-    // k_conv_ws run tables (first tile + length of every virtual workgroup's run), one per distinct layer geometry,
-    // built on first use and kept for the life of the context: (key, device pointer)
-    std::vector<std::pair<std::vector<int>, void*>> ws_runs;
-    std::vector<std::vector<int>> ws_runs_host;   // parallel to ws_runs: the host copy of a run table (empty for descriptor tables)
-    size_t ws_desc_bytes = 0;                     // bytes of the per-launch descriptor tables (key[0] == -1); boa_trim releases them
+    ConvSchedTables sched;  // run and descriptor tables of k_conv_ws / k_conv_ns, built on first use (conv_sched.hip)
     // boa_malloc / boa_free: stream-ordered caching allocator for the transient volume-sized buffers of the host code
     // (a freed block goes back to `pool_free` without a device synchronisation and is handed out again for a request of
     // about its size; every use of a block is enqueued on `stream`, so reuse is ordered).  Network activations and weight
@@ -86,6 +83,10 @@ struct boa_ctx {
     unsigned long long act_gen = 0;
 };
 int boa_malloc_raw(boa_ctx* c, size_t bytes, void** dev_out);
+// conv_sched.hip: bytes of descriptor tables held; release them (the stream is idle: boa_trim); release every table (boa_destroy)
+size_t conv_sched_desc_bytes(const boa_ctx* c);
+void conv_sched_release_desc(boa_ctx* c);
+void conv_sched_destroy(boa_ctx* c);
 
 // RAII-less explicit bracket: KernelTimer t(ctx, klass, flops, bytes); <launch>; t.stop();
 struct KernelTimer {

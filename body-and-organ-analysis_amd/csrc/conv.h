@@ -57,8 +57,7 @@ void pack_convt_weights(const float* w /*[Cin][Cout][s0][s1][s2]*/, int Cin, int
 // sums of (x, x^2) per (n, cout) into partials[N][Cout][2][nblk]; returns nblk through *nblk_out.
 int launch_conv_mfma(boa_ctx* ctx, const ActSrc& s0, const ActSrc& s1, const ConvGeom& g, const ConvTile& t,
                      const __half* wpk, const float* bias, float slope, __half* out, float* partials);
-int conv_nblk(const ConvTile& t, int cu_count, int Cout);
-int conv_ws_nslots(int tiles_per_sample, int cu_count);
+int conv_nblk(const ConvTile& t, int cu_count, int Cout);   // (k_conv_ws / k_conv_ns: conv_ws_nslots, conv_sched.h)
 // split-precision conv (k_conv_ws<..., X3>): fp32 octet-planar sources / output, fp32 (scale, shift) tables
 int launch_conv_x3(boa_ctx* ctx, const float* src0, const float* ss0, int C0, const float* src1, const float* ss1, int C1,
                    const ConvGeom& g, const ConvTile& t, const __half* wpk, float wscale, const float* bias, float slope, float* out,
@@ -80,7 +79,6 @@ bool conv_ws_row_reuse(int R, int k1, int s1, int w1, int b1, int b2);
 bool conv_ws_cy_fast(int c_units, int Cout, int R);
 bool conv_ws_supported(const int k[3], int HV);
 bool conv_ws_resident(int HV, int taps, int ncc, int Cout);
-int conv_ws_vw(int tiles_per_sample, int cu_count);
 int conv_ns_wn(int Cout);
 int convt_mfma_form(int Cin, const int s[3], bool norm_src);
 int convt_x3_mt(size_t vin);
@@ -154,6 +152,23 @@ __device__ __forceinline__ uint4 norm_act8(uint4 raw, const float* sc, const flo
     }
     return x.u;
 }
+
+// ---- conv_sched.hip: the tile schedule of a k_conv_ws / k_conv_ns launch (arithmetic and table types: conv_sched.h) -----------------------
+struct ConvSched {
+    int grid;          // physical workgroups
+    const int* desc;   // descriptor table [grid][desc_row][8] (conv_ws_dev.h), built on ctx->stream ahead of the launch on first use
+    int desc_row;
+    int dbg;           // BOA_WS_DBG (traced build: stage ablation), read once per process
+};
+// Fills a.nslots / vw / vstep_* / runs / trace from a.ncy, a.cy_fast and the geometry already in `a`, checks the limits the shared
+// producer code has (24-bit voxel offsets, 32-bit byte offsets) and looks up or builds the launch's tables.  `what` names the kernel in errors.
+int conv_sched_prepare(boa_ctx* ctx, ConvArgs& a, int tiles_per_sample, const char* what, ConvSched* out);
+#ifdef WS_WITH_TRACE
+// BOA_WS_TRACE (armed by conv_sched_prepare): waits for the launch, prints the stamps ([ws-trace], R >= 1; [ns-trace], R = 0), frees the buffer
+void conv_sched_trace_dump(boa_ctx* ctx, const ConvArgs& a, const ConvSched& s, int tiles_per_sample, int R);
+#else
+static inline void conv_sched_trace_dump(boa_ctx*, const ConvArgs&, const ConvSched&, int, int) {}
+#endif
 
 int launch_conv_ws(boa_ctx* ctx, const ConvArgs& a, const ConvTile& t, double flops, double bytes, bool x3 = false);
 // fused gather head (head_gather.hip): all covering tiles of a voxel -> label, from the stash of last decoder activations

@@ -285,7 +285,7 @@ __global__ __launch_bounds__(WS_THREADS) void k_conv_ns(ConvArgs p, int dbg_arg,
     const int buf_bytes = 2 * plane;  // LDS: [halo buf 0][halo buf 1], each two k-octet planes
     unsigned char* bufs = smem;
 
-    // this workgroup's row of the launch's descriptor table (k_ws_build_desc, conv_ws.hip): entry 0 = its tile count, entry 1 + k =
+    // this workgroup's row of the launch's descriptor table (k_ws_build_desc, conv_sched.hip): entry 0 = its tile count, entry 1 + k =
     // its k-th tile; each role reads one 32-byte descriptor per tile with scalar loads instead of walking the run tables
     const int* __restrict__ drow = desc + (size_t)blockIdx.x * desc_row * 8;
     const int my_tiles = drow[0];
@@ -631,10 +631,6 @@ __global__ __launch_bounds__(WS_THREADS) void k_conv_ns(ConvArgs p, int dbg_arg,
 }
 
 // ---- host side ---------------------------------------------------------------------------------------
-const int* ws_run_table(boa_ctx* ctx, const ConvArgs& a, int tiles_per_sample, int vw);
-const int* ws_desc_table(boa_ctx* ctx, const ConvArgs& a, int tiles_per_sample, int grid, int* row_out);
-int conv_ws_vw(int tiles_per_sample, int cu_count);
-
 // The layers k_conv_ns takes (a function of the layer geometry only): 3x3x3 kernels with stride 2 on all axes, at least two cout
 // chunks and an output of at least 8^3 voxels -- measured per layer against k_conv_ws on the `total` geometry (8 tiles): 32 -> 64
 // @128^3, 64 -> 128 @64^3 453 -> 194 us, 128 -> 256 @32^3 224 -> 96 us, 256 -> 320 @16^3 114 -> 81 us.  The stride-1 layers with
@@ -670,73 +666,35 @@ void conv_ns_tile(const ConvGeom& g, ConvTile* t) {
 int conv_ns_ncy(int Cout) { return (Cout / 32 + ns_wn(Cout) - 1) / ns_wn(Cout); }
 
 template <int S, int WN, int RM, bool X3 = false>
-static void launch_ns(boa_ctx* ctx, const ConvArgs& a, const ConvTile& t, int grid, const int* desc, int desc_row) {
+static void launch_ns(boa_ctx* ctx, const ConvArgs& a, const ConvTile& t, const ConvSched& s) {
     static bool once = (hipFuncSetAttribute((const void*)k_conv_ns<S, WN, RM, X3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), true);
     (void)once;
-    hipLaunchKernelGGL((k_conv_ns<S, WN, RM, X3>), dim3(grid), dim3(WS_THREADS), t.lds_bytes, ctx->stream, a,
-                       getenv("BOA_WS_DBG") ? atoi(getenv("BOA_WS_DBG")) : 0, desc, desc_row);
+    hipLaunchKernelGGL((k_conv_ns<S, WN, RM, X3>), dim3(s.grid), dim3(WS_THREADS), t.lds_bytes, ctx->stream, a, s.dbg, s.desc, s.desc_row);
 }
 
 int launch_conv_ns(boa_ctx* ctx, const ConvArgs& a_in, const ConvTile& t, double flops, double bytes, bool x3) {
     ConvArgs a = a_in;
     a.ncy = conv_ns_ncy(a.Cout);
+    a.cy_fast = 0;
     const int total = t.tiles[0] * t.tiles[1] * t.tiles[2] * a.ncy;  // tiles of one sample
-    const int vw = conv_ws_vw(total, ctx->cu_count);
-    const int grid = (int)std::min<long long>((long long)vw * a.N, ctx->cu_count);
-    BOA_REQUIRE((double)a.Di * a.Hi * a.Wi <= 16777216.0, "conv_ns: more than 2^24 input voxels per sample (24-bit offset multiply)");
-    BOA_REQUIRE((double)a.Di * a.Hi * a.Wi * std::max(a.C0, a.C1) * 2.0 < 4294967296.0,
-                "conv_ns: one sample of the input exceeds 4 GiB (32-bit voxel offsets)");
     BOA_REQUIRE(t.h[0] == 9 && t.h[1] == 9 && t.h[2] == 17 && a.h0 * a.h1 * a.h2 == NS_HV && a.xs == a.h1 * a.h2,
                 "conv_ns: the producers are unrolled for the 9 x 9 x 17 halo");
-#ifdef WS_WITH_TRACE
-    static const bool want_trace = getenv("BOA_WS_TRACE") != nullptr;
-#else
-    static const bool want_trace = false;   // (the stamps are compiled out of the production build: conv_ws_dev.h)
-#endif
-    a.trace = nullptr;
-    if (want_trace) {
-        hipMalloc(&a.trace, WS_TRACE_SLOTS * 8);
-        hipMemsetAsync(a.trace, 0, WS_TRACE_SLOTS * 8, ctx->stream);
-        const unsigned long long blk = (unsigned long long)std::min(std::max(atoi(getenv("BOA_WS_TRACE")), 0), grid - 1);
-        hipMemcpyAsync(a.trace + WS_TRACE_SLOTS - 5, &blk, 8, hipMemcpyHostToDevice, ctx->stream);
-    }
-    a.nslots = 4 * vw;
-    a.vw = vw;
-    a.vstep_n = grid / vw;
-    a.vstep_j = grid % vw;
-    a.cy_fast = 0;
-    a.runs = ws_run_table(ctx, a, total, vw);
-    BOA_REQUIRE(a.runs != nullptr, "conv_ns: could not allocate the run table");
-    int desc_row = 0;
-    const int* desc = ws_desc_table(ctx, a, total, grid, &desc_row);
-    BOA_REQUIRE(desc != nullptr, "conv_ns: could not allocate the tile descriptor table");
+    BOA_REQUIRE(a.s0 == 2, "conv_ns: instantiated for stride 2 only");
+    ConvSched s;
+    BOA_TRY(conv_sched_prepare(ctx, a, total, "conv_ns", &s));
     KernelTimer tm(ctx, BOA_K_CONV_MFMA, flops, bytes);
     ctx->counters[x3 ? BOA_CNT_CONV_X3 : BOA_CNT_CONV_WS]++;
-    BOA_REQUIRE(a.s0 == 2, "conv_ns: instantiated for stride 2 only");
     if (x3) {
         if (ns_wn(a.Cout) == 2)
-            launch_ns<2, 2, 2, true>(ctx, a, t, grid, desc, desc_row);
+            launch_ns<2, 2, 2, true>(ctx, a, t, s);
         else
-            launch_ns<2, 4, 4, true>(ctx, a, t, grid, desc, desc_row);
+            launch_ns<2, 4, 4, true>(ctx, a, t, s);
     } else if (ns_wn(a.Cout) == 2)
-        launch_ns<2, 2, 2>(ctx, a, t, grid, desc, desc_row);
+        launch_ns<2, 2, 2>(ctx, a, t, s);
     else
-        launch_ns<2, 4, 4>(ctx, a, t, grid, desc, desc_row);
+        launch_ns<2, 4, 4>(ctx, a, t, s);
     tm.stop();
-    if (want_trace && a.trace) {
-        static unsigned long long host[WS_TRACE_SLOTS];
-        hipStreamSynchronize(ctx->stream);
-        hipMemcpy(host, a.trace, sizeof(host), hipMemcpyDeviceToHost);
-        hipFree(a.trace);
-        fprintf(stderr, "[ns-trace] Cin=%d Cout=%d in=%d s=%d:", a.C0 + a.C1, a.Cout, a.Di, a.s0);
-        for (int i = 1; i < 80 && host[i]; ++i)
-            fprintf(stderr, " %d:%llu", (int)(host[i] >> 56), (host[i] & 0x00ffffffffffffffull) - (host[i - 1] & 0x00ffffffffffffffull));
-        fprintf(stderr, "\n[ns-trace] producer:");
-        const unsigned long long* hp = host + WS_TRACE_SLOTS / 2;
-        for (int i = 41; i < 110 && hp[i]; ++i)
-            fprintf(stderr, " %d:%llu", (int)(hp[i] >> 56), (hp[i] & 0x00ffffffffffffffull) - (hp[i - 1] & 0x00ffffffffffffffull));
-        fprintf(stderr, "\n");
-    }
+    conv_sched_trace_dump(ctx, a, s, total, 0);
     BOA_HIP_TRY(hipGetLastError());
     return BOA_OK;
 }

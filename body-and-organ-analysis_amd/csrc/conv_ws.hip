@@ -13,7 +13,7 @@
 // 2-chunk / 2-cout-chunk case, where the staged halo is reused), so the staging of a tile's first chunk hides under
 // the previous tile's last chunk and the chip-wide working set is a contiguous run of tiles (halo reuse in L2).
 // Per-tile bookkeeping is ONE scalar load per role: the tile sequence of every workgroup (conv_ws_dev.h: virtual workgroups, run
-// tables) is walked once per (layer geometry, batch, grid) by k_ws_build_desc below into a table of 32-byte descriptors (tile
+// tables) is walked once per (layer geometry, batch, grid) by k_ws_build_desc (conv_sched.hip) into a table of 32-byte descriptors (tile
 // coordinates, statistics slot, halo class and faces, output offset).  A role is a single wave per SIMD: it issues an instruction
 // every ~4.7 cycles and pays ~25 cycles per SGPR-spill reload and ~22 per taken branch (tools/issue_rate.hip), so what the role
 // loops carry per tile -- not the MFMA pipe -- sets the tile time (profiles/r05_conv_ws_experiments.txt).
@@ -21,8 +21,9 @@
 // Same arithmetic as k_conv_mfma (conv.hip).  Statistics: partials[n][cout][2][nslots], one slot per (workgroup,
 // consumer wave), written once per (sample, cout chunk) a wave works on; the table is zero elsewhere (zeroed at
 // allocation, re-zeroed by k_norm_finalize).
-// Debug (TRACED build only, -DWS_WITH_TRACE: tools/build_alt.sh trace -DWS_WITH_TRACE; the production build compiles both out of the
-// role loops): `dbg` bits (BOA_WS_DBG) skip stages for ablation -- 2 producers, 4 output stores, 8 epilogue, 16 weight staging,
+// Debug (tools/build_alt.sh trace -DWS_WITH_TRACE; the launchers pass `dbg` and `p.trace` in every build, the production build ignores
+// both: `dbg` is a compile-time zero in the role loops and the stamps are empty): `dbg` bits (BOA_WS_DBG) skip stages for ablation --
+// 2 producers, 4 output stores, 8 epilogue, 16 weight staging,
 // 32 halo commit, 64 transform, 128 halo loads, 256 / 1024 default wave priorities off, 2048 producers first, 4096 consumers without
 // fragment reads and MFMAs; results are then wrong by design (except the priority bits).
 // BOA_WS_TRACE=<block> records s_memtime stamps of that workgroup (consumer wave 0: 4 chunk start, 5 MFMA loop done, 6 before the
@@ -32,30 +33,6 @@
 
 #include "conv.h"
 #include "conv_ws_dev.h"
-
-// Builds the descriptor rows of a launch: thread b walks physical workgroup b's tile sequence with the kernels' own code.
-__global__ __launch_bounds__(64) void k_ws_build_desc(ConvArgs p, int grid, int row, int* __restrict__ out) {
-    const int b = (int)blockIdx.x * 64 + (int)threadIdx.x;
-    if (b >= grid) return;
-    int* r = out + (size_t)b * row * 8;
-    int my = 0;
-    for (int v = b; v < p.N * p.vw; v += grid) my += p.runs[(v % p.vw) * 8];
-    if (my > row - 1) my = row - 1;   // (unreachable: ws_desc_table checks every workgroup's tile count against the row length on the host before the launch)
-    r[0] = my;
-    for (int i = 1; i < 8; ++i) r[i] = 0;
-    TileSeq s;
-    s.n = s.left = s.j = 0;
-    for (int k = 0; k < my; ++k) {
-        bool new_run = true;
-        if (k == 0)
-            seq_first_of(p, s, b);
-        else
-            new_run = seq_next(p, s);
-        const TileDesc d = make_desc(p, s, new_run);
-        int* e = r + (size_t)(k + 1) * 8;
-        e[0] = d.tc.n; e[1] = d.tc.cy; e[2] = d.tc.ox0; e[3] = d.tc.oy0; e[4] = d.tc.oz0; e[5] = d.flags; e[6] = d.vo; e[7] = d.ibase;
-    }
-}
 
 // ---- consumer ----------------------------------------------------------------------------------------
 // One 16-channel chunk: acc[r] += W[tap] x X[tap][r] for all taps.  bp[r]: LDS address of this lane's voxel of
@@ -853,12 +830,6 @@ size_t conv_ws_lds_bytes(int HV, int taps, int ncc, int Cout) {
     return 2 * (2 * ws_plane_host(HV) + (size_t)taps * 1024);
 }
 
-// virtual workgroups per sample (a function of the layer geometry only) and the statistics slots of a layer: one per (virtual
-// workgroup, consumer wave) -- sized per layer, so that k_norm_finalize reads and re-zeroes 4 vw entries per (n, cout), not 4 x CUs
-// (the deep layers have 10-64 tiles per sample)
-int conv_ws_vw(int tiles_per_sample, int cu_count) { return std::min(tiles_per_sample, cu_count); }
-int conv_ws_nslots(int tiles_per_sample, int cu_count) { return conv_ws_vw(tiles_per_sample, cu_count) * 4; }
-
 bool conv_ws_supported(const int k[3], int HV) {
     const bool k333 = k[0] == 3 && k[1] == 3 && k[2] == 3;
     const bool k133 = k[0] == 1 && k[1] == 3 && k[2] == 3;
@@ -866,11 +837,11 @@ bool conv_ws_supported(const int k[3], int HV) {
 }
 
 template <int R, int K0, int K1, int K2, bool YR, bool X3>
-static void launch_ws_y(boa_ctx* ctx, const ConvArgs& a, const ConvTile& t, int total, int grid, int resident, const int* desc, int desc_row) {
+static void launch_ws_y(boa_ctx* ctx, const ConvArgs& a, const ConvTile& t, int total, int resident, const ConvSched& s) {
     static bool once = (hipFuncSetAttribute((const void*)k_conv_ws<R, K0, K1, K2, YR, X3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), true);
     (void)once;
-    hipLaunchKernelGGL((k_conv_ws<R, K0, K1, K2, YR, X3>), dim3(grid), dim3(WS_THREADS), t.lds_bytes + 2048, ctx->stream, a, total, resident,
-                       getenv("BOA_WS_DBG") ? atoi(getenv("BOA_WS_DBG")) : 0, desc, desc_row);
+    hipLaunchKernelGGL((k_conv_ws<R, K0, K1, K2, YR, X3>), dim3(s.grid), dim3(WS_THREADS), t.lds_bytes + 2048, ctx->stream, a, total, resident, s.dbg,
+                       s.desc, s.desc_row);
 }
 
 bool conv_ws_row_reuse(int R, int k1, int s1, int w1, int b1, int b2) {
@@ -881,22 +852,22 @@ bool conv_ws_row_reuse(int R, int k1, int s1, int w1, int b1, int b2) {
 bool conv_ws_cy_fast(int c_units, int Cout, int R) { return c_units == 32 && Cout == 64 && R == 1; }
 
 template <int R, int K0, int K1, int K2, bool X3>
-static void launch_ws_t(boa_ctx* ctx, const ConvArgs& a, const ConvTile& t, int total, int grid, int resident, const int* desc, int desc_row) {
+static void launch_ws_t(boa_ctx* ctx, const ConvArgs& a, const ConvTile& t, int total, int resident, const ConvSched& s) {
     // row reuse: the R M-tiles of a wave are consecutive output rows (m = cw * R + r, my = m & (b1 - 1) when b2 == 1),
     // one voxel high, stride 1 along y
     const bool yr = conv_ws_row_reuse(R, K1, a.s1, a.w1, a.b1, a.b2);
     if (R > 1 && yr)
-        launch_ws_y<R, K0, K1, K2, (R > 1), X3>(ctx, a, t, total, grid, resident, desc, desc_row);
+        launch_ws_y<R, K0, K1, K2, (R > 1), X3>(ctx, a, t, total, resident, s);
     else
-        launch_ws_y<R, K0, K1, K2, false, X3>(ctx, a, t, total, grid, resident, desc, desc_row);
+        launch_ws_y<R, K0, K1, K2, false, X3>(ctx, a, t, total, resident, s);
 }
 
 template <int R, bool X3>
-static int launch_ws_r(boa_ctx* ctx, const ConvArgs& a, const ConvTile& t, int total, int grid, int resident, const int* desc, int desc_row) {
+static int launch_ws_r(boa_ctx* ctx, const ConvArgs& a, const ConvTile& t, int total, int resident, const ConvSched& s) {
     if (a.k0 == 3 && a.k1 == 3 && a.k2 == 3)
-        launch_ws_t<R, 3, 3, 3, X3>(ctx, a, t, total, grid, resident, desc, desc_row);
+        launch_ws_t<R, 3, 3, 3, X3>(ctx, a, t, total, resident, s);
     else if (a.k0 == 1 && a.k1 == 3 && a.k2 == 3)
-        launch_ws_t<R, 1, 3, 3, X3>(ctx, a, t, total, grid, resident, desc, desc_row);
+        launch_ws_t<R, 1, 3, 3, X3>(ctx, a, t, total, resident, s);
     else {
         boa_set_error("conv_ws: kernel %dx%dx%d not instantiated", a.k0, a.k1, a.k2);
         return BOA_EINVAL;
@@ -904,174 +875,33 @@ static int launch_ws_r(boa_ctx* ctx, const ConvArgs& a, const ConvTile& t, int t
     return BOA_OK;
 }
 
-// Run table of a layer: the tiles of ONE sample (decode_tile's order) cut into vw contiguous runs, 8 XCD ranges first
-// (virtual workgroup j <-> XCD j % 8) and then the virtual workgroups of an XCD; entry j = {count, cy, sp, ox0, oy0, oz0}
-// of the run's first tile.  A function of the layer geometry only (never of the batch size).
-const int* ws_run_table(boa_ctx* ctx, const ConvArgs& a, int tiles_per_sample, int vw) {
-    std::vector<int> key = {a.t0, a.t1, a.t2, a.b0, a.b1, a.b2, a.w0, a.w1, a.w2, a.Cout, a.cy_fast, vw, a.ncy};
-    for (auto& e : ctx->ws_runs)
-        if (e.first == key) return (const int*)e.second;
-    std::vector<int> tab((size_t)vw * 8, 0);
-    const int nsp = a.t0 * a.t1 * a.t2, ncy = a.ncy;
-    for (int j = 0; j < vw; ++j) {
-        int first, count;
-        if (vw % 8 != 0) {
-            const int q = tiles_per_sample / vw, r = tiles_per_sample % vw;
-            first = j * q + std::min(j, r);
-            count = q + (j < r ? 1 : 0);
-        } else {
-            const int xcd = j & 7, slot = j >> 3, per = vw >> 3;
-            const int q = tiles_per_sample / 8, rem = tiles_per_sample % 8;
-            const int lo = xcd * q + std::min(xcd, rem), len = q + (xcd < rem ? 1 : 0);
-            const int cq = len / per, cr = len % per;
-            first = lo + slot * cq + std::min(slot, cr);
-            count = cq + (slot < cr ? 1 : 0);
-        }
-        int cy, sp;
-        if (a.cy_fast) {
-            cy = first % ncy;
-            sp = first / ncy;
-        } else {
-            sp = first % nsp;
-            cy = first / nsp;
-        }
-        int bt = sp;
-        const int tx = bt % a.t0;
-        bt /= a.t0;
-        const int tz = bt % a.t2, ty = bt / a.t2;
-        int* e = &tab[(size_t)j * 8];
-        e[0] = count; e[1] = cy; e[2] = sp; e[3] = tx * a.b0 * a.w0; e[4] = ty * a.b1 * a.w1; e[5] = tz * a.b2 * a.w2;
-    }
-    void* dev = nullptr;
-    if (hipMalloc(&dev, tab.size() * sizeof(int)) != hipSuccess) return nullptr;
-    if (hipMemcpy(dev, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-        hipFree(dev);
-        return nullptr;
-    }
-    ctx->ws_runs.emplace_back(std::move(key), dev);
-    ctx->ws_runs_host.emplace_back(std::move(tab));
-    return (const int*)dev;
-}
-
-// Descriptor table of a launch (WS_DESC): a function of the layer geometry, the batch and the grid; built once per key on the
-// device by k_ws_build_desc and kept for the context's lifetime (8 samples of the 128^3 layers: 32 768 tiles = 1 MiB).
-const int* ws_desc_table(boa_ctx* ctx, const ConvArgs& a, int tiles_per_sample, int grid, int* row_out) {
-    std::vector<int> key = {-1,   a.t0, a.t1, a.t2, a.b0, a.b1, a.b2, a.w0, a.w1, a.w2, a.Cout, a.cy_fast, a.vw, a.ncy, a.N,  grid,
-                            a.Do, a.Ho, a.Wo, a.Di, a.Hi, a.Wi, a.s0, a.s1, a.s2, a.p0, a.p1,   a.p2,      a.h0, a.h1,  a.h2, a.xs};
-    // rows: an upper bound of a workgroup's tiles.  A run has at most tiles_per_sample / vw + 2 tiles (ws_run_table: the 8 XCD ranges
-    // differ by one tile, the runs inside a range by one more) and a workgroup executes ceil(N vw / grid) runs.  The tables live as long
-    // as the context (one per layer geometry, batch and grid: the tail batches of a volume add a few; <= ~150 MB for every batch size
-    // 1 .. 25 of one net geometry).
-    const int vper = (a.N * a.vw + grid - 1) / grid;
-    const int row = vper * (tiles_per_sample / a.vw + 2) + 1;
-    *row_out = row;
-    for (auto& e : ctx->ws_runs)
-        if (e.first == key) return (const int*)e.second;
-    // the row length is an upper bound of every workgroup's tile count: checked here against the host copy of the run table, so the
-    // builder kernel can neither truncate a row nor write past it (an error return instead of a device trap)
-    {
-        const std::vector<int>* runs_host = nullptr;
-        for (size_t i = 0; i < ctx->ws_runs.size(); ++i)
-            if (ctx->ws_runs[i].second == (const void*)a.runs) runs_host = &ctx->ws_runs_host[i];
-        if (!runs_host || runs_host->size() < (size_t)a.vw * 8) return nullptr;
-        for (int b = 0; b < grid; ++b) {
-            long long my = 0;
-            for (long long v = b; v < (long long)a.N * a.vw; v += grid) my += (*runs_host)[(size_t)(v % a.vw) * 8];
-            if (my > row - 1) {
-                boa_set_error("conv_ws: workgroup %d walks %lld tiles, descriptor rows hold %d", b, my, row - 1);
-                return nullptr;
-            }
-        }
-    }
-    void* dev = nullptr;
-    const size_t bytes = (size_t)grid * row * 8 * sizeof(int);
-    if (hipMalloc(&dev, bytes) != hipSuccess) return nullptr;
-    hipLaunchKernelGGL(k_ws_build_desc, dim3((grid + 63) / 64), dim3(64), 0, ctx->stream, a, grid, row, (int*)dev);
-    ctx->ws_runs.emplace_back(std::move(key), dev);
-    ctx->ws_runs_host.emplace_back();
-    ctx->ws_desc_bytes += bytes;
-    return (const int*)dev;
-}
-
 int launch_conv_ws(boa_ctx* ctx, const ConvArgs& a_in, const ConvTile& t, double flops, double bytes, bool x3) {
-    const ConvArgs& a0 = a_in;
-    // tiles of one sample; its virtual workgroups (batch-invariant statistics, see tile_walk); physical grid
-    const int total = t.tiles[0] * t.tiles[1] * t.tiles[2] * (a0.Cout / 32);
-    const int vw = conv_ws_vw(total, ctx->cu_count);
-    const int grid = (int)std::min<long long>((long long)vw * a0.N, ctx->cu_count);
-    const int taps = a0.k0 * a0.k1 * a0.k2;
-    const int HV = t.h[0] * (t.xs > 0 ? t.xs : t.h[1] * t.h[2]);
-    const int resident = conv_ws_resident(HV, taps, (a0.C0 + a0.C1) / 16, a0.Cout) ? 1 : 0;
-    BOA_REQUIRE(!x3 || a0.Cout * 4 <= 2048, "conv_ws (split precision): Cout %d exceeds the 512-entry bias table kept in LDS behind the halo buffers", a0.Cout);
-    BOA_REQUIRE((double)a0.Di * a0.Hi * a0.Wi <= 16777216.0 && std::max(a0.C0, a0.C1) * 2 < 16777216,
-                "conv_ws: more than 2^24 input voxels per sample (24-bit offset multiply)");
-    BOA_REQUIRE((double)a0.Di * a0.Hi * a0.Wi * std::max(a0.C0, a0.C1) * 2.0 < 4294967296.0,
-                "conv_ws: one sample of the input exceeds 4 GiB (32-bit voxel offsets)");
-#ifdef WS_WITH_TRACE
-    static const bool want_trace = getenv("BOA_WS_TRACE") != nullptr;
-#else
-    static const bool want_trace = false;
-    static const bool trace_note = getenv("BOA_WS_TRACE") != nullptr && (fprintf(stderr, "[boa_hip] BOA_WS_TRACE needs a library built with -DWS_WITH_TRACE (tools/build_alt.sh trace -DWS_WITH_TRACE)\n"), true);
-    (void)trace_note;
-#endif
     ConvArgs a = a_in;
-    a.trace = nullptr;
-    // statistics slots: one per (workgroup, consumer wave); waves that never touch an (n, cout chunk) leave zeros
-    a.nslots = 4 * vw;  // = conv_nblk(t, cu_count, Cout): the stride the caller allocated and k_norm_finalize reads
-    a.vw = vw;
-    a.vstep_n = grid / vw;
-    a.vstep_j = grid % vw;
     a.ncy = a.Cout / 32;
     a.cy_fast = conv_ws_cy_fast(a.C0 + a.C1, a.Cout, t.R) ? 1 : 0;
-    a.runs = ws_run_table(ctx, a, total, vw);
-    BOA_REQUIRE(a.runs != nullptr, "conv_ws: could not allocate the run table");
-    const int* desc = nullptr;
-    int desc_row = 0;
-    desc = ws_desc_table(ctx, a, total, grid, &desc_row);
-    BOA_REQUIRE(desc != nullptr, "conv_ws: could not allocate the tile descriptor table");
-    // a.partials must be all zero on entry: the callers zero it once (allocation / test seam) and k_norm_finalize
-    // clears what it has read, so no per-launch memset is needed
-    if (want_trace) {
-        hipMalloc(&a.trace, WS_TRACE_SLOTS * 8);
-        hipMemsetAsync(a.trace, 0, WS_TRACE_SLOTS * 8, ctx->stream);
-        const unsigned long long blk = (unsigned long long)std::min(std::max(atoi(getenv("BOA_WS_TRACE")), 0), grid - 1);
-        hipMemcpyAsync(a.trace + WS_TRACE_SLOTS - 5, &blk, 8, hipMemcpyHostToDevice, ctx->stream);
-        hipStreamSynchronize(ctx->stream);
-    }
+    const int total = t.tiles[0] * t.tiles[1] * t.tiles[2] * a.ncy;  // tiles of one sample
+    const int taps = a.k0 * a.k1 * a.k2;
+    const int HV = t.h[0] * (t.xs > 0 ? t.xs : t.h[1] * t.h[2]);
+    const int resident = conv_ws_resident(HV, taps, (a.C0 + a.C1) / 16, a.Cout) ? 1 : 0;
+    BOA_REQUIRE(!x3 || a.Cout * 4 <= 2048, "conv_ws (split precision): Cout %d exceeds the 512-entry bias table kept in LDS behind the halo buffers", a.Cout);
+    ConvSched s;
+    BOA_TRY(conv_sched_prepare(ctx, a, total, "conv_ws", &s));
     KernelTimer tm(ctx, BOA_K_CONV_MFMA, flops, bytes);
     ctx->counters[x3 ? BOA_CNT_CONV_X3 : BOA_CNT_CONV_WS]++;
     int rc;
     switch (t.R + (x3 ? 8 : 0)) {
-        case 4: rc = launch_ws_r<4, false>(ctx, a, t, total, grid, resident, desc, desc_row); break;
-        case 2: rc = launch_ws_r<2, false>(ctx, a, t, total, grid, resident, desc, desc_row); break;
-        case 1: rc = launch_ws_r<1, false>(ctx, a, t, total, grid, resident, desc, desc_row); break;
-        case 12: rc = launch_ws_r<4, true>(ctx, a, t, total, grid, resident, desc, desc_row); break;
-        case 10: rc = launch_ws_r<2, true>(ctx, a, t, total, grid, resident, desc, desc_row); break;
-        case 9: rc = launch_ws_r<1, true>(ctx, a, t, total, grid, resident, desc, desc_row); break;
+        case 4: rc = launch_ws_r<4, false>(ctx, a, t, total, resident, s); break;
+        case 2: rc = launch_ws_r<2, false>(ctx, a, t, total, resident, s); break;
+        case 1: rc = launch_ws_r<1, false>(ctx, a, t, total, resident, s); break;
+        case 12: rc = launch_ws_r<4, true>(ctx, a, t, total, resident, s); break;
+        case 10: rc = launch_ws_r<2, true>(ctx, a, t, total, resident, s); break;
+        case 9: rc = launch_ws_r<1, true>(ctx, a, t, total, resident, s); break;
         default:
             boa_set_error("conv_ws: unsupported R=%d", t.R);
             rc = BOA_EINVAL;
     }
     tm.stop();
-    if (want_trace && a.trace) {
-        // debug: print the per-event deltas (cycles) of block 0: consumer wave 0 then producer wave 4
-        static unsigned long long host[WS_TRACE_SLOTS];
-        hipStreamSynchronize(ctx->stream);
-        hipMemcpy(host, a.trace, sizeof(host), hipMemcpyDeviceToHost);
-        hipFree(a.trace);
-        fprintf(stderr, "[ws-clock] Cin=%d Cout=%d in=%d: %llu cycles in %llu x10ns -> %.3f GHz, %d tiles per block\n", a0.C0 + a0.C1, a0.Cout, a0.Di,
-                host[WS_TRACE_SLOTS - 2] - host[WS_TRACE_SLOTS - 4], host[WS_TRACE_SLOTS - 1] - host[WS_TRACE_SLOTS - 3],
-                (double)(host[WS_TRACE_SLOTS - 2] - host[WS_TRACE_SLOTS - 4]) / (10.0 * (double)(host[WS_TRACE_SLOTS - 1] - host[WS_TRACE_SLOTS - 3])),
-                (total * a0.N + grid - 1) / grid);
-        for (int role = 0; role < 2; ++role) {
-            const unsigned long long* h = host + role * (WS_TRACE_SLOTS / 2);
-            fprintf(stderr, "[ws-trace] %s Cin=%d Cout=%d in=%d R=%d:", role ? "producer" : "consumer", a0.C0 + a0.C1, a0.Cout, a0.Di, t.R);
-            const int lo = 40, hi = 40 + (role ? 50 : 80);
-            for (int i = lo; i < hi && h[i]; ++i)
-                fprintf(stderr, " %d:%llu", (int)(h[i] >> 56), (h[i] & 0x00ffffffffffffffull) - (h[i - 1] & 0x00ffffffffffffffull));
-            fprintf(stderr, "\n");
-        }
-    }
+    conv_sched_trace_dump(ctx, a, s, total, t.R);
     if (rc) return rc;
     BOA_HIP_TRY(hipGetLastError());
     return BOA_OK;

@@ -104,7 +104,7 @@ __device__ __forceinline__ void next_tile(const ConvArgs& p, TileCoord& c) {
 // speed.  Workgroup b is observed to run on XCD b % 8 (each XCD has a private 4 MiB L2): a sample's tile list is cut into 8
 // contiguous ranges, one per XCD (j % 8 == b % 8), and the virtual workgroups of an XCD take contiguous runs of that range,
 // so the halos an XCD re-reads are the ones its own L2 just fetched.  The runs (first tile's coordinates + length) are a
-// host-built table per layer geometry (`ws_run_table`): starting a run costs a few scalar loads, no divisions.
+// host-built table per layer geometry (conv_sched.h: `conv_sched_runs`): starting a run costs a few scalar loads, no divisions.
 struct TileSeq {
     int n, j;  // current virtual workgroup: sample, index within the sample (statistics slot = 4 j + wave)
     int left;  // tiles left in its run, the current one included

@@ -209,6 +209,38 @@ def test_conv_form(ctx, case):
             assert np.array_equal(three["ss16"][n], one["ss16"][0]), f"ss16 of sample {n} differs"
 
 
+def _trim_cases():
+    """The fewest-MAC case of (ws, fp16), (ns, fp16), (ws, split) and of the ws cases in which a workgroup's run crosses a sample boundary."""
+    cases = cf.conv_cases()
+    picks = [lambda c: c["key"][0] == "ws" and c["mode"] == "fp16", lambda c: c["key"][0] == "ns" and c["mode"] == "fp16",
+             lambda c: c["key"][0] == "ws" and c["mode"] == "split", lambda c: c["key"][0] == "ws" and c["crossing"]]
+    chosen = [min((c for c in cases if pick(c)), key=lambda c: c["macs"]) for pick in picks]
+    return list({c["id"]: c for c in chosen}.values())
+
+
+@pytest.mark.parametrize("case", _trim_cases(), ids=lambda c: c["id"])
+def test_conv_tables_rebuilt_after_trim(ctx, case):
+    """boa_trim releases the descriptor tables of the launches so far (the run tables stay): a launch after it, at the same batch and at
+    another, builds them again and gives every sample the bits of the first run."""
+    from boa_hip._lib import check
+    d = _conv_inputs(case)
+    fp16 = case["mode"] == "fp16"
+    u = np.uint16 if fp16 else np.uint32
+    first = None
+    for step in (1, "trim", 1, cf.BATCH, "trim", cf.BATCH):
+        if step == "trim":
+            check(ctx.lib.boa_trim(ctx.h))
+            continue
+        got = _conv_launch(ctx, case, d, step)
+        first = first or got
+        assert got["plan"][:29] == case["plan"][:29]
+        for n in range(step):
+            assert np.array_equal(got["raw"][n].view(u), first["raw"][0].view(u)), f"N = {step}: sample {n} differs from the first run"
+            assert np.array_equal(got["ss"][n].view(np.uint32), first["ss"][0].view(np.uint32)), f"N = {step}: (scale, shift) of sample {n} differ"
+            if fp16:
+                assert np.array_equal(got["ss16"][n], first["ss16"][0]), f"N = {step}: ss16 of sample {n} differs"
+
+
 # ---- transposed convs ------------------------------------------------------------------------------------------------------------------
 # Over the bar by the bar's derivation, not by the kernel: tau_x3 was measured on layers of K >= 32.  At K = Cin = 16 a voxel whose
 # normalised inputs mostly sit on the LeakyReLU's negative side (|y| ~ 0.01 |x|, below 2^-3) has A = sum |w| |y| of a few 1e-2 while the

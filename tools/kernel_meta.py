@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
 """Per-kernel register / spill / LDS metadata of the gfx950 code objects embedded in csrc/*.o (or any hipcc -c output).
 
-    tools/kernel_meta.py body-and-organ-analysis_amd/csrc/conv_ws.o [more.o ...] [--spills] [--check PATTERN ...]
+    tools/kernel_meta.py body-and-organ-analysis_amd/csrc/conv_ws.o [more.o ...] [--spills] [--code-hash] [--check PATTERN ...]
 
 --spills      only kernels with a non-zero spill count
+--code-hash   one line per kernel, sorted by name: symbol size and sha256 of its bytes in the code object's .text, then the register /
+              LDS / scratch figures -- two builds whose listings are equal run the same machine code (a refactor of host code: diff them)
 --check P ... exit 1 if a kernel whose (demangled) name contains one of the patterns spills (the Makefile's gate for the hot
               instantiations: a spilled VGPR in an MFMA loop is scratch traffic on the critical path)
 """
+import hashlib
 import os
 import re
 import subprocess
@@ -46,9 +49,27 @@ def kernels(co):
     return out
 
 
+def code_hashes(co):
+    """{mangled kernel name: (symbol size, sha256 of its bytes)} from the code object's .text"""
+    text = co + ".text"
+    subprocess.check_call([f"{LLVM}/llvm-objcopy", "-O", "binary", "--only-section=.text", co, text])
+    with open(text, "rb") as f:
+        code = f.read()
+    base = int(re.search(r"\.text\s+PROGBITS\s+([0-9a-f]+)", subprocess.check_output([f"{LLVM}/llvm-readelf", "-S", "-W", co], text=True)).group(1), 16)
+    out = {}
+    for line in subprocess.check_output([f"{LLVM}/llvm-readelf", "-s", "-W", co], text=True).splitlines():
+        f = line.split()
+        if len(f) >= 8 and f[3] == "FUNC":
+            at, size = int(f[1], 16) - base, int(f[2])
+            assert 0 <= at and at + size <= len(code), line
+            out[f[7]] = (size, hashlib.sha256(code[at:at + size]).hexdigest())
+    return out
+
+
 def main():
     args = sys.argv[1:]
     only_spills = "--spills" in args
+    want_hash = "--code-hash" in args
     pats = []
     if "--check" in args:
         i = args.index("--check")
@@ -58,7 +79,15 @@ def main():
     bad = 0
     with tempfile.TemporaryDirectory() as tmp:
         for f in files:
-            for k in kernels(code_object(f, tmp)):
+            co = code_object(f, tmp)
+            if want_hash and co is not None:
+                sym = code_hashes(co)
+                for k in sorted(kernels(co), key=lambda k: k["pretty"]):
+                    if not pats or any(p in k["pretty"] for p in pats):
+                        print(f"{os.path.basename(f)} {k['pretty']} size {sym[k['name']][0]} sha256 {sym[k['name']][1]} vgpr {k['vgpr']} agpr {k['agpr']} "
+                              f"sgpr {k['sgpr']} vspill {k['vspill']} sspill {k['sspill']} scratch {k['scratch']} lds {k['lds']}")
+                continue
+            for k in kernels(co):
                 if only_spills and not (k["vspill"] or k["sspill"]):
                     continue
                 hot = any(p in k["pretty"] for p in pats)
